@@ -11,12 +11,15 @@ Unit of work = one output keypoint (extracted, described, matched).  value = key
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL), frames sharded by rank, no data-path
 collective (weak scaling: B frames per GPU per step); barrier + synchronize around the timed region, max over ranks.
 
-Extra objects on the JSON line:
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, runs W warm-up steps, times exactly N steps (one block), optionally
+writes the last step's outputs (--dump-outputs DIR) and prints the headline line.  Everything else is measured with --full
+(which also times --repeat = 5 blocks and reports the median one); extra objects on the JSON line then include:
   roofline      dominant kernel (k_fast_nms): algorithmic bytes (every pyramid pixel read once = 950 532 B/frame at
                 640x480) x frames per launch / mean launch duration measured with hipEvents recorded on
                 the launch stream inside the timed region; peak = 8 TB/s HBM3E.
   cpu_baseline  the CPU oracle (oracle/, kind "port": the reference cannot be built here) timed single-threaded on
                 rank 0 on a bounded sample of the same frames, reference-faithful call pattern (variant 1).
+  multi_gpu, pairs10k_strong, host_fed, batch_sweep, ...
 """
 import argparse
 import importlib
@@ -1070,6 +1073,35 @@ def extra_single_frame(afv, device, reps=200):
     return out
 
 
+DUMP_FRAMES = 128      # --dump-outputs: frames in the fixed seeded sample whose keypoints, descriptors and matches are written
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, kps, desc, n_out, match, nmatch):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float .npy files, so that two builds can be
+    compared output for output.  keypoint_counts / match_counts: every frame / frame pair.  For a fixed seeded sample of at most
+    DUMP_FRAMES frames (sample_frames, ascending), the valid rows of each, concatenated in frame order: keypoints (x, y, size, angle,
+    response, octave, class_id), descriptors (the 32 bytes as values 0..255) and matches (per keypoint of frame t: the index of its
+    match in frame t-1, or -1)."""
+    import torch
+    B = n_out.shape[0]
+    idx = np.sort(np.random.default_rng(0).choice(B, min(B, DUMP_FRAMES), replace=False))
+    sel = torch.from_numpy(idx).to(kps.device)
+    n = n_out.cpu().numpy()
+    k, d, m = (t.index_select(0, sel).cpu().numpy() for t in (kps, desc, match))
+    rows = [(i, int(n[f])) for i, f in enumerate(idx)]
+    kp = np.concatenate([k[i, :c] for i, c in rows])
+    out = {"keypoint_counts": n.astype(np.float64), "match_counts": nmatch.cpu().numpy().astype(np.float64),
+           "sample_frames": idx.astype(np.float64),
+           "keypoints": np.concatenate([kp[:, :5], np.ascontiguousarray(kp[:, 5:]).view(np.int32).astype(np.float32)], axis=1),
+           "descriptors": np.concatenate([d[i, :c] for i, c in rows]).astype(np.float32),
+           "matches": np.concatenate([m[i, :c] for i, c in rows]).astype(np.float32)}
+    assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _self_launch(args):
     """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU"""
     import socket
@@ -1087,7 +1119,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeat", type=int, default=5, help="timed blocks of --steps steps each; the line reports the median block (value_min / value_max: the others)")
+    ap.add_argument("--full", action="store_true", help="orb32: besides the headline, measure and report everything else (stage events, "
+                    "roofline, profile-derived figures, multi_gpu, the secondary workloads, the CPU baseline); --repeat defaults to 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="orb32: after the timed steps write the outputs of the last step "
+                    "(per-frame counts; keypoints, descriptors and matches of a fixed seeded sample of frames) as DIR/<name>.npy")
+    ap.add_argument("--repeat", type=int, default=None, help="timed blocks of --steps steps each (default 1; 5 with --full); the line reports "
+                    "the median block (value_min / value_max: the others)")
     ap.add_argument("--batch", type=int, default=512, help="frames per GPU per step")
     ap.add_argument("--cpu-frames", type=int, default=256, help="frames in the bounded CPU-baseline sample (0 = skip)")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-stage hipEvents")
@@ -1111,6 +1148,10 @@ def main():
     ap.add_argument("--jobs", type=int, default=10000, help="pairs10k: pair jobs per step (whole job, all GPUs)")
     ap.add_argument("--bcast-reps", type=int, default=3, help="pairs10k: repetitions of the table broadcast")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "orb32":
+        ap.error("--dump-outputs: orb32 only")
+    if args.repeat is None:
+        args.repeat = 5 if args.full else 1
     if args.lib:
         importlib.import_module("anyfeature-vslam_amd._lib").use_library(args.lib)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and args.workload != "akaze61":
@@ -1204,7 +1245,8 @@ def main():
     # the library's stage events (roofline.achieved, stage_ms_per_step) are recorded on every PROF_EVERY-th step of the timed region:
     # an event pair per stage and chunk costs about 3 % of a step when every step carries them
     prof_steps = (args.steps + PROF_EVERY - 1) // PROF_EVERY
-    if not args.no_profile:
+    profile = args.full and not args.no_profile
+    if profile:
         ctx.profile_enable(True, every=PROF_EVERY)
     # The timed region, `repeat` times over: every block is EXACTLY `steps` steps between two barriers (the contract's bracket), the
     # reported value is the MEDIAN block's (one 51 ms window moves by a few per cent with a clock-ramp hiccup), the slowest and
@@ -1218,9 +1260,11 @@ def main():
             step()
         barrier()
         block_dt.append(time.perf_counter() - t0)
-        if blk == 0 and not args.no_profile:
+        if blk == 0 and profile:
             stages = ctx.profile_read()
             ctx.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kps, desc, n_out, match, nmatch)
 
     kp_step = int(n_out.sum().item())
     nm_step = int(nmatch.sum().item())
@@ -1241,9 +1285,9 @@ def main():
 
     # collective, every rank: who ran where, and config #4 as the STRONG-scaling companion of this weak-scaling line (10 000 jobs in all,
     # table broadcast from rank 0 through the C-ABI communicator) - at N = 1 the same code path gives the single-GPU figure
-    ident = multi_gpu_identity(rank, world, local, dev, dist, args.backend, None, args.single_device)
+    ident = multi_gpu_identity(rank, world, local, dev, dist, args.backend, None, args.single_device) if args.full else None
     strong = None
-    if world > 1 and not args.no_extras:   # (N = 1: after the other sub-runs - initialising RCCL ahead of the host-fed pipeline figure
+    if args.full and world > 1 and not args.no_extras:   # (N = 1: after the other sub-runs - initialising RCCL ahead of the host-fed figure
         try:                               # costs that figure a third of its PCIe rate on this box: 4.0 -> 6.0 ms per 512 frames, measured)
             strong = pairs_run(args, rank, world, local, dev, dist, 5, 2, False, False)
         except Exception as e:
@@ -1263,8 +1307,9 @@ def main():
             "keypoints_per_ms": total_kp / dt / 1e3,
             "frames_per_s": B * world * args.steps / dt,
             "csrc_sha": _csrc_sha(),
-            "multi_gpu": ident,
         }
+        if ident:
+            out["multi_gpu"] = ident
         if stages:
             px = level_pixels(W, H)
             fh = stages["fast_nms"]
@@ -1376,7 +1421,7 @@ def main():
             # may exceed ms_per_step - these are not kernel durations (rocprof: profiles/rNN/kernel_stats_default.csv)
             out["stage_event_ms_per_step_summed_over_concurrent_streams"] = {kk: (v["total_ms"] / prof_steps) for kk, v in stages.items()}
             out["stage_events_on_steps"] = "%d of %d timed steps (every %d-th)" % (prof_steps, args.steps, PROF_EVERY)
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # extraction alone, device-resident (the yardstick of the host-fed pipeline)
             barrier()
             t1 = time.perf_counter()
@@ -1401,7 +1446,7 @@ def main():
                     out[key] = fn(afv, local)
                 except Exception as e:  # a secondary figure must never cost the headline line
                     out[key] = {"error": repr(e)[:300]}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             try:
                 strong = pairs_run(args, rank, world, local, dev, dist, 5, 2, False, False)
             except Exception as e:
@@ -1413,9 +1458,9 @@ def main():
                 "matches_per_job": strong["config"]["matches_per_job"], "broadcast": strong["broadcast"], "covisible": strong["covisible"],
                 "rccl_ranks_seen": strong["multi_gpu"]["rccl_ranks_seen"],
                 "note": "BASELINE.json configs[3] on the same ranks: total work fixed, table replicated with one broadcast from rank 0"}
-        if args.cpu_frames > 0 and world == 1:
+        if args.full and args.cpu_frames > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(afv, args.cpu_frames, seed0)
-        elif args.cpu_frames > 0:
+        elif args.full and args.cpu_frames > 0:
             out["cpu_baseline"] = None
         emit(out)
     if world > 1:

@@ -501,7 +501,7 @@ def test_bench_two_ranks_on_one_device_through_the_self_launch(workload):
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--single-device", "--steps", "2", "--warmup", "1",
-           "--cpu-frames", "0", "--no-extras", "--no-profile", "--workload", workload]
+           "--full", "--cpu-frames", "0", "--no-extras", "--no-profile", "--workload", workload]
     cmd += ["--batch", "16"] if workload == "orb32" else ["--keyframes", "64", "--jobs", "400", "--bcast-reps", "1"]
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):

@@ -55,12 +55,12 @@ print(json.dumps(res))
 PYEOF
 
 echo "== default bench (the BENCH line) + kernel stats of the same command"
-cd "$ROOT" && $PY bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; cd /tmp
-timeout 400 rocprofv3 --kernel-trace --stats -d "$OUT/stats_default" -o st --output-format csv -- $PY "$ROOT/bench.py" --cpu-frames 0 --no-extras > /dev/null 2>&1
+cd "$ROOT" && $PY bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"; cd /tmp
+timeout 400 rocprofv3 --kernel-trace --stats -d "$OUT/stats_default" -o st --output-format csv -- $PY "$ROOT/bench.py" --full --cpu-frames 0 --no-extras > /dev/null 2>&1
 cp "$OUT"/stats_default/*kernel_stats.csv "$OUT/kernel_stats_default.csv" 2>/dev/null || cp "$OUT"/stats_default/*/*kernel_stats.csv "$OUT/kernel_stats_default.csv"
 
 echo "== the dominant kernel in the launch shape bench.py's roofline quotes: one stream, one chunk (bench.py --no-split), rocprof beside the hipEvents"
-timeout 400 rocprofv3 --kernel-trace --stats -d "$OUT/stats_single" -o st --output-format csv -- $PY "$ROOT/bench.py" --no-split --cpu-frames 0 --no-extras --no-profile > /dev/null 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats -d "$OUT/stats_single" -o st --output-format csv -- $PY "$ROOT/bench.py" --full --no-split --cpu-frames 0 --no-extras --no-profile > /dev/null 2>&1
 cp "$(find "$OUT/stats_single" -name "*kernel_stats.csv" | head -1)" "$OUT/kernel_stats_single_stream.csv"
 cd "$ROOT" && $PY tools/kernel_stats_json.py "$OUT/kernel_stats_single_stream.csv" "$OUT/kernel_stats_single_stream.json" 512; cd /tmp
 rm -rf "$OUT/stats_single"
