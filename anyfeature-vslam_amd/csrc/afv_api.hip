@@ -1110,6 +1110,7 @@ extern "C" int afv_orb_compute(afv_ctx *c, const uint8_t *gray, int width, int h
         const float cx = rintf(k.x * L.inv_scale), cy = rintf(k.y * L.inv_scale);
         if (!(cx >= 0.f && cx <= (float)L.w && cy >= 0.f && cy <= (float)L.h)) return AFV_EINVAL;  // (also refuses NaN)
     }
+    c->prof = false;  // no stage events: a profiled extract before this call must not leave the flag set for the pyramid launch below
     if (n == 0) return AFV_OK;
     return guarded(c, [&]() -> int {
         struct Quiesce {

@@ -129,9 +129,10 @@ __device__ int block_excl_scan2(int *a, int na, int *u, int nu, int *tmp) {
 }
 
 // k-th largest over a histogram hist[0..nbins): returns the bin b such that sum(hist[b+1..]) < k <= sum(hist[b..]),
-// and *above = sum(hist[b+1..]).  hist is destroyed.  Requires sum(hist) >= k >= 1.
+// *above = sum(hist[b+1..]) and *in_bin = hist[b], all three read from tmp[3..5] (written before the last barrier), so they are uniform
+// even when the caller rewrites hist right after the return.  Requires sum(hist) >= k >= 1.
 template <int ST>
-__device__ int block_kth_from_top(int *hist, int nbins, int k, int *above, int *tmp) {
+__device__ int block_kth_from_top(int *hist, int nbins, int k, int *above, int *in_bin, int *tmp) {
     int *ws = tmp + 16;
     // suffix sums via a prefix scan of the reversed index space
     const int per = (nbins + ST - 1) / ST;
@@ -152,6 +153,7 @@ __device__ int block_kth_from_top(int *hist, int nbins, int k, int *above, int *
         for (int i = b; i < e; ++i) {
             const int h = hist[nbins - 1 - i];
             if (cum < k && k <= cum + h) {
+                tmp[3] = h;
                 tmp[4] = nbins - 1 - i;
                 tmp[5] = cum;
             }
@@ -161,6 +163,7 @@ __device__ int block_kth_from_top(int *hist, int nbins, int k, int *above, int *
     __syncthreads();
     const int bin = tmp[4];
     *above = tmp[5];
+    *in_bin = tmp[3];
     __syncthreads();
     return bin;
 }
@@ -289,9 +292,11 @@ __device__ __forceinline__ void select_quadtree_body(const Geo *__restrict__ geo
         __syncthreads();
         FOR_CAND({ atomicAdd(&hist[float_key(r) >> 20], 1); })
         __syncthreads();
-        int above;
-        const int bin = block_kth_from_top<ST>(hist, 4096, k, &above, tmp);
-        const int in_bin = hist[bin], kk = k - above;  // the kk-th largest key of the bin is the threshold
+        int above, in_bin;
+        const int bin = block_kth_from_top<ST>(hist, 4096, k, &above, &in_bin, tmp);
+        const int kk = k - above;  // the kk-th largest key of the bin is the threshold
+        // in_bin comes from tmp[3], not hist[bin]: the radix fallback zeroes hist[0..2047] without a barrier first, so a late wavefront
+        // reading hist[bin] (bins < 2048: negative responses) could see 0 and take the exact branch alone
         if (in_bin <= SEL_EXACT) {  // uniform
             FOR_CAND({
                 const uint32_t key = float_key(r);
@@ -331,8 +336,8 @@ __device__ __forceinline__ void select_quadtree_body(const Geo *__restrict__ geo
                 if ((key & mask) == prefix) atomicAdd(&hist[(key >> sh) & (nb - 1)], 1);
             })
             __syncthreads();
-            int above;
-            const int bin = block_kth_from_top<ST>(hist, nb, k, &above, tmp);
+            int above, in_bin;
+            const int bin = block_kth_from_top<ST>(hist, nb, k, &above, &in_bin, tmp);
             k -= above;
             prefix |= (uint32_t)bin << sh;
             mask |= (uint32_t)(nb - 1) << sh;

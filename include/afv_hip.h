@@ -92,8 +92,10 @@ int afv_orb_extract(afv_ctx *ctx, const uint8_t *gray, int width, int height, in
  *                    ascending level order: keypoints with angle and response, no descriptors.
  *   afv_orb_compute  computeDescriptors: cv::ORB::compute (:42-53) for n caller-given keypoints - each described in its own octave at
  *                    cvRound(pt / scale) with its own angle, on the pyramid rebuilt from `gray` (cv::ORB::compute rebuilds levels 0 .. max
- *                    octave of its keypoints).  desc32[n][32] in the order of kps.  Keypoints whose octave is not a level of the context
- *                    or whose centre falls off their level image: AFV_EINVAL, nothing is written. */
+ *                    octave of its keypoints).  desc32[n][32] in the order of kps.  A keypoint is accepted when its octave is a level of
+ *                    the context and its rounded centre (cx, cy) = cvRound(pt / scale) lies in 0 <= cx <= w, 0 <= cy <= h of that level: one
+ *                    column / row past the last pixel is still described, as by the CPU baseline.  Any
+ *                    other keypoint (NaN coordinates included): AFV_EINVAL, nothing is written. */
 int afv_orb_detect(afv_ctx *ctx, const uint8_t *gray, int width, int height, int stride_bytes, afv_keypoint *kps, int cap, int *n_out);
 int afv_orb_compute(afv_ctx *ctx, const uint8_t *gray, int width, int height, int stride_bytes, const afv_keypoint *kps, int n,
                     uint8_t *desc32);

@@ -855,7 +855,8 @@ int afvo_orb_extract(const afvo_params *p, const u8 *gray, int w, int h, int str
  * cv::ORB::compute = detectAndCompute(..., useProvidedKeypoints = true) - levels 0 .. (octave of the keypoints) are rebuilt from the image and
  * blurred, every keypoint is described at cvRound(pt * (1 / scale)) of its own octave with the angle it carries (orb.cpp computeOrbDescriptors);
  * KeyPointsFilter::runByImageBorder with edgeThreshold 0 (Feature_orb32.cpp:23) removes nothing.  desc32[n][32] in the order of kps.
- * Returns -1 for a keypoint whose octave is not a level or whose centre lies off its level image (the sampling would leave the apron). */
+ * Returns -1 for a keypoint whose octave is not a level or whose rounded centre lies outside 0..w x 0..h of its level (the sampling would
+ * leave the apron), or whose coordinates are not finite. */
 int afvo_orb_compute(const afvo_params *p, const u8 *gray, int w, int h, int stride, const afvo_keypoint *kps, int n, u8 *desc32) {
     const int nl = p->nlevels;
     if (nl < 1 || nl > AFVO_MAX_LEVELS) return -1;
@@ -869,6 +870,8 @@ int afvo_orb_compute(const afvo_params *p, const u8 *gray, int w, int h, int str
         const int L = kps[i].octave;
         if (L < 0 || L >= nl) { rc = -1; break; }
         const float inv = 1.f / ls[L];
+        /* NaN / inf: lrintf's result is unspecified (truncated to int it can come out as 0, a centre on the level): refused */
+        if (!isfinite(kps[i].x) || !isfinite(kps[i].y)) { rc = -1; break; }
         const int cx = cv_round_f(kps[i].x * inv), cy = cv_round_f(kps[i].y * inv);
         if (cx < 0 || cx > lw[L] || cy < 0 || cy > lh[L]) { rc = -1; break; }
         if (!bb[L]) bb[L] = faithful_compute_level(gray, w, h, stride, lw, lh, L);

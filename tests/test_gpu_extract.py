@@ -214,6 +214,87 @@ def test_compute_refuses_keypoints_it_cannot_describe(gpu_ctx, frames, afv):
             gpu_ctx.compute(img, bad)
 
 
+def _edge_keypoints(scales, lw, lh):
+    """keypoints whose rounded centres (float32 pt * (1 / scale), round half to even: cvRound) are 0, w - 1, w, h - 1, h of every level,
+    plus centres that land exactly on n + 0.5 (both parities of n, and w + 0.5 / h + 0.5) where the rounding rule decides.  Returns the
+    accepted keypoints and, separately, keypoints whose centre is w + 1 / h + 1."""
+    kp_dtype = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"),
+                         ("class_id", "<i4")])
+
+    def coord(target, scale):
+        """a float32 coordinate whose product with the level's float32 inverse scale is exactly `target`"""
+        inv = np.float32(1) / np.float32(scale)
+        x = np.float32(np.float32(target) * np.float32(scale))
+        for _ in range(256):
+            p = np.float32(x * inv)
+            if p == np.float32(target):
+                return x
+            x = np.nextafter(x, np.float32(np.inf) if p < target else np.float32(-np.inf), dtype=np.float32)
+        return None
+
+    good, bad = [], []
+    angles = [0.0, 45.3, 133.0, 271.9, 359.5]
+    for l, s in enumerate(scales):
+        w, h = lw[l], lh[l]
+        tx = [0, 1, w - 1, w, 2.5, 3.5, w - 1.5, w - 0.5, w + 0.5]
+        ty = [0, h - 1, h, 1.5, h - 0.5, h + 0.5]
+        pts = [(x, y) for x in tx for y in (0, h // 2, h)] + [(x, y) for x in (0, w // 2, w) for y in ty]
+        for i, (x, y) in enumerate(pts):
+            fx, fy = coord(x, s), coord(y, s)
+            if fx is None or fy is None:  # no float32 coordinate lands exactly there at this scale
+                continue
+            inv = np.float32(1) / np.float32(s)
+            cx, cy = np.rint(np.float32(fx * inv)), np.rint(np.float32(fy * inv))
+            (good if cx <= w and cy <= h else bad).append((fx, fy, angles[i % 5], l))
+        for x, y in ((w + 1, h // 2), (w // 2, h + 1), (w + 1, h + 1)):
+            bad.append((np.float32(x * s), np.float32(y * s), 10.0, l))  # w + 1 +- a few ulps: still rounds to w + 1
+    bad.append((np.float32(np.nan), np.float32(5), 0.0, 0))
+
+    def pack(rows):
+        k = np.zeros(len(rows), kp_dtype)
+        for i, (x, y, a, l) in enumerate(rows):
+            k[i] = (x, y, 31.0 * scales[l], a, 0.0, l, -1)
+        return k
+    return pack(good), pack(bad)
+
+
+@pytest.mark.parametrize("w,h", [(115, 115), (640, 480)])
+def test_compute_at_the_edges_of_every_level(gpu_ctx, oracle, afv, w, h):
+    """afv_orb_compute accepts a rounded centre 0 <= cx <= w, 0 <= cy <= h of the keypoint's level (the CPU baseline's rule): at 0, w - 1,
+    w, h - 1, h and on exact halves on every level, the descriptors equal the oracle's bit for bit; w + 1 / h + 1 are refused by both.
+    115 x 115 at 8 levels x 1.2: the top level is 32 x 32, the smallest a context takes (one reflection of the apron is just enough)."""
+    img = afv.synth.corners_frame(17, w, h) if w > 200 else afv.synth.noise_frame(5, w, h)
+    _, _, tr = oracle.orb_extract_trace(img)
+    if w == 115:
+        assert tr["lw"][7] == 32 and tr["lh"][7] == 32
+    good, bad = _edge_keypoints(tr["lscale"], tr["lw"], tr["lh"])
+    assert len(good) > 8 * 30 and len(bad) > 8 * 3
+    inv = np.float32(1) / np.asarray(tr["lscale"], np.float32)[bad["octave"]]
+    assert np.all(np.isnan(bad["x"]) | (np.rint(bad["x"] * inv) > np.asarray(tr["lw"])[bad["octave"]]) |
+                  (np.rint(bad["y"] * inv) > np.asarray(tr["lh"])[bad["octave"]]))
+    got = gpu_ctx.compute(img, good)
+    assert np.array_equal(got, oracle.orb_compute(img, good))
+    for i in range(len(bad)):
+        one = bad[i:i + 1]
+        with pytest.raises(RuntimeError):
+            oracle.orb_compute(img, one)
+        with pytest.raises(afv._lib.AfvError):
+            gpu_ctx.compute(img, np.concatenate([good[:3], one]))
+
+
+def test_compute_after_a_profiled_extract_records_no_stage(afv):
+    """afv_orb_compute leaves the stage profile alone, also right after an extract call that was profiled"""
+    img = afv.synth.corners_frame(1)
+    ctx = afv.Context()
+    ctx.profile_enable(True)
+    k, d = ctx.extract(img)
+    before = ctx.profile_read()
+    assert np.array_equal(ctx.compute(img, k), d)
+    after = ctx.profile_read()
+    assert after == before
+    ctx.close()
+
+
 def test_plugin_virtuals_one_by_one(afv, oracle):
     """detectKeypoints -> filterKeypoints -> computeDescriptors -> merge, as detectAndCompute composes them (Feature_orb32.cpp:11-18)"""
     ext = afv.FeatureExtractor_orb32(1000)
