@@ -1461,10 +1461,10 @@ static int afv_match_bow_impl(afv_ctx *c, const afv_match_job *jobs, int njobs, 
                 const float *angp = any_ori ? reinterpret_cast<const float *>(c->d_match + ang_off) : nullptr;
                 const int *np_ = reinterpret_cast<const int *>(c->d_match + n_off);
                 const int *pa_ = reinterpret_cast<const int *>(c->d_match + pa_off), *pb_ = reinterpret_cast<const int *>(c->d_match + pb_off);
-                afv_launch_match_topk(c->d_match + desc_off, np_, cap, pa_, pb_, i1 - i0, c->d_match + topk_off, i0, c->match_engine, nslices, c->d_slice, c->d_tickets, c->stream);
+                afv_launch_match_topk(c->d_match + desc_off, np_, cap, pa_, pb_, i1 - i0, c->d_match + topk_off, i0, c->match_engine, nslices, c->d_slice, c->d_tickets, 8, c->stream);
                 afv_launch_match_resolve(c->d_match + desc_off, angp, 1, np_, cap, pa_, pb_, i1 - i0, jobs[i0].th_low, jobs[i0].nnratio,
                                          jobs[i0].check_orientation != 0, reinterpret_cast<int *>(c->d_match + match_off),
-                                         reinterpret_cast<int *>(c->d_match + nm_off), c->d_match + topk_off, i0, resolve_engine_for(c, njobs), c->stream);
+                                         reinterpret_cast<int *>(c->d_match + nm_off), c->d_match + topk_off, i0, resolve_engine_for(c, njobs), 8, c->stream);
                 i0 = i1;
             }
             HIPCHK(c, hipGetLastError());
@@ -1630,10 +1630,11 @@ int afv_check_resolve_guard(afv_ctx *c, const int32_t *nmatches, int n) {
     return AFV_OK;
 }
 
-// core of the device-resident brute-force batch; angles as a strided float array (see afv_launch_match_resolve)
+// core of the device-resident brute-force batch; angles as a strided float array (see afv_launch_match_resolve); words = dwords per row of
+// d_desc (8: descriptors of up to 32 bytes, 16: 33 to 64 bytes, zero padded)
 int afv_match_pairs_core(afv_ctx *c, const uint8_t *d_desc, const float *d_ang, int ang_stride, const int32_t *d_n, int cap,
                          const int32_t *d_pair_a, const int32_t *d_pair_b, int npairs, float th_low, float nnratio,
-                         int check_orientation, int32_t *d_match, int32_t *d_nmatches, hipStream_t s) {
+                         int check_orientation, int32_t *d_match, int32_t *d_nmatches, hipStream_t s, int words) {
     c->prof = c->prof_every && (c->prof_tick_match++ % (unsigned)c->prof_every) == 0;
     // the small-batch path deals the column tiles of phase 1 to several workgroups per row tile (two 64-column tiles each): a single
     // pair then runs on 32 workgroups instead of 4, and the resolve kernel merges the slices' key records
@@ -1664,22 +1665,22 @@ int afv_match_pairs_core(afv_ctx *c, const uint8_t *d_desc, const float *d_ang, 
             hipStream_t ks = (k & 1) ? c->stream2 : s;
             {
                 StageTimer t_(c, AFV_STAGE_MATCH, ks, e0 - b0);
-                afv_launch_match_topk(d_desc, d_n, cap, d_pair_a, d_pair_b, e0 - b0, c->d_topk, b0, c->match_engine, nslices, c->d_slice, c->d_tickets, ks);
+                afv_launch_match_topk(d_desc, d_n, cap, d_pair_a, d_pair_b, e0 - b0, c->d_topk, b0, c->match_engine, nslices, c->d_slice, c->d_tickets, words, ks);
             }
             StageTimer t_(c, AFV_STAGE_MATCH_RESOLVE, ks, e0 - b0);
             afv_launch_match_resolve(d_desc, d_ang, ang_stride, d_n, cap, d_pair_a, d_pair_b, e0 - b0, th_low, nnratio, check_orientation,
-                                     d_match, d_nmatches, c->d_topk, b0, resolve_engine_for(c, npairs), ks);
+                                     d_match, d_nmatches, c->d_topk, b0, resolve_engine_for(c, npairs), words, ks);
         }
         HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
         HIPCHK(c, hipStreamWaitEvent(s, c->ev_join, 0));
     } else {
         {
             StageTimer t_(c, AFV_STAGE_MATCH, s, npairs);
-            afv_launch_match_topk(d_desc, d_n, cap, d_pair_a, d_pair_b, npairs, c->d_topk, 0, c->match_engine, nslices, c->d_slice, c->d_tickets, s);
+            afv_launch_match_topk(d_desc, d_n, cap, d_pair_a, d_pair_b, npairs, c->d_topk, 0, c->match_engine, nslices, c->d_slice, c->d_tickets, words, s);
         }
         StageTimer t_(c, AFV_STAGE_MATCH_RESOLVE, s, npairs);
         afv_launch_match_resolve(d_desc, d_ang, ang_stride, d_n, cap, d_pair_a, d_pair_b, npairs, th_low, nnratio, check_orientation, d_match,
-                                 d_nmatches, c->d_topk, 0, resolve_engine_for(c, npairs), s);
+                                 d_nmatches, c->d_topk, 0, resolve_engine_for(c, npairs), words, s);
     }
     {
         const hipError_t e = hipGetLastError();
@@ -1704,7 +1705,7 @@ extern "C" int afv_match_bruteforce_pairs_device(afv_ctx *c, const uint8_t *d_de
     HIPCHK(c, hipSetDevice(c->device));
     return afv_match_pairs_core(c, d_desc, d_kps ? &d_kps->angle : nullptr, (int)(sizeof(afv_keypoint) / sizeof(float)), d_n, cap,
                                 d_pair_a, d_pair_b, npairs, th_low, nnratio, check_orientation, d_match, d_nmatches,
-                                stream ? (hipStream_t)stream : c->stream);
+                                stream ? (hipStream_t)stream : c->stream, 8);
 }
 
 static int afv_match_l2_impl(afv_ctx *c, const float *desc1, int n1, const float *desc2, int n2, int dim, const uint8_t *valid1,
@@ -1840,7 +1841,7 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
         if (by_ref) {
             // MapPoint descriptors by reference (rows of a keyframe table): checked here, gathered on the device behind the upload
             const afv_table *qt = dev->qref_table;
-            if (qt->c != c || !dev->qref_slot || !dev->qref_idx || o.words != 8) return AFV_EINVAL;
+            if (qt->c != c || !dev->qref_slot || !dev->qref_idx || j.float_dim || j.desc_bytes != qt->desc_bytes) return AFV_EINVAL;
             for (int q = 0; q < j.nq; ++q) {
                 const int sl = dev->qref_slot[q];
                 if (sl < 0 || sl >= qt->nsets || dev->qref_idx[q] < 0 || dev->qref_idx[q] >= qt->h_n[sl]) return AFV_EINVAL;
@@ -1869,7 +1870,7 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
         offs[i].keys = b.reserve_scratch((size_t)std::max(j.nq, 1) * 64);  // 64-byte record / 8 keys per query
         offs[i].ncand = b.reserve_scratch((size_t)std::max(j.nq, 1) * 4);
         offs[i].ori = b.reserve_scratch((size_t)std::max(j.nq, 1) * 8);
-        if (dev && dev->qref_table && !dev->qdesc_dev) offs[i].qd = b.reserve_scratch((size_t)std::max(j.nq, 1) * 32);
+        if (dev && dev->qref_table && !dev->qdesc_dev) offs[i].qd = b.reserve_scratch((size_t)std::max(j.nq, 1) * dev->qref_table->words * 4);
         if (!dev) {
             offs[i].cptr = b.reserve_scratch(((size_t)j.grid_cols * j.grid_rows + 1) * 4);
             offs[i].cent = b.reserve_scratch((size_t)std::max(j.n, 1) * 16);
@@ -1956,7 +1957,7 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
     if (dev && dev->qref_table && !dev->qdesc_dev) {
         const afv_table *qt = dev->qref_table;
         afv_launch_frame_gather(qt->d_desc, qt->d_n, qt->nsets, qt->cap, reinterpret_cast<const int *>(IN + offs[0].qrs),
-                                reinterpret_cast<const int *>(IN + offs[0].qri), jobs[0].nq, B + offs[0].qd, nullptr, c->stream);
+                                reinterpret_cast<const int *>(IN + offs[0].qri), jobs[0].nq, B + offs[0].qd, nullptr, qt->words, c->stream);
     }
     const DevProjJob *dj = reinterpret_cast<const DevProjJob *>(B + jobs_off);
     const DevProjJob *one = zero_copy_in ? reinterpret_cast<const DevProjJob *>(H + jobs_off) : nullptr;

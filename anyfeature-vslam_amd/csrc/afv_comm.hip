@@ -5,7 +5,9 @@
 // (src/Tracking.cc:1162-1182) does the same per relocalisation candidate; LocalMapping::CreateNewMapPoints
 // (src/LocalMapping.cc:238-297) runs SearchForTriangulation against <= 20 neighbours.  Every call re-reads descriptors
 // that are const after keyframe construction (include/KeyFrame.h:190).  Here they are uploaded ONCE into a table
-// [nsets][cap][32] and batches of (a, b) jobs run against it; only pair lists go in and match vectors come out.
+// [nsets][cap][pitch] and batches of (a, b) jobs run against it; only pair lists go in and match vectors come out.  Binary descriptors of
+// 1 to 64 bytes: rows zero-padded to a pitch of 32 bytes (up to 32-byte descriptors) or 64 bytes (33 to 64), the rule of resident frames;
+// the padding is zero on both sides of every distance, so it adds nothing.
 //
 // Multi-GPU: one process per GPU; the table is replicated with ONE ncclBroadcast per array (RCCL over
 // xGMI), jobs are block-partitioned (afv_shard_range), no other data-path collective exists.  RCCL is resolved at run
@@ -54,7 +56,9 @@ static void table_free(afv_table *t) {
     delete t;
 }
 
-extern "C" int afv_table_create(afv_ctx *c, int nsets, int cap, afv_table **out) {
+static inline size_t table_pitch(const afv_table *t) { return (size_t)t->words * 4; }
+
+static int table_create(afv_ctx *c, int nsets, int cap, int desc_bytes, afv_table **out) {
     if (!c || !out || nsets < 1 || cap < 1 || cap > 4096) return AFV_EINVAL;
     *out = nullptr;
     HIPCHK(c, hipSetDevice(c->device));
@@ -63,7 +67,11 @@ extern "C" int afv_table_create(afv_ctx *c, int nsets, int cap, afv_table **out)
     t->c = c;
     t->nsets = nsets;
     t->cap = cap;
-    hipError_t e = hipMalloc(&t->d_desc, (size_t)nsets * cap * 32);
+    t->desc_bytes = desc_bytes;
+    t->words = desc_bytes <= 32 ? 8 : 16;
+    hipError_t e = hipMalloc(&t->d_desc, (size_t)nsets * cap * table_pitch(t));
+    // rows narrower than their pitch: the padding starts (and, since every writer writes whole padded rows, stays) zero
+    if (e == hipSuccess && (size_t)desc_bytes != table_pitch(t)) e = afv_fill(c, t->d_desc, 0, (size_t)nsets * cap * table_pitch(t));
     if (e == hipSuccess) e = hipMalloc(&t->d_angle, (size_t)nsets * cap * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&t->d_n, (size_t)nsets * sizeof(int32_t));
     if (e == hipSuccess) e = afv_fill(c, t->d_n, 0, (size_t)nsets * sizeof(int32_t));
@@ -91,6 +99,13 @@ extern "C" int afv_table_create(afv_ctx *c, int nsets, int cap, afv_table **out)
     return AFV_OK;
 }
 
+extern "C" int afv_table_create(afv_ctx *c, int nsets, int cap, afv_table **out) { return table_create(c, nsets, cap, AFV_DESC_BYTES, out); }
+
+extern "C" int afv_table_create_bytes(afv_ctx *c, int nsets, int cap, int desc_bytes, afv_table **out) {
+    if (desc_bytes < 1 || desc_bytes > 64) return AFV_EINVAL;
+    return table_create(c, nsets, cap, desc_bytes, out);
+}
+
 extern "C" void afv_table_destroy(afv_table *t) {
     if (!t) return;
     {
@@ -111,7 +126,15 @@ extern "C" int afv_table_set(afv_table *t, int set, const uint8_t *desc32, const
     if (!t || set < 0 || set >= t->nsets || n < 0 || n > t->cap || (n > 0 && !desc32)) return AFV_EINVAL;
     afv_ctx *c = t->c;
     HIPCHK(c, hipSetDevice(c->device));
-    if (n) HIPCHK(c, hipMemcpyAsync(t->d_desc + (size_t)set * t->cap * 32, desc32, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    const size_t pitch = table_pitch(t);
+    if (n && (size_t)t->desc_bytes == pitch) {
+        HIPCHK(c, hipMemcpyAsync(t->d_desc + (size_t)set * t->cap * pitch, desc32, (size_t)n * pitch, hipMemcpyHostToDevice, c->stream));
+    } else if (n) {  // rows of desc_bytes -> zero-padded rows of the pitch (the stream is synchronised below: the staging outlives the copy)
+        std::vector<uint8_t> rows((size_t)n * pitch, 0);
+        for (int i = 0; i < n; ++i) std::memcpy(rows.data() + (size_t)i * pitch, desc32 + (size_t)i * t->desc_bytes, (size_t)t->desc_bytes);
+        HIPCHK(c, hipMemcpyAsync(t->d_desc + (size_t)set * t->cap * pitch, rows.data(), rows.size(), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     if (n && angles)
         HIPCHK(c, hipMemcpyAsync(t->d_angle + (size_t)set * t->cap, angles, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
     else if (n)
@@ -288,7 +311,7 @@ static int table_unpack_meta(afv_table *t, const int32_t *blob, size_t len) {
 }
 
 extern "C" int afv_table_clone(const afv_table *src, afv_table *dst) {
-    if (!src || !dst || src == dst || src->nsets != dst->nsets || src->cap != dst->cap) return AFV_EINVAL;
+    if (!src || !dst || src == dst || src->nsets != dst->nsets || src->cap != dst->cap || src->desc_bytes != dst->desc_bytes) return AFV_EINVAL;
     afv_ctx *c = dst->c;
     return guarded(c, [&]() -> int {
         HIPCHK(c, hipSetDevice(src->c->device));
@@ -298,7 +321,7 @@ extern "C" int afv_table_clone(const afv_table *src, afv_table *dst) {
         if (src->d_idx && !dst->d_idx) HIPCHK(c, hipMalloc(&dst->d_idx, plane * sizeof(int32_t)));
         if (src->d_geo && !dst->d_geo) HIPCHK(c, hipMalloc(&dst->d_geo, 4 * plane * sizeof(float)));
         if (src->d_valid && !dst->d_valid) HIPCHK(c, hipMalloc(&dst->d_valid, plane));
-        HIPCHK(c, afv_copy_dd(c, dst->d_desc, src->d_desc, plane * 32));
+        HIPCHK(c, afv_copy_dd(c, dst->d_desc, src->d_desc, plane * table_pitch(dst)));
         HIPCHK(c, afv_copy_dd(c, dst->d_angle, src->d_angle, plane * sizeof(float)));
         HIPCHK(c, afv_copy_dd(c, dst->d_n, src->d_n, (size_t)dst->nsets * sizeof(int32_t)));
         if (src->d_idx) HIPCHK(c, afv_copy_dd(c, dst->d_idx, src->d_idx, plane * sizeof(int32_t)));
@@ -350,7 +373,7 @@ extern "C" int afv_table_match_pairs_device(afv_table *t, const int32_t *d_pair_
     afv_ctx *c = t->c;
     HIPCHK(c, hipSetDevice(c->device));
     return afv_match_pairs_core(c, t->d_desc, t->d_angle, 1, t->d_n, t->cap, d_pair_a, d_pair_b, npairs, th_low, nnratio,
-                                check_orientation, d_match12, d_nmatches, stream ? (hipStream_t)stream : c->stream);
+                                check_orientation, d_match12, d_nmatches, stream ? (hipStream_t)stream : c->stream, t->words);
 }
 
 extern "C" int afv_table_match_pairs(afv_table *t, const int32_t *pair_a, const int32_t *pair_b, int npairs, float th_low, float nnratio,
@@ -366,7 +389,7 @@ extern "C" int afv_table_match_pairs(afv_table *t, const int32_t *pair_a, const 
     std::memcpy(hp + t->pair_cap, pair_b, (size_t)npairs * sizeof(int32_t));
     HIPCHK(c, hipMemcpyAsync(t->d_pairs, hp, (size_t)t->pair_cap * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     rc = afv_match_pairs_core(c, t->d_desc, t->d_angle, 1, t->d_n, t->cap, t->d_pairs, t->d_pairs + t->pair_cap, npairs, th_low, nnratio,
-                              check_orientation, t->d_out, t->d_nm, c->stream);
+                              check_orientation, t->d_out, t->d_nm, c->stream, t->words);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(h_nm, t->d_nm, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (match12)
@@ -432,11 +455,11 @@ static int table_match_bow_impl(afv_table *t, const int32_t *pair_a, const int32
     for (int p = 0; p < npairs; ++p) {
         const int a = pair_a[p], bb = pair_b[p];
         DevMatchJob &d = J[p];
-        d.d1 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)a * cap * 32);
-        d.d2 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)bb * cap * 32);
+        d.d1 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)a * cap * table_pitch(t));
+        d.d2 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)bb * cap * table_pitch(t));
         d.n1 = t->h_n[a];
         d.n2 = t->h_n[bb];
-        d.words = 8;
+        d.words = t->words;
         d.segs = reinterpret_cast<const Seg *>(c->d_match + segs_off) + seg_first[p];
         d.nseg = seg_first[p + 1] - seg_first[p];
         d.idx1 = t->d_idx + (size_t)a * cap;
@@ -522,7 +545,8 @@ static int table_match_bow_frame_impl(afv_table *t, const int32_t *slots, int ns
         seg_first[p + 1] = (int)segs.size();
     }
     const int nfe = std::max(nf, 1);
-    const size_t fdesc_off = fr ? 0 : b.put(F->desc32, (size_t)nf * 32);
+    // the frame view's rows are packed at the table's width; the device rows are padded to its pitch
+    const size_t fdesc_off = fr ? 0 : (t->desc_bytes == AFV_DESC_BYTES ? b.put(F->desc32, (size_t)nf * 32) : put_desc(b, F->desc32, nf, t->desc_bytes, t->words));
     const size_t fang_off = (!fr && check_orientation && nf) ? b.put(F->angle, (size_t)nf * sizeof(float)) : 0;
     const size_t fidx_off = fr ? 0 : b.put(F->nnodes > 0 ? F->seg_idx : nullptr, (size_t)(F->nnodes > 0 ? FV.seg_ptr[F->nnodes] : 0) * sizeof(int32_t));
     const size_t segs_off = b.put(segs.data(), segs.size() * sizeof(Seg));
@@ -541,11 +565,11 @@ static int table_match_bow_frame_impl(afv_table *t, const int32_t *slots, int ns
     for (int p = 0; p < nslots; ++p) {
         const int a = slots[p];
         DevMatchJob &d = J[p];
-        d.d1 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)a * cap * 32);
+        d.d1 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)a * cap * table_pitch(t));
         d.d2 = fr ? reinterpret_cast<const uint32_t *>(fr->d_desc) : reinterpret_cast<const uint32_t *>(c->d_match + fdesc_off);
         d.n1 = t->h_n[a];
         d.n2 = nf;
-        d.words = 8;
+        d.words = t->words;
         d.segs = reinterpret_cast<const Seg *>(c->d_match + segs_off) + seg_first[p];
         d.nseg = seg_first[p + 1] - seg_first[p];
         d.idx1 = t->d_idx + (size_t)a * cap;
@@ -590,7 +614,7 @@ extern "C" int afv_table_match_bow_frame_h(afv_table *t, const int32_t *slots, i
                                            int check_orientation, int32_t *match_f, int32_t *nmatches) {
     if (!t || !slots || nslots < 1 || !f || !nmatches) return AFV_EINVAL;
     if (f->c != t->c || !f->has_features || !f->has_fv) return AFV_EINVAL;  // afv_frame_bow_transform first
-    if (f->desc_bytes != AFV_DESC_BYTES) return AFV_EUNSUPPORTED;           // the table holds 32-byte rows
+    if (f->float_dim || f->desc_bytes != t->desc_bytes) return AFV_EUNSUPPORTED;  // binary rows of the table's width only
     afv_frame_view view{};
     view.n = f->n;
     return guarded(t->c, [&] { return table_match_bow_frame_impl(t, slots, nslots, &view, th_low, nnratio, check_orientation, match_f, nmatches, f); });
@@ -600,7 +624,7 @@ extern "C" int afv_table_match_bow_frame_h(afv_table *t, const int32_t *slots, i
 // table planes; the FeatureVector's node structure goes host to host
 extern "C" int afv_table_set_from_frame(afv_table *t, int slot, afv_frame *f) {
     if (!t || !f || slot < 0 || slot >= t->nsets || f->c != t->c || !f->has_features) return AFV_EINVAL;
-    if (f->desc_bytes != AFV_DESC_BYTES) return AFV_EUNSUPPORTED;  // the table holds 32-byte rows
+    if (f->float_dim || f->desc_bytes != t->desc_bytes) return AFV_EUNSUPPORTED;  // binary rows of the table's width only
     if (f->n > t->cap) return AFV_ECAPACITY;
     afv_ctx *c = t->c;
     return guarded(c, [&]() -> int {
@@ -614,7 +638,7 @@ extern "C" int afv_table_set_from_frame(afv_table *t, int slot, afv_frame *f) {
         A.f_desc = reinterpret_cast<const uint4 *>(f->d_desc);
         A.f_angle = f->d_angle; A.f_x = f->d_x; A.f_y = f->d_y; A.f_sigma2 = f->d_sigma2; A.f_ur = f->d_ur;
         A.f_seg_idx = f->has_fv ? f->d_seg_idx : nullptr;
-        A.t_desc = reinterpret_cast<uint4 *>(t->d_desc + (size_t)slot * t->cap * 32);
+        A.t_desc = reinterpret_cast<uint4 *>(t->d_desc + (size_t)slot * t->cap * table_pitch(t));  // the frame's rows have the same pitch
         A.t_angle = t->d_angle + (size_t)slot * t->cap;
         A.t_x = t->d_geo + (size_t)slot * t->cap;
         A.t_y = t->d_geo + plane + (size_t)slot * t->cap;
@@ -624,7 +648,7 @@ extern "C" int afv_table_set_from_frame(afv_table *t, int slot, afv_frame *f) {
         A.t_valid = t->d_valid ? t->d_valid + (size_t)slot * t->cap : nullptr;
         A.t_n = t->d_n + slot;
         A.n = f->n; A.cap = t->cap; A.nkept = f->has_fv ? f->fv_total : 0;
-        afv_launch_table_promote(&A, f->n, t->cap, c->stream);
+        afv_launch_table_promote(&A, f->n, t->cap, t->words, c->stream);
         HIPCHK(c, hipGetLastError());
         t->h_n[slot] = f->n;
         t->fv[slot] = HostFeatVec();
@@ -713,12 +737,12 @@ static int table_match_tri_impl(afv_table *t, const int32_t *pair_a, const int32
         const int a = pair_a[p], bb = pair_b[p];
         DevTriJob &T = J[p];
         DevMatchJob &d = T.m;
-        d.d1 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)a * cap * 32);
-        d.d2 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)bb * cap * 32);
+        d.d1 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)a * cap * table_pitch(t));
+        d.d2 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)bb * cap * table_pitch(t));
         d.n1 = t->h_n[a];
         d.n2 = t->h_n[bb];
         max_n1 = std::max(max_n1, d.n1);
-        d.words = 8;
+        d.words = t->words;
         d.segs = reinterpret_cast<const Seg *>(c->d_match + segs_off) + seg_first[p];
         d.nseg = seg_first[p + 1] - seg_first[p];
         d.idx1 = t->d_idx + (size_t)a * cap;
@@ -903,16 +927,33 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         // replica image (host-side FeatureVector structure + per-set flags)
         std::vector<int32_t> blob;
         if (m->rank == root) table_pack_meta(t, blob);
-        int32_t flags[4] = {t->d_idx != nullptr, t->d_geo != nullptr, t->d_valid != nullptr, (int32_t)blob.size()};
+        // ... and its shape: every rank compares it with its own table and ALL ranks learn every verdict (one all-gather of a flag) before any
+        // plane moves, so that a table of another shape or row width on any rank is refused everywhere instead of mismatching the
+        // lengths of the broadcasts below
+        int32_t flags[7] = {t->d_idx != nullptr, t->d_geo != nullptr, t->d_valid != nullptr, (int32_t)blob.size(), t->nsets, t->cap, t->desc_bytes};
         int32_t *d_flags = nullptr;
-        HIPCHK(c, hipMalloc(&d_flags, sizeof(flags)));
+        HIPCHK(c, hipMalloc(&d_flags, sizeof(flags) + (size_t)(m->nranks + 1) * sizeof(int32_t)));
+        int32_t *d_ok = d_flags + 7, *d_oks = d_ok + 1;
         hipError_t e = hipMemcpyAsync(d_flags, flags, sizeof(flags), hipMemcpyHostToDevice, c->stream);
         int rc = e == hipSuccess ? afv_comm_broadcast(m, d_flags, sizeof(flags), root, c->stream) : AFV_EHIP;
         if (rc == AFV_OK) e = hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream);
         if (rc == AFV_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        std::vector<int32_t> oks((size_t)m->nranks, 0);
+        if (rc == AFV_OK && e == hipSuccess) {
+            const int32_t ok = flags[4] == t->nsets && flags[5] == t->cap && flags[6] == t->desc_bytes;
+            e = hipMemcpyAsync(d_ok, &ok, sizeof(ok), hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) rc = afv_comm_allgather(m, d_ok, d_oks, sizeof(int32_t), c->stream);
+            if (rc == AFV_OK && e == hipSuccess) e = hipMemcpyAsync(oks.data(), d_oks, oks.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+            if (rc == AFV_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        }
         (void)hipFree(d_flags);
         if (rc) return rc;
         HIPCHK(c, e);
+        for (int32_t ok : oks)
+            if (!ok) {
+                c->last_error = "afv_table_broadcast: the tables of the ranks differ in nsets, cap or desc_bytes";
+                return AFV_EINVAL;
+            }
         if (flags[3] < 1) return AFV_EINVAL;
         const size_t plane = (size_t)t->nsets * t->cap;
         if (flags[0] && !t->d_idx) HIPCHK(c, hipMalloc(&t->d_idx, plane * sizeof(int32_t)));
@@ -923,7 +964,7 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         struct Free { void *p; ~Free() { (void)hipFree(p); } } free_meta{d_meta};
         if (m->rank == root) HIPCHK(c, hipMemcpyAsync(d_meta, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipEventRecord(t->ev0, c->stream));
-        rc = afv_comm_broadcast(m, t->d_desc, plane * 32, root, c->stream);
+        rc = afv_comm_broadcast(m, t->d_desc, plane * table_pitch(t), root, c->stream);
         if (!rc) rc = afv_comm_broadcast(m, t->d_angle, plane * sizeof(float), root, c->stream);
         if (!rc) rc = afv_comm_broadcast(m, t->d_n, (size_t)t->nsets * sizeof(int32_t), root, c->stream);
         if (!rc && flags[0]) rc = afv_comm_broadcast(m, t->d_idx, plane * sizeof(int32_t), root, c->stream);

@@ -56,10 +56,10 @@ extern "C" void afv_launch_match_bow_seg(const DevMatchJob *jobs, int njobs, con
 extern "C" int afv_match_topk_slices(int cap, int engine, int want);
 extern "C" void afv_launch_match_topk(const uint8_t *desc, const int *nset, int cap, const int *pa, const int *pb, int npairs,
                                       void *topk_scratch, int pair_base, int engine, int nslices, void *slice_scratch, int *tickets,
-                                      hipStream_t stream);
+                                      int words, hipStream_t stream);
 extern "C" void afv_launch_match_resolve(const uint8_t *desc, const float *ang, int ang_stride, const int *nset, int cap, const int *pa,
                                          const int *pb, int npairs, float th, float ratio, int check_ori, int *match, int *nmatches,
-                                         const void *topk_scratch, int pair_base, int engine, hipStream_t stream);
+                                         const void *topk_scratch, int pair_base, int engine, int words, hipStream_t stream);
 extern "C" void afv_launch_match_tri(const DevTriJob *jobs, int njobs, int max_n1, hipStream_t stream);
 extern "C" void afv_launch_match_l2(const float *d1, int n1, const float *d2, int n2, int dim, const uint8_t *v1,
                                     const uint8_t *v2, float th, float ratio, int *out, int *nmatches, hipStream_t stream);
@@ -80,10 +80,10 @@ extern "C" size_t afv_featvec_build_lds(int cap, int width);
 extern "C" void afv_launch_frame_grid(const DevGridJob *jobs, int njobs, size_t lds_bytes, hipStream_t stream);
 extern "C" void afv_launch_frame_grid1(const DevGridJob *job, size_t lds_bytes, hipStream_t stream);
 extern "C" void afv_launch_frame_gather(const uint8_t *table, const int *nset, int nsets, int cap, const int *slot, const int *idx, int nq,
-                                        void *out, int *bad, hipStream_t stream);
+                                        void *out, int *bad, int words, hipStream_t stream);
 extern "C" void afv_launch_featvec_build(const int *leaf, const int *nid, const int *dense, int n, int cap, int width, const uint8_t *stopped,
                                          int *seg_idx, int *n_kept, int *h_leaf, int *h_nid, int *h_dense, hipStream_t stream);
-extern "C" void afv_launch_table_promote(const void *args, int n, int cap, hipStream_t stream);
+extern "C" void afv_launch_table_promote(const void *args, int n, int cap, int words, hipStream_t stream);
 extern "C" void afv_launch_match_fuse(const DevProjJob *jobs, int njobs, int max_nq, const DevProjJob *one, hipStream_t stream);
 extern "C" size_t afv_match_l2_scratch_bytes(int n1, int n2, int *ntiles_out, int *cols_per_tile_out);
 extern "C" int afv_launch_match_l2_tiled(const float *d1, int n1, const float *d2, int n2, int dim, const uint8_t *v1, const uint8_t *v2,
@@ -432,7 +432,8 @@ struct HostFeatVec {  // host copy of one keyframe's FeatureVector (node ids, CS
 struct afv_table {
     afv_ctx *c = nullptr;
     int nsets = 0, cap = 0;
-    uint8_t *d_desc = nullptr;  // [nsets][cap][32]
+    int desc_bytes = 32, words = 8;  // descriptor size and dwords per zero-padded row: 8 up to 32 bytes, 16 up to 64 (afv_table_create_bytes)
+    uint8_t *d_desc = nullptr;  // [nsets][cap][4 * words]
     float *d_angle = nullptr;   // [nsets][cap]
     int32_t *d_n = nullptr;     // [nsets]
     int32_t *d_idx = nullptr;   // [nsets][cap] FeatureVector feature indices in node order (afv_table_set_featvec), lazily allocated
@@ -454,7 +455,7 @@ struct afv_table {
 // ---- shared between afv_api.hip and afv_comm.hip ----
 int afv_match_pairs_core(afv_ctx *c, const uint8_t *d_desc, const float *d_ang, int ang_stride, const int32_t *d_n, int cap,
                          const int32_t *d_pair_a, const int32_t *d_pair_b, int npairs, float th_low, float nnratio,
-                         int check_orientation, int32_t *d_match, int32_t *d_nmatches, hipStream_t s);
+                         int check_orientation, int32_t *d_match, int32_t *d_nmatches, hipStream_t s, int words);
 void afv_shared_segments(const afv_match_job &j, std::vector<Seg> &segs);
 int afv_check_resolve_guard(afv_ctx *c, const int32_t *nmatches, int n);
 void afv_table_release_all(afv_ctx *c);  // afv_destroy: tables / communicators still alive die with their context

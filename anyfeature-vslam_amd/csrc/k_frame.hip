@@ -232,25 +232,33 @@ extern "C" void afv_launch_frame_grid1(const DevGridJob *job, size_t lds_bytes, 
 }
 
 // ---------------- k_frame_gather: descriptor rows by reference ----------------
-// out[q] = table[(slot[q] * cap + idx[q])] (32 bytes = 2 x uint4; eight queries per 16 threads would not matter at this size: a thread per
-// half row); a reference outside the table yields a zero row and raises *bad (may be null: the host checked the references)
-extern "C" __global__ __launch_bounds__(256) void k_frame_gather(const uint8_t *__restrict__ table, const int *__restrict__ nset, int nsets, int cap,
-                                                              const int *__restrict__ slot, const int *__restrict__ idx, int nq,
-                                                              uint4 *__restrict__ out, int *__restrict__ bad) {
+// out[q] = table[(slot[q] * cap + idx[q])] (a row of Q x 16 bytes: 2 for the 32-byte pitch, 4 for the 64-byte one; eight queries per 16
+// threads would not matter at this size: a thread per 16 bytes); a reference outside the table yields a zero row and raises *bad (may be
+// null: the host checked the references)
+template <int Q>
+__global__ __launch_bounds__(256) void k_frame_gather(const uint8_t *__restrict__ table, const int *__restrict__ nset, int nsets, int cap,
+                                                      const int *__restrict__ slot, const int *__restrict__ idx, int nq,
+                                                      uint4 *__restrict__ out, int *__restrict__ bad) {
     const int t = blockIdx.x * 256 + threadIdx.x;
-    const int q = t >> 1, h = t & 1;
+    const int q = t >> (Q == 2 ? 1 : 2), h = t & (Q - 1);
     if (q >= nq) return;
     const int s = slot[q], i = idx[q];
     uint4 v = make_uint4(0, 0, 0, 0);
-    if (s >= 0 && s < nsets && i >= 0 && i < min(nset[s], cap)) v = reinterpret_cast<const uint4 *>(table + ((size_t)s * cap + i) * 32)[h];
+    if (s >= 0 && s < nsets && i >= 0 && i < min(nset[s], cap)) v = reinterpret_cast<const uint4 *>(table + ((size_t)s * cap + i) * (Q * 16))[h];
     else if (h == 0 && bad) atomicOr(bad, 1);
-    out[2 * q + h] = v;
+    out[Q * q + h] = v;
 }
 
+// words: dwords per row of the table (8 or 16)
 extern "C" void afv_launch_frame_gather(const uint8_t *table, const int *nset, int nsets, int cap, const int *slot, const int *idx, int nq,
-                                        void *out, int *bad, hipStream_t stream) {
-    if (nq > 0) hipLaunchKernelGGL(k_frame_gather, dim3((2 * nq + 255) / 256), dim3(256), 0, stream, table, nset, nsets, cap, slot, idx, nq,
-                                   reinterpret_cast<uint4 *>(out), bad);
+                                        void *out, int *bad, int words, hipStream_t stream) {
+    if (nq <= 0) return;
+    if (words == 16)
+        hipLaunchKernelGGL(k_frame_gather<4>, dim3((4 * nq + 255) / 256), dim3(256), 0, stream, table, nset, nsets, cap, slot, idx, nq,
+                           reinterpret_cast<uint4 *>(out), bad);
+    else
+        hipLaunchKernelGGL(k_frame_gather<2>, dim3((2 * nq + 255) / 256), dim3(256), 0, stream, table, nset, nsets, cap, slot, idx, nq,
+                           reinterpret_cast<uint4 *>(out), bad);
 }
 
 // ---------------- k_featvec_build ----------------
@@ -363,11 +371,12 @@ extern "C" void afv_launch_featvec_build(const int *leaf, const int *nid, const 
 }
 
 // ---------------- k_table_promote ----------------
-// the frame's arrays into slot `set` of the table planes (descriptors 32 B rows, angle, x / y / sigma2 / mvuRight, FeatureVector body,
-// validity = 1, count): one launch instead of nine small copies
-extern "C" __global__ __launch_bounds__(256) void k_table_promote(PromoteArgs A) {
+// the frame's arrays into slot `set` of the table planes (descriptors as rows of Q x 16 bytes = the frame's zero-padded rows, angle,
+// x / y / sigma2 / mvuRight, FeatureVector body, validity = 1, count): one launch instead of nine small copies
+template <int Q>
+__global__ __launch_bounds__(256) void k_table_promote(PromoteArgs A) {
     const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t < 2 * A.n) A.t_desc[t] = A.f_desc[t];
+    if (t < Q * A.n) A.t_desc[t] = A.f_desc[t];
     if (t < A.n) {
         A.t_angle[t] = A.f_angle[t];
         if (A.t_x) {
@@ -382,8 +391,10 @@ extern "C" __global__ __launch_bounds__(256) void k_table_promote(PromoteArgs A)
     if (t == 0) *A.t_n = A.n;
 }
 
-extern "C" void afv_launch_table_promote(const void *args, int n, int cap, hipStream_t stream) {
+// words: dwords per descriptor row of the frame and the table (8 or 16)
+extern "C" void afv_launch_table_promote(const void *args, int n, int cap, int words, hipStream_t stream) {
     const PromoteArgs &A = *reinterpret_cast<const PromoteArgs *>(args);
-    const int work = std::max(std::max(2 * n, cap), 1);
-    hipLaunchKernelGGL(k_table_promote, dim3((work + 255) / 256), dim3(256), 0, stream, A);
+    const int work = std::max(std::max(words / 4 * n, cap), 1);
+    if (words == 16) hipLaunchKernelGGL(k_table_promote<4>, dim3((work + 255) / 256), dim3(256), 0, stream, A);
+    else hipLaunchKernelGGL(k_table_promote<2>, dim3((work + 255) / 256), dim3(256), 0, stream, A);
 }

@@ -483,28 +483,46 @@ __global__ __launch_bounds__(MT) void k_match_bow_finish(const DevMatchJob *__re
 #define TOPK 4
 #define COL_TILE 1024
 
+// popcount over one 16-byte quarter of a row
+__device__ __forceinline__ int popc_x4(const uint4 q, const uint4 c) {
+    return __popc(q.x ^ c.x) + __popc(q.y ^ c.y) + __popc(q.z ^ c.z) + __popc(q.w ^ c.w);
+}
+
+// W = dwords per (zero-padded) row: 8 up to 32-byte descriptors, 16 up to 64.  A column tile is 32 KB of LDS at either width.
+template <int W>
 __global__ __launch_bounds__(MT) void k_match_topk(const uint8_t *__restrict__ desc, const int *__restrict__ nset, int cap,
                                                    const int *__restrict__ pair_a, const int *__restrict__ pair_b,
                                                    int4 *__restrict__ topk, int pair_base) {
+    constexpr int Q = W / 4, CT = COL_TILE * 8 / W;  // 16-byte quarters per row, columns per tile
     __shared__ __attribute__((aligned(16))) uint32_t s_cols[COL_TILE * 8];
     const int p = pair_base + blockIdx.y;
     const int a = pair_a[p], b = pair_b[p];
     const int n1 = min(nset[a], cap), n2 = min(nset[b], cap);
     const int row = blockIdx.x * MT + threadIdx.x;
     if (blockIdx.x * MT >= n1) return;  // uniform
-    const uint4 *qa = reinterpret_cast<const uint4 *>(desc + ((size_t)a * cap + min(row, n1 - 1)) * 32);
-    const uint4 q0 = qa[0], q1 = qa[1];
+    const uint4 *qa = reinterpret_cast<const uint4 *>(desc + ((size_t)a * cap + min(row, n1 - 1)) * (W * 4));
+    uint4 qv[Q];
+#pragma unroll
+    for (int h = 0; h < Q; ++h) qv[h] = qa[h];
+    const uint4 q0 = qv[0], q1 = qv[1];
     int k[TOPK] = {NO_KEY, NO_KEY, NO_KEY, NO_KEY};
-    const uint4 *cb = reinterpret_cast<const uint4 *>(desc + (size_t)b * cap * 32);
-    for (int c0 = 0; c0 < n2; c0 += COL_TILE) {
-        const int nc = min(COL_TILE, n2 - c0);
+    const uint4 *cb = reinterpret_cast<const uint4 *>(desc + (size_t)b * cap * (W * 4));
+    for (int c0 = 0; c0 < n2; c0 += CT) {
+        const int nc = min(CT, n2 - c0);
         __syncthreads();
-        for (int i = threadIdx.x; i < nc * 2; i += MT) reinterpret_cast<uint4 *>(s_cols)[i] = cb[(size_t)c0 * 2 + i];
+        for (int i = threadIdx.x; i < nc * Q; i += MT) reinterpret_cast<uint4 *>(s_cols)[i] = cb[(size_t)c0 * Q + i];
         __syncthreads();
         for (int j = 0; j < nc; ++j) {
-            const uint4 c_lo = reinterpret_cast<const uint4 *>(s_cols)[2 * j], c_hi = reinterpret_cast<const uint4 *>(s_cols)[2 * j + 1];
-            int d = __popc(q0.x ^ c_lo.x) + __popc(q0.y ^ c_lo.y) + __popc(q0.z ^ c_lo.z) + __popc(q0.w ^ c_lo.w);
-            d += __popc(q1.x ^ c_hi.x) + __popc(q1.y ^ c_hi.y) + __popc(q1.z ^ c_hi.z) + __popc(q1.w ^ c_hi.w);
+            int d;
+            if constexpr (W == 8) {
+                const uint4 c_lo = reinterpret_cast<const uint4 *>(s_cols)[2 * j], c_hi = reinterpret_cast<const uint4 *>(s_cols)[2 * j + 1];
+                d = __popc(q0.x ^ c_lo.x) + __popc(q0.y ^ c_lo.y) + __popc(q0.z ^ c_lo.z) + __popc(q0.w ^ c_lo.w);
+                d += __popc(q1.x ^ c_hi.x) + __popc(q1.y ^ c_hi.y) + __popc(q1.z ^ c_hi.z) + __popc(q1.w ^ c_hi.w);
+            } else {
+                d = popc_x4(qv[0], reinterpret_cast<const uint4 *>(s_cols)[Q * j]);
+#pragma unroll
+                for (int h = 1; h < Q; ++h) d += popc_x4(qv[h], reinterpret_cast<const uint4 *>(s_cols)[Q * j + h]);
+            }
             const int key = (d << 16) | (c0 + j);
             // sorted insert into k[0] <= k[1] <= k[2] <= k[3], the largest of the five falls out: the new k[i] is the median of
             // (k[i-1], k[i], key) — one v_min + three v_med3 per column
@@ -526,13 +544,16 @@ __global__ __launch_bounds__(MT) void k_match_topk(const uint8_t *__restrict__ d
 // LDS of one k_match_resolve workgroup, sized by the per-set capacity of the launch (23 KB at cap = 1024, so several pairs share a
 // CU: the ordered walk is one wavefront deep and latency-bound, what a batch costs is set by how many walks run at once)
 #define PAIR_COLS_LDS 1024  // sets up to this capacity also keep the column descriptors in LDS (exact rescans of the walk): 56 KB in all,
-                            // below the 64 KB a launch may ask for without raising the function's dynamic-LDS limit
-static inline size_t resolve_lds_bytes(int cap, bool stage_cols) {
+                            // below the 64 KB a launch may ask for without raising the function's dynamic-LDS limit.  The threshold counts
+                            // 32-byte rows: 64-byte rows (W = 16) are staged up to half that capacity, the same 32 KB of columns
+static inline int pair_cols_lds(int words) { return PAIR_COLS_LDS * 8 / words; }
+static inline size_t resolve_lds_bytes(int cap, bool stage_cols, int words) {
     const size_t c = ((size_t)cap + 63) & ~(size_t)63;
     return std::min<size_t>(c, PAIR_KEYS_LDS) * 32 /*key records*/ + c * 4 /*claim*/ + c * 2 /*live*/ + c /*bin*/ + c / 8 /*matched*/ +
-           (stage_cols ? c * 32 + 16 : 0) /*columns, 16-byte aligned*/;
+           (stage_cols ? c * words * 4 + 16 : 0) /*columns, 16-byte aligned*/;
 }
 
+template <int W>
 __global__ __launch_bounds__(MT, 2) void k_match_resolve(const uint8_t *__restrict__ desc, const float *__restrict__ ang, int ang_stride,
                                                       const int *__restrict__ nset, int cap, const int *__restrict__ pair_a,
                                                       const int *__restrict__ pair_b, const int4 *__restrict__ topk, float th,
@@ -553,7 +574,9 @@ __global__ __launch_bounds__(MT, 2) void k_match_resolve(const uint8_t *__restri
 #endif
     __shared__ int s_hist[32];
     __shared__ int s_wave[8];
-    __shared__ int s_nm, s_drop[3];
+    // the three kept histogram bins as scalars, not an array: a template's static locals are not split by the optimizer the way a plain
+    // function's are, and an array would move them in the static LDS layout
+    __shared__ int s_nm, s_drop0, s_drop1, s_drop2;
     const int p = pair_base + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 #ifdef AFV_RESOLVE_STATS
     const long long st_k0 = wall_clock64();
@@ -593,8 +616,8 @@ __global__ __launch_bounds__(MT, 2) void k_match_resolve(const uint8_t *__restri
         nlive += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
         __syncthreads();
     }
-    const uint32_t *d1 = reinterpret_cast<const uint32_t *>(desc + (size_t)a * cap * 32);
-    const uint32_t *d2 = reinterpret_cast<const uint32_t *>(desc + (size_t)b * cap * 32);
+    const uint32_t *d1 = reinterpret_cast<const uint32_t *>(desc + (size_t)a * cap * (W * 4));
+    const uint32_t *d2 = reinterpret_cast<const uint32_t *>(desc + (size_t)b * cap * (W * 4));
 #ifdef AFV_RESOLVE_STATS
     if (tid == 0) s_t[0] = wall_clock64();
 #endif
@@ -605,9 +628,9 @@ __global__ __launch_bounds__(MT, 2) void k_match_resolve(const uint8_t *__restri
         if (cols_in_lds && nlive > 0) {
             uint4 *sc = reinterpret_cast<uint4 *>(s_cols);
             const uint4 *gc = reinterpret_cast<const uint4 *>(d2);
-            // all loads of a thread in flight together (<= 11 x 16 B at PAIR_COLS_LDS = 1024): two round trips instead of eleven
+            // all loads of a thread in flight together (<= 11 x 16 B at PAIR_COLS_LDS = 1024 32-byte rows): two round trips instead of eleven
             static_assert(PAIR_COLS_LDS * 2 <= 11 * (MT - 64), "column copy: eleven 16-byte loads per thread");
-            const int last = n2 * 2 - 1, i0 = tid - 64;
+            const int last = n2 * (W / 4) - 1, i0 = tid - 64;
 #define AFV_COL(k) const uint4 v##k = gc[min(i0 + (k) * (MT - 64), last)];
             AFV_COL(0) AFV_COL(1) AFV_COL(2) AFV_COL(3) AFV_COL(4) AFV_COL(5) AFV_COL(6) AFV_COL(7) AFV_COL(8) AFV_COL(9) AFV_COL(10)
 #undef AFV_COL
@@ -656,8 +679,10 @@ __global__ __launch_bounds__(MT, 2) void k_match_resolve(const uint8_t *__restri
             const float last_d = (float)(last_key >> 16);  // every column outside the list is at least this far
             // every lane fetches its row's descriptor now: if the round is cut at this lane, the rescan needs it, and the round trip
             // hides behind the fixed-point passes
-            const uint4 *qp = reinterpret_cast<const uint4 *>(d1 + (size_t)row * 8);
-            const uint4 qlo = qp[0], qhi = qp[1];
+            const uint4 *qp = reinterpret_cast<const uint4 *>(d1 + (size_t)row * W);
+            uint4 qrow[W / 4];
+#pragma unroll
+            for (int h = 0; h < W / 4; ++h) qrow[h] = qp[h];
             // the matched set does not change inside a round: one look per key.  v[q] = the key while it can still be chosen, else
             // "none"; cq[q] = its column (0 for a slot that holds no key: a harmless claim lookup)
             int v[RKEYS], cq[RKEYS];
@@ -750,29 +775,38 @@ __global__ __launch_bounds__(MT, 2) void k_match_resolve(const uint8_t *__restri
                 }
                 const uint4 *cb = cols_in_lds ? reinterpret_cast<const uint4 *>(s_cols) : reinterpret_cast<const uint4 *>(d2);
                 const int i = __builtin_amdgcn_readlane(row, stop);
-                const uint32_t qv[8] = {qlo.x, qlo.y, qlo.z, qlo.w, qhi.x, qhi.y, qhi.z, qhi.w};
-                uint32_t q[8];
+                uint4 q[W / 4];
 #pragma unroll
-                for (int w = 0; w < 8; ++w) q[w] = (uint32_t)__builtin_amdgcn_readlane((int)qv[w], stop);
+                for (int h = 0; h < W / 4; ++h)
+                    q[h] = make_uint4((uint32_t)__builtin_amdgcn_readlane((int)qrow[h].x, stop), (uint32_t)__builtin_amdgcn_readlane((int)qrow[h].y, stop),
+                                      (uint32_t)__builtin_amdgcn_readlane((int)qrow[h].z, stop), (uint32_t)__builtin_amdgcn_readlane((int)qrow[h].w, stop));
                 int k = NO_KEY, s2nd = NO_KEY >> 16;
                 // four columns per lane and step, branch-free: the eight 16-byte loads and the four matched-bit words are in flight
                 // together, a taken or out-of-range column enters as the "no column" key.  k = best key, s2nd = second-best distance
                 // (invariant s2nd >= k >> 16): inserting a key is  s2nd = min(s2nd, max(k, key) >> 16), k = min(k, key).
                 for (int c0 = lane; c0 < n2; c0 += 256) {
-                    uint4 lo[4], hi[4];
+                    uint4 cv[4][W / 4];
                     uint32_t mw[4];
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int c = min(c0 + 64 * u, n2 - 1);
-                        lo[u] = cb[2 * c];
-                        hi[u] = cb[2 * c + 1];
+#pragma unroll
+                        for (int h = 0; h < W / 4; ++h) cv[u][h] = cb[(W / 4) * c + h];
                         mw[u] = s_matched[c >> 5];
                     }
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int c = c0 + 64 * u;
-                        const int d = __popc(q[0] ^ lo[u].x) + __popc(q[1] ^ lo[u].y) + __popc(q[2] ^ lo[u].z) + __popc(q[3] ^ lo[u].w) +
-                                      __popc(q[4] ^ hi[u].x) + __popc(q[5] ^ hi[u].y) + __popc(q[6] ^ hi[u].z) + __popc(q[7] ^ hi[u].w);
+                        int d;
+                        if constexpr (W == 8) {
+                            const uint4 *lo = &cv[u][0], *hi = &cv[u][1];
+                            d = __popc(q[0].x ^ lo->x) + __popc(q[0].y ^ lo->y) + __popc(q[0].z ^ lo->z) + __popc(q[0].w ^ lo->w) +
+                                __popc(q[1].x ^ hi->x) + __popc(q[1].y ^ hi->y) + __popc(q[1].z ^ hi->z) + __popc(q[1].w ^ hi->w);
+                        } else {
+                            d = popc_x4(q[0], cv[u][0]);
+#pragma unroll
+                            for (int h = 1; h < W / 4; ++h) d += popc_x4(q[h], cv[u][h]);
+                        }
                         const bool usable = c < n2 && !((mw[u] >> (c & 31)) & 1u);
                         const int key = usable ? ((d << 16) | c) : NO_KEY;
                         s2nd = min(s2nd, max(k, key) >> 16);
@@ -840,10 +874,10 @@ __global__ __launch_bounds__(MT, 2) void k_match_resolve(const uint8_t *__restri
             }
             if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
             else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            s_drop[0] = i1; s_drop[1] = i2; s_drop[2] = i3;
+            s_drop0 = i1; s_drop1 = i2; s_drop2 = i3;
         }
         __syncthreads();
-        const int i1 = s_drop[0], i2 = s_drop[1], i3 = s_drop[2];
+        const int i1 = s_drop0, i2 = s_drop1, i3 = s_drop2;
         int dropped = 0;
         for (int i = tid; i < n1; i += MT) {
             if (out[i] >= 0) {
@@ -883,10 +917,10 @@ __global__ __launch_bounds__(MT, 2) void k_match_resolve(const uint8_t *__restri
 #define RW_RPW 2      // waiting rows a wavefront rescans together (they share the column loads): 32 per step
 #define RWT 1024      // threads: one per live row
 #define RW_NW (RWT / 64)
-static inline size_t resolve_wg_lds_bytes(int cap, bool stage_cols) {
+static inline size_t resolve_wg_lds_bytes(int cap, bool stage_cols, int words) {
     const size_t c = ((size_t)cap + 63) & ~(size_t)63;
     return std::min<size_t>(c, PAIR_KEYS_LDS) * 32 /*key records*/ + 3 * c * 4 /*claims*/ + c * 4 /*matches*/ + 2 * c * 2 /*wants of the last two passes*/ +
-           c * 2 /*live*/ + c /*bin*/ + c /*flags*/ + (stage_cols ? c * 32 + 16 : 0) /*columns, 16-byte aligned*/;
+           c * 2 /*live*/ + c /*bin*/ + c /*flags*/ + (stage_cols ? c * words * 4 + 16 : 0) /*columns, 16-byte aligned*/;
 }
 
 // one row against the claims in R: the column it accepts (-1: none) and whether it needs the exact rescan.  Same decisions as the walk of
@@ -934,6 +968,7 @@ __device__ __forceinline__ void resolve_eval(const int4 t4, const int4 t8, const
     rescan = type == 2;
 }
 
+template <int W>
 __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restrict__ desc, const float *__restrict__ ang, int ang_stride,
                                                          const int *__restrict__ nset, int cap, const int *__restrict__ pair_a,
                                                          const int *__restrict__ pair_b, const int4 *__restrict__ topk, float th,
@@ -950,7 +985,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
     uint8_t *s_flag = s_bin + capr;  // per live row: 1 = asked for a rescan in the last pass, 2 = pinned by a rescan
     uint32_t *s_cols = reinterpret_cast<uint32_t *>((reinterpret_cast<uintptr_t>(s_flag + capr) + 15) & ~(uintptr_t)15);
     __shared__ int s_hist[32];
-    __shared__ int s_nm, s_drop[3], s_first, s_part[RW_RPW * RW_NW], s_cntw[RW_NW];
+    __shared__ int s_nm, s_drop0, s_drop1, s_drop2, s_first, s_part[RW_RPW * RW_NW], s_cntw[RW_NW];
     __shared__ unsigned short s_wlist[RW_WLIST];  // live indices of the rows waiting for a rescan, in row order
     const int p = pair_base + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int a = pair_a[p], b = pair_b[p];
@@ -996,8 +1031,8 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         nlive += tot;
         __syncthreads();
     }
-    const uint32_t *d1 = reinterpret_cast<const uint32_t *>(desc + (size_t)a * cap * 32);
-    const uint32_t *d2 = reinterpret_cast<const uint32_t *>(desc + (size_t)b * cap * 32);
+    const uint32_t *d1 = reinterpret_cast<const uint32_t *>(desc + (size_t)a * cap * (W * 4));
+    const uint32_t *d2 = reinterpret_cast<const uint32_t *>(desc + (size_t)b * cap * (W * 4));
 #if defined(AFV_RESOLVE_STATS) && AFV_RESOLVE_STATS == 4
     const long long wg_t0 = wall_clock64();
     long long wg_tresc = 0;
@@ -1015,7 +1050,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
             guard_hit = true;
             break;
         }
-        int *R = s_claim + (pass % 3) * capr, *W = s_claim + ((pass + 1) % 3) * capr, *Z = s_claim + ((pass + 2) % 3) * capr;
+        int *R = s_claim + (pass % 3) * capr, *Wc = s_claim + ((pass + 1) % 3) * capr, *Z = s_claim + ((pass + 2) % 3) * capr;
         bool changed = false;
         for (int li = tid; li < nlive; li += RWT) {
             const int w1 = s_w1[li], w2 = s_w2[li];
@@ -1037,7 +1072,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
                 resolve_eval(t4, t8, R, li, n2, th, ratio, want, rescan);
                 s_flag[li] = rescan ? 1 : 0;
             }
-            if (want >= 0) atomicMin(&W[want], li);
+            if (want >= 0) atomicMin(&Wc[want], li);
             if (w2 >= 0) Z[w2] = RW_INF;  // what this row put into Z two passes ago (every row that did clears it: the array is empty before it is written again)
             s_w2[li] = (short)w1;
             s_w1[li] = (short)want;
@@ -1045,7 +1080,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         }
         ++pass;
         if (__syncthreads_or(changed ? 1 : 0)) continue;
-        // converged: W holds the claims of the final wants (so far).  The rows that asked for a rescan, in row order (s_wlist): live row
+        // converged: Wc holds the claims of the final wants (so far).  The rows that asked for a rescan, in row order (s_wlist): live row
         // t is held by thread t, so a ballot + the wavefronts' counts place them
         {
             const bool waits = tid < nlive && (s_flag[tid] & 3) == 1;  // the first 1024 live rows are looked at per cycle
@@ -1089,7 +1124,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         if (stage_cols && !cols_ready) {  // first rescan of this pair: park the column descriptors in LDS
             const uint4 *gc = reinterpret_cast<const uint4 *>(d2);
             uint4 *sc = reinterpret_cast<uint4 *>(s_cols);
-            for (int i = tid; i < n2 * 2; i += RWT) sc[i] = gc[i];
+            for (int i = tid; i < n2 * (W / 4); i += RWT) sc[i] = gc[i];
             cols_ready = true;
             __syncthreads();
         }
@@ -1104,36 +1139,44 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         bool took = false;
         for (int g0 = 0; g0 < nw && !took; g0 += RW_RPW * RW_NW) {
             int rr[RW_RPW], kk[RW_RPW], s2[RW_RPW], wr[RW_RPW];
-            uint32_t q[RW_RPW][8];
+            uint4 q[RW_RPW][W / 4];
             const int gb = g0 + wv * RW_RPW;
 #pragma unroll
             for (int j = 0; j < RW_RPW; ++j) {
                 rr[j] = s_wlist[min(gb + j, nw - 1)];
-                const uint4 *qp = reinterpret_cast<const uint4 *>(d1 + (size_t)s_live[rr[j]] * 8);
-                const uint4 qlo = qp[0], qhi = qp[1];
-                q[j][0] = qlo.x, q[j][1] = qlo.y, q[j][2] = qlo.z, q[j][3] = qlo.w, q[j][4] = qhi.x, q[j][5] = qhi.y, q[j][6] = qhi.z, q[j][7] = qhi.w;
+                const uint4 *qp = reinterpret_cast<const uint4 *>(d1 + (size_t)s_live[rr[j]] * W);
+#pragma unroll
+                for (int h = 0; h < W / 4; ++h) q[j][h] = qp[h];
                 kk[j] = NO_KEY;
                 s2[j] = NO_KEY >> 16;
                 wr[j] = -1;
             }
             if (gb < nw) {
                 for (int c0 = lane; c0 < n2; c0 += 128) {
-                    uint4 lo[2], hi[2];
+                    uint4 cv[2][W / 4];
                     int cl[2];
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
                         const int c = min(c0 + 64 * u, n2 - 1);
-                        lo[u] = cb[2 * c];
-                        hi[u] = cb[2 * c + 1];
-                        cl[u] = W[c];
+#pragma unroll
+                        for (int h = 0; h < W / 4; ++h) cv[u][h] = cb[(W / 4) * c + h];
+                        cl[u] = Wc[c];
                     }
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
                         const int c = c0 + 64 * u;
 #pragma unroll
                         for (int j = 0; j < RW_RPW; ++j) {
-                            const int d = __popc(q[j][0] ^ lo[u].x) + __popc(q[j][1] ^ lo[u].y) + __popc(q[j][2] ^ lo[u].z) + __popc(q[j][3] ^ lo[u].w) +
-                                          __popc(q[j][4] ^ hi[u].x) + __popc(q[j][5] ^ hi[u].y) + __popc(q[j][6] ^ hi[u].z) + __popc(q[j][7] ^ hi[u].w);
+                            int d;
+                            if constexpr (W == 8) {
+                                const uint4 *lo = &cv[u][0], *hi = &cv[u][1];
+                                d = __popc(q[j][0].x ^ lo->x) + __popc(q[j][0].y ^ lo->y) + __popc(q[j][0].z ^ lo->z) + __popc(q[j][0].w ^ lo->w) +
+                                    __popc(q[j][1].x ^ hi->x) + __popc(q[j][1].y ^ hi->y) + __popc(q[j][1].z ^ hi->z) + __popc(q[j][1].w ^ hi->w);
+                            } else {
+                                d = popc_x4(q[j][0], cv[u][0]);
+#pragma unroll
+                                for (int h = 1; h < W / 4; ++h) d += popc_x4(q[j][h], cv[u][h]);
+                            }
                             const bool usable = c < n2 && !(cl[u] < rr[j]);
                             const int key = usable ? ((d << 16) | c) : NO_KEY;
                             s2[j] = min(s2[j], max(kk[j], key) >> 16);
@@ -1224,10 +1267,10 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
             }
             if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
             else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            s_drop[0] = i1; s_drop[1] = i2; s_drop[2] = i3;
+            s_drop0 = i1; s_drop1 = i2; s_drop2 = i3;
         }
         __syncthreads();
-        const int i1 = s_drop[0], i2 = s_drop[1], i3 = s_drop[2];
+        const int i1 = s_drop0, i2 = s_drop1, i3 = s_drop2;
         int dropped = 0;
         for (int i = tid; i < n1; i += RWT) {
             if (s_out[i] >= 0) {
@@ -1380,9 +1423,11 @@ extern "C" void afv_launch_match_bow_seg(const DevMatchJob *jobs, int njobs, con
 // phase 1 (VALU-bound: the 8 xor + 8 v_bcnt per descriptor pair) and phase 2 (latency-bound ordered resolve) are launched
 // separately so that the runtime can time them apart.
 extern "C" void afv_launch_match_topk_mfma(const uint8_t *desc, const int *nset, int cap, const int *pa, const int *pb, int npairs,
-                                           void *topk_scratch, int pair_base, int nslices, void *slice_scratch, void *tickets, hipStream_t stream);
+                                           void *topk_scratch, int pair_base, int nslices, void *slice_scratch, void *tickets, int words,
+                                           hipStream_t stream);
 // engine: AFV_MATCH_ENGINE_MFMA (default: the exact i8 contraction of k_match_mfma.hip; its keys hold the column in 13 bits) or
-// AFV_MATCH_ENGINE_POPCOUNT (k_match_topk below).  Both write the same top-4 keys.
+// AFV_MATCH_ENGINE_POPCOUNT (k_match_topk below).  Both write the same top-4 keys.  words: dwords per row of `desc`, 8 (rows of up to 32
+// bytes) or 16 (33 to 64 bytes, zero padded).
 // Column slices of phase 1 (the small-batch path; only the matrix-core engine deals its column tiles out).  A sliced launch needs, beside
 // the key records (2 x int4 per row), `slice_scratch` = 2 x int4 per row AND slice, and `tickets` = one int per pair and row tile of
 // 256 rows, ZERO before the first launch (the kernel re-arms them), both indexed by the global pair number like the records.
@@ -1391,13 +1436,16 @@ extern "C" int afv_match_topk_slices(int cap, int engine, int want) {
 }
 extern "C" void afv_launch_match_topk(const uint8_t *desc, const int *nset, int cap, const int *pa, const int *pb, int npairs,
                                       void *topk_scratch, int pair_base, int engine, int nslices, void *slice_scratch, int *tickets,
-                                      hipStream_t stream) {
+                                      int words, hipStream_t stream) {
     if (engine == AFV_MATCH_ENGINE_MFMA && cap < 8192) {
-        afv_launch_match_topk_mfma(desc, nset, cap, pa, pb, npairs, topk_scratch, pair_base, nslices, slice_scratch, tickets, stream);
+        afv_launch_match_topk_mfma(desc, nset, cap, pa, pb, npairs, topk_scratch, pair_base, nslices, slice_scratch, tickets, words, stream);
         return;
     }
     int4 *topk = reinterpret_cast<int4 *>(topk_scratch);
-    hipLaunchKernelGGL(k_match_topk, dim3((cap + MT - 1) / MT, npairs), dim3(MT), 0, stream, desc, nset, cap, pa, pb, topk, pair_base);
+    if (words == 16)
+        hipLaunchKernelGGL(k_match_topk<16>, dim3((cap + MT - 1) / MT, npairs), dim3(MT), 0, stream, desc, nset, cap, pa, pb, topk, pair_base);
+    else
+        hipLaunchKernelGGL(k_match_topk<8>, dim3((cap + MT - 1) / MT, npairs), dim3(MT), 0, stream, desc, nset, cap, pa, pb, topk, pair_base);
 }
 // ang: keypoint angles in degrees, element (set, i) at ang[(set * cap + i) * ang_stride] (stride 7 = afv_keypoint::angle)
 // test hook (process-wide, 0 = off): caps the passes of the fixed-point engines (k_match_resolve_wg, k_proj_resolve_wg, k_init_resolve_wg) so
@@ -1540,29 +1588,43 @@ extern "C" int afv_debug_pass_cap = 0;
 
 // once per context (afv_create, on the context's device): both ordered-phase kernels may ask for more dynamic LDS than the default 64 KB
 extern "C" int afv_match_prepare(void) {
-    bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_resolve_wg), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess;
-    ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_match_resolve), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess && ok;
+    bool ok = true;
+    for (const void *fn : {reinterpret_cast<const void *>(k_match_resolve_wg<8>), reinterpret_cast<const void *>(k_match_resolve_wg<16>),
+                           reinterpret_cast<const void *>(k_match_resolve<8>), reinterpret_cast<const void *>(k_match_resolve<16>)})
+        ok = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess && ok;
     if (!ok) (void)hipGetLastError();
     return ok ? 1 : 0;
 }
 
-extern "C" void afv_launch_match_resolve(const uint8_t *desc, const float *ang, int ang_stride, const int *nset, int cap, const int *pa,
-                                         const int *pb, int npairs, float th, float ratio, int check_ori, int *match, int *nmatches,
-                                         const void *topk_scratch, int pair_base, int engine, hipStream_t stream) {
+template <int W>
+static void launch_match_resolve(const uint8_t *desc, const float *ang, int ang_stride, const int *nset, int cap, const int *pa, const int *pb,
+                                 int npairs, float th, float ratio, int check_ori, int *match, int *nmatches, const void *topk_scratch, int pair_base,
+                                 int engine, hipStream_t stream) {
     const int4 *topk = reinterpret_cast<const int4 *>(topk_scratch);
     if (engine == 1) {  // workgroup-wide fixed point (round 4); columns are parked in LDS only for batches, and only once a pair needs a rescan
-        const bool stage = cap <= PAIR_COLS_LDS && npairs > 8;
-        const size_t lds_wg = resolve_wg_lds_bytes(cap, stage);  // (the raised LDS limit: afv_match_prepare at afv_create)
-        hipLaunchKernelGGL(k_match_resolve_wg, dim3(npairs), dim3(RWT), lds_wg, stream, desc, ang, ang_stride, nset, cap, pa, pb, topk, th, ratio,
+        const bool stage = cap <= pair_cols_lds(W) && npairs > 8;
+        const size_t lds_wg = resolve_wg_lds_bytes(cap, stage, W);  // (the raised LDS limit: afv_match_prepare at afv_create)
+        hipLaunchKernelGGL(k_match_resolve_wg<W>, dim3(npairs), dim3(RWT), lds_wg, stream, desc, ang, ang_stride, nset, cap, pa, pb, topk, th, ratio,
                            check_ori, match, nmatches, pair_base, stage ? 1 : 0, afv_debug_pass_cap);
         return;
     }
     // the column descriptors ride in LDS (for the exact rescans) when they fit and the launch is a batch; a handful of pairs (the
     // single-frame plugin path) runs leaner: 39 KB instead of 71 KB, rescans through L2
-    const bool stage_cols = cap <= PAIR_COLS_LDS && npairs > 8;
-    const size_t lds = resolve_lds_bytes(cap, stage_cols);  // 71 KB with the columns: above the default 64 KB limit (afv_match_prepare)
-    hipLaunchKernelGGL(k_match_resolve, dim3(npairs), dim3(MT), lds, stream, desc, ang, ang_stride, nset, cap, pa, pb, topk, th, ratio,
+    const bool stage_cols = cap <= pair_cols_lds(W) && npairs > 8;
+    const size_t lds = resolve_lds_bytes(cap, stage_cols, W);  // 71 KB with the columns: above the default 64 KB limit (afv_match_prepare)
+    hipLaunchKernelGGL(k_match_resolve<W>, dim3(npairs), dim3(MT), lds, stream, desc, ang, ang_stride, nset, cap, pa, pb, topk, th, ratio,
                        check_ori, match, nmatches, pair_base, stage_cols ? 1 : 0);
+}
+// words: dwords per row of `desc` (8 or 16)
+extern "C" void afv_launch_match_resolve(const uint8_t *desc, const float *ang, int ang_stride, const int *nset, int cap, const int *pa,
+                                         const int *pb, int npairs, float th, float ratio, int check_ori, int *match, int *nmatches,
+                                         const void *topk_scratch, int pair_base, int engine, int words, hipStream_t stream) {
+    if (words == 16)
+        launch_match_resolve<16>(desc, ang, ang_stride, nset, cap, pa, pb, npairs, th, ratio, check_ori, match, nmatches, topk_scratch, pair_base, engine,
+                                 stream);
+    else
+        launch_match_resolve<8>(desc, ang, ang_stride, nset, cap, pa, pb, npairs, th, ratio, check_ori, match, nmatches, topk_scratch, pair_base, engine,
+                                stream);
 }
 extern "C" void afv_launch_match_tri(const DevTriJob *jobs, int njobs, int max_n1, hipStream_t stream) {
     if (max_n1 > 0) hipLaunchKernelGGL(k_match_tri, dim3((max_n1 + MT - 1) / MT, njobs), dim3(MT), 0, stream, jobs);

@@ -19,6 +19,9 @@
 // kernel).  Train descriptors are expanded 64 at a time into LDS (bit -> +-64 byte through a 256-entry byte -> 8-byte table that also
 // lives in LDS), double-buffered, one barrier per tile; every wavefront reads its A fragments with ds_read_b128 (row pitch 304 B =
 // 256 expanded bytes + the 32 index slots + 16: 16 consecutive rows start in 16 different bank quads).
+//
+// The kernel is templated on W, the dwords of a row: W = 8 is the above; W = 16 serves keyframe tables of 33-64-byte descriptors (rows
+// zero-padded to 64 bytes) with 16 + 1 instructions per block over 512 k-slots, key 8192 * d - 2^21 + m, A pitch 560 B.
 #include "afv_device.h"
 #include "afv_runtime.h"  // the launchers below are declared there: a signature that drifts is a compile error, not a silent ABI mismatch
 
@@ -43,24 +46,34 @@ __device__ __forceinline__ void mq_insert(int (&k)[4], int key) {
     k[3] = n3;
 }
 
+// A tile row pitch: W dwords expanded (32 W bytes) + the 32 index slots + 16, so that 16 consecutive rows start in 16 different bank quads
+// (304 B = 19 quads at W = 8, 560 B = 35 quads at W = 16: both odd)
+template <int W>
+struct MqPitch {
+    static constexpr int value = W * 32 + 48;
+};
+static_assert(MqPitch<8>::value == A_PITCH, "the 256-bit tile keeps its pitch");
+
 // expand 64 train descriptors (rows tile_row0 .. +63, clamped to n2 - 1) into one LDS buffer
+template <int W>
 __device__ __forceinline__ void mq_stage(const uint32_t *__restrict__ train, int n2, int tile_row0, const uint2 *lut, uint8_t *buf, int tid) {
-    uint32_t w[2];
+    constexpr int P = MqPitch<W>::value, L = T_TILE * W / MQ_T;  // loads per thread: 2 (W = 8), 4 (W = 16)
+    uint32_t w[L];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int idx = tid + MQ_T * k, row = idx >> 3, wd = idx & 7;
-        w[k] = train[(size_t)min(tile_row0 + row, n2 - 1) * 8 + wd];
+    for (int k = 0; k < L; ++k) {
+        const int idx = tid + MQ_T * k, row = idx / W, wd = idx % W;
+        w[k] = train[(size_t)min(tile_row0 + row, n2 - 1) * W + wd];
     }
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int idx = tid + MQ_T * k, row = idx >> 3, wd = idx & 7;
+    for (int k = 0; k < L; ++k) {
+        const int idx = tid + MQ_T * k, row = idx / W, wd = idx % W;
         const uint2 e0 = lut[w[k] & 255u], e1 = lut[(w[k] >> 8) & 255u], e2 = lut[(w[k] >> 16) & 255u], e3 = lut[w[k] >> 24];
-        uint4 *dst = reinterpret_cast<uint4 *>(buf + row * A_PITCH + wd * 32);
+        uint4 *dst = reinterpret_cast<uint4 *>(buf + row * P + wd * 32);
         dst[0] = make_uint4(e0.x, e0.y, e1.x, e1.y);
         dst[1] = make_uint4(e2.x, e2.y, e3.x, e3.y);
-        if (wd == 0) {  // the index slots: k-slots 256, 257 = (m & 63, m >> 6), the other 30 zero
+        if (wd == 0) {  // the index slots: k-slots 32 W, 32 W + 1 = (m & 63, m >> 6), the other 30 zero
             const uint32_t mi = (uint32_t)(tile_row0 + row);
-            uint4 *ix = reinterpret_cast<uint4 *>(buf + row * A_PITCH + 256);
+            uint4 *ix = reinterpret_cast<uint4 *>(buf + row * P + W * 32);
             ix[0] = make_uint4((mi & 63u) | ((mi >> 6) << 8), 0u, 0u, 0u);
             ix[1] = make_uint4(0u, 0u, 0u, 0u);
         }
@@ -92,43 +105,76 @@ __device__ __forceinline__ void mq_merge_record(int (&m)[RKEYS], int &bound, con
     }
 }
 
-template <bool PARTIAL>
-__device__ __forceinline__ void mq_compute(const uint8_t *buf, const v4i (&bq)[2][8], const v4i &bidx, int (&kk)[2][4], int tile_row0, int n2,
+template <bool PARTIAL, int W>
+__device__ __forceinline__ void mq_compute(const uint8_t *buf, const v4i (&bq)[2][W], const v4i &bidx, int (&kk)[2][4], int tile_row0, int n2,
                                            int lane) {
+    constexpr int P = MqPitch<W>::value;
+    if constexpr (W == 8) {
 #pragma unroll
-    for (int sub = 0; sub < 2; ++sub) {
-        v4i a[9];
-        const uint8_t *ap = buf + (sub * 32 + (lane & 31)) * A_PITCH + (lane >> 5) * 16;
+        for (int sub = 0; sub < 2; ++sub) {
+            v4i a[9];
+            const uint8_t *ap = buf + (sub * 32 + (lane & 31)) * P + (lane >> 5) * 16;
 #pragma unroll
-        for (int t = 0; t < 9; ++t) a[t] = *reinterpret_cast<const v4i *>(ap + t * 32);
-        const int off = tile_row0 + sub * 32 + 4 * (lane >> 5);
+            for (int t = 0; t < 9; ++t) a[t] = *reinterpret_cast<const v4i *>(ap + t * 32);
+            const int off = tile_row0 + sub * 32 + 4 * (lane >> 5);
 #pragma unroll
-        for (int qb = 0; qb < 2; ++qb) {
-            v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[8], bidx, acc, 0, 0, 0);  // + m
+            for (int qb = 0; qb < 2; ++qb) {
+                v16i acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[8], bidx, acc, 0, 0, 0);  // + m
 #pragma unroll
-            for (int t = 0; t < 8; ++t) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[t], bq[qb][t], acc, 0, 0, 0);
+                for (int t = 0; t < 8; ++t) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[t], bq[qb][t], acc, 0, 0, 0);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                int key = acc[r];
-                // C/D register r holds train row (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the 32-row block
-                if (PARTIAL) key = ((r & 3) + 8 * (r >> 2) + off < n2) ? key : NO_KEY;
-                mq_insert(kk[qb], key);
+                for (int r = 0; r < 16; ++r) {
+                    int key = acc[r];
+                    // C/D register r holds train row (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the 32-row block
+                    if (PARTIAL) key = ((r & 3) + 8 * (r >> 2) + off < n2) ? key : NO_KEY;
+                    mq_insert(kk[qb], key);
+                }
             }
+        }
+    } else {
+        // 512 bits: the B fragments of the two query blocks already take 128 registers, so every A fragment feeds both blocks as soon as it
+        // arrives (two accumulators, a few fragments in flight) instead of all seventeen being held at once: no spill at 2 waves / SIMD
+#pragma unroll
+        for (int sub = 0; sub < 2; ++sub) {
+            const uint8_t *ap = buf + (sub * 32 + (lane & 31)) * P + (lane >> 5) * 16;
+            const int off = tile_row0 + sub * 32 + 4 * (lane >> 5);
+            const v4i ai = *reinterpret_cast<const v4i *>(ap + W * 32);
+            v16i acc[2];
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) {
+                acc[qb] = v16i{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                acc[qb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ai, bidx, acc[qb], 0, 0, 0);  // + m
+            }
+#pragma unroll
+            for (int t = 0; t < W; ++t) {
+                const v4i a = *reinterpret_cast<const v4i *>(ap + t * 32);
+#pragma unroll
+                for (int qb = 0; qb < 2; ++qb) acc[qb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, bq[qb][t], acc[qb], 0, 0, 0);
+            }
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    int key = acc[qb][r];
+                    if (PARTIAL) key = ((r & 3) + 8 * (r >> 2) + off < n2) ? key : NO_KEY;
+                    mq_insert(kk[qb], key);
+                }
         }
     }
 }
 
-// SLICED = false: the batch form (one workgroup per row tile walks all column tiles; nslices is 1 and the slice arguments are unused) -
-// kept as its own instantiation so that the column-slice logic costs the throughput-bound launches nothing
-template <bool SLICED>
+// W = dwords per row (8: up to 32-byte descriptors, 16: 33 to 64 bytes, zero padded).  At W = 16 the contraction runs over 512 k-slots
+// (16 + 1 instructions per 32 x 32 block): sum_k A_k B_k = 8192 * d - 2^21, the key  8192 * d - 2^21 + m  orders as before and the record
+// written below holds  d << 16 | m  at both widths.
+template <bool SLICED, int W>
 __global__ __launch_bounds__(MQ_T, 2) void k_match_topk_mfma(const uint8_t *__restrict__ desc, const int *__restrict__ nset, int cap,
                                                              const int *__restrict__ pair_a, const int *__restrict__ pair_b,
                                                              int4 *__restrict__ topk, int pair_base, int nslices_arg, int4 *__restrict__ slice_rec,
                                                              int *__restrict__ tickets) {
     const int nslices = SLICED ? nslices_arg : 1;
     __shared__ __attribute__((aligned(16))) uint2 s_lut[256];
-    __shared__ __attribute__((aligned(16))) uint8_t s_a[2][T_TILE * A_PITCH];
+    __shared__ __attribute__((aligned(16))) uint8_t s_a[2][T_TILE * MqPitch<W>::value];
     const int p = pair_base + blockIdx.y;
     const int sa = pair_a[p], sb = pair_b[p];
     const int n1 = min(nset[sa], cap), n2 = min(nset[sb], cap);
@@ -154,15 +200,22 @@ __global__ __launch_bounds__(MQ_T, 2) void k_match_topk_mfma(const uint8_t *__re
         __syncthreads();  // table ready
         // B fragments: lane (n = lane & 31, g = lane >> 5) holds, for instruction t, the k-slots 32 t + 16 g .. + 15 = descriptor bytes
         // 4 t + 2 g, 4 t + 2 g + 1 of query row0 + 32 qb + n, signs flipped
-        v4i bq[2][8];
+        v4i bq[2][W];
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
             const int q = min(row0 + 32 * qb + (lane & 31), n1 - 1);
-            const uint4 *qp = reinterpret_cast<const uint4 *>(desc + ((size_t)sa * cap + q) * 32);
-            const uint4 q0 = qp[0], q1 = qp[1];
-            const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+            const uint4 *qp = reinterpret_cast<const uint4 *>(desc + ((size_t)sa * cap + q) * (W * 4));
+            uint32_t w[W];
 #pragma unroll
-            for (int t = 0; t < 8; ++t) {
+            for (int h = 0; h < W / 4; ++h) {
+                const uint4 qv = qp[h];
+                w[4 * h] = qv.x;
+                w[4 * h + 1] = qv.y;
+                w[4 * h + 2] = qv.z;
+                w[4 * h + 3] = qv.w;
+            }
+#pragma unroll
+            for (int t = 0; t < W; ++t) {
                 const uint32_t h = (lane >> 5) ? (w[t] >> 16) : (w[t] & 0xffffu);
                 const uint2 e0 = s_lut[h & 255u], e1 = s_lut[h >> 8];
                 v4i v;
@@ -173,18 +226,18 @@ __global__ __launch_bounds__(MQ_T, 2) void k_match_topk_mfma(const uint8_t *__re
                 bq[qb][t] = v;
             }
         }
-        // B fragment of the index instruction: k-slots 256, 257 (lanes 0..31 hold them) carry the weights (1, 64)
+        // B fragment of the index instruction: k-slots 32 W, 32 W + 1 (lanes 0..31 hold them) carry the weights (1, 64)
         v4i bidx = {0, 0, 0, 0};
         if (lane < 32) bidx[0] = 1 | (64 << 8);
-        const uint32_t *train = reinterpret_cast<const uint32_t *>(desc + (size_t)sb * cap * 32);
+        const uint32_t *train = reinterpret_cast<const uint32_t *>(desc + (size_t)sb * cap * (W * 4));
         const bool wave_has_rows = row0 < n1;
-        mq_stage(train, n2, tile0 * T_TILE, s_lut, s_a[tile0 & 1], tid);
+        mq_stage<W>(train, n2, tile0 * T_TILE, s_lut, s_a[tile0 & 1], tid);
         __syncthreads();
         for (int tile = tile0; tile < tile1; ++tile) {
-            if (tile + 1 < tile1) mq_stage(train, n2, (tile + 1) * T_TILE, s_lut, s_a[(tile + 1) & 1], tid);
+            if (tile + 1 < tile1) mq_stage<W>(train, n2, (tile + 1) * T_TILE, s_lut, s_a[(tile + 1) & 1], tid);
             if (wave_has_rows) {
-                if ((tile + 1) * T_TILE <= n2) mq_compute<false>(s_a[tile & 1], bq, bidx, kk, tile * T_TILE, n2, lane);
-                else mq_compute<true>(s_a[tile & 1], bq, bidx, kk, tile * T_TILE, n2, lane);
+                if ((tile + 1) * T_TILE <= n2) mq_compute<false, W>(s_a[tile & 1], bq, bidx, kk, tile * T_TILE, n2, lane);
+                else mq_compute<true, W>(s_a[tile & 1], bq, bidx, kk, tile * T_TILE, n2, lane);
             }
             __syncthreads();
         }
@@ -215,7 +268,7 @@ __global__ __launch_bounds__(MQ_T, 2) void k_match_topk_mfma(const uint8_t *__re
             int s[7];
 #pragma unroll
             for (int i = 0; i < 7; ++i) {
-                const int D = m[i] + (1 << 20);
+                const int D = m[i] + (W == 8 ? (1 << 20) : (1 << 21));
                 s[i] = m[i] == NO_KEY ? NO_KEY : (((D >> 13) << 16) | (D & 8191));
             }
             int4 *rec = SLICED ? slice_rec + (((size_t)p * cap + row) * nslices + slice) * 2 : topk + ((size_t)p * cap + row) * 2;
@@ -270,13 +323,22 @@ __global__ __launch_bounds__(MQ_T, 2) void k_match_topk_mfma(const uint8_t *__re
     rec[1] = make_int4(m[4], m[5], m[6], max(nk, 1));
 }
 
-extern "C" void afv_launch_match_topk_mfma(const uint8_t *desc, const int *nset, int cap, const int *pa, const int *pb, int npairs,
-                                           void *topk_scratch, int pair_base, int nslices, void *slice_scratch, void *tickets, hipStream_t stream) {
+template <int W>
+static void launch_topk_mfma(const uint8_t *desc, const int *nset, int cap, const int *pa, const int *pb, int npairs, void *topk_scratch,
+                             int pair_base, int nslices, void *slice_scratch, void *tickets, hipStream_t stream) {
     int4 *topk = reinterpret_cast<int4 *>(topk_scratch);
     if (nslices > 1)
-        hipLaunchKernelGGL(k_match_topk_mfma<true>, dim3((cap + MQ_T - 1) / MQ_T * nslices, npairs), dim3(MQ_T), 0, stream, desc, nset, cap, pa, pb, topk,
-                           pair_base, nslices, reinterpret_cast<int4 *>(slice_scratch), reinterpret_cast<int *>(tickets));
+        hipLaunchKernelGGL((k_match_topk_mfma<true, W>), dim3((cap + MQ_T - 1) / MQ_T * nslices, npairs), dim3(MQ_T), 0, stream, desc, nset, cap, pa, pb,
+                           topk, pair_base, nslices, reinterpret_cast<int4 *>(slice_scratch), reinterpret_cast<int *>(tickets));
     else
-        hipLaunchKernelGGL(k_match_topk_mfma<false>, dim3((cap + MQ_T - 1) / MQ_T, npairs), dim3(MQ_T), 0, stream, desc, nset, cap, pa, pb, topk,
+        hipLaunchKernelGGL((k_match_topk_mfma<false, W>), dim3((cap + MQ_T - 1) / MQ_T, npairs), dim3(MQ_T), 0, stream, desc, nset, cap, pa, pb, topk,
                            pair_base, 1, static_cast<int4 *>(nullptr), static_cast<int *>(nullptr));
+}
+
+// words: dwords per row of `desc` (8 or 16)
+extern "C" void afv_launch_match_topk_mfma(const uint8_t *desc, const int *nset, int cap, const int *pa, const int *pb, int npairs,
+                                           void *topk_scratch, int pair_base, int nslices, void *slice_scratch, void *tickets, int words,
+                                           hipStream_t stream) {
+    if (words == 16) launch_topk_mfma<16>(desc, nset, cap, pa, pb, npairs, topk_scratch, pair_base, nslices, slice_scratch, tickets, stream);
+    else launch_topk_mfma<8>(desc, nset, cap, pa, pb, npairs, topk_scratch, pair_base, nslices, slice_scratch, tickets, stream);
 }

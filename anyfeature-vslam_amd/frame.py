@@ -141,7 +141,7 @@ class Frame:
             table, slots, idx = qref
             sl = np.ascontiguousarray(slots, np.int32); ix = np.ascontiguousarray(idx, np.int32)
             keep += [sl, ix]
-            s.qref_table = table.handle; s.qref_slot = ptr(sl); s.qref_idx = ptr(ix); s.desc_bytes = 32
+            s.qref_table = table.handle; s.qref_slot = ptr(sl); s.qref_idx = ptr(ix); s.desc_bytes = table.desc_bytes
         s.qvalid = ptr(q.valid); s.qu = ptr(q.u); s.qv = ptr(q.v); s.qr = ptr(q.r)
         s.qmin_size = ptr(q.min_size); s.qmax_size = ptr(q.max_size); s.qangle = ptr(q.angles); s.qoccupies = ptr(q.occupies)
         s.q_ur = ptr(q.ur); s.q_er_max = ptr(q.er_max)

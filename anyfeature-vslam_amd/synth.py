@@ -86,14 +86,15 @@ def perturbed_descriptors(desc, seed, flip_prob_256=26, replace_frac_256=77, ret
     return (out, repl) if return_mask else out
 
 
-def keyframe_table(nkeyframes, cap=1000, seed=7):
+def keyframe_table(nkeyframes, cap=1000, seed=7, nbytes=32):
     """config #4 table: K keyframes x cap x 32-byte descriptors, keyframe k+1 = keyframe k with each bit
     flipped w.p. ~0.1 and ~30 % of the rows replaced.  Angles (degrees) follow the keyframes: a common rotation of
     -10..10 degrees per step plus -1..1 degree of per-feature jitter; replaced rows get a fresh angle.
-    Returns (table uint8 [K, cap, 32], angles float32 [K, cap], counts int32 [K])."""
-    table = np.zeros((nkeyframes, cap, 32), np.uint8)
+    nbytes: descriptor width (the same recipe for AKAZE61 / BRISK48 / ... tables).
+    Returns (table uint8 [K, cap, nbytes], angles float32 [K, cap], counts int32 [K])."""
+    table = np.zeros((nkeyframes, cap, nbytes), np.uint8)
     angles = np.zeros((nkeyframes, cap), np.float32)
-    d = random_descriptors(seed, cap)
+    d = random_descriptors(seed, cap, nbytes)
     a = (lcg_states(seed + 1, cap) >> np.uint32(8)) % np.uint32(36000)
     a = a.astype(np.int64)                                    # centi-degrees: exact integer bookkeeping
     for k in range(nkeyframes):

@@ -69,12 +69,29 @@ def shard_range(n_units, rank, world):
 
 
 class DescriptorTable:
-    def __init__(self, ctx, nsets, cap):
+    """`desc_bytes`: width of the binary rows, 1 .. 64 (32 = ORB32, 61 = AKAZE61, 48 = BRISK48 ...).  The device keeps them zero-padded to
+    `pitch` = 32 (up to 32 bytes) or 64 bytes; host arrays in and out are `desc_bytes` wide."""
+
+    def __init__(self, ctx, nsets, cap, desc_bytes=32):
         self.ctx, self.lib = ctx, ctx.lib
         self.nsets, self.cap = int(nsets), int(cap)
+        if isinstance(desc_bytes, bool) or not isinstance(desc_bytes, (int, np.integer)) or not 1 <= int(desc_bytes) <= 64:
+            raise ValueError("desc_bytes must be an integer in 1..64, got %r" % (desc_bytes,))
+        self.desc_bytes = int(desc_bytes)
+        self.pitch = 32 if self.desc_bytes <= 32 else 64
         h = C.c_void_p()
-        ctx.check(self.lib.afv_table_create(ctx.handle, self.nsets, self.cap, C.byref(h)), "afv_table_create")
+        if self.desc_bytes == 32:
+            ctx.check(self.lib.afv_table_create(ctx.handle, self.nsets, self.cap, C.byref(h)), "afv_table_create")
+        else:
+            ctx.check(self.lib.afv_table_create_bytes(ctx.handle, self.nsets, self.cap, self.desc_bytes, C.byref(h)), "afv_table_create_bytes")
         self.handle = h
+
+    def _rows(self, desc, what):
+        """host rows as a contiguous (n, desc_bytes) uint8 array; a row of another width raises before any library call"""
+        a = np.asarray(desc)
+        if a.ndim != 2 or a.shape[1] != self.desc_bytes:
+            raise ValueError("%s: rows must be (n, %d) uint8 for this table, got shape %s" % (what, self.desc_bytes, a.shape))
+        return np.ascontiguousarray(a, np.uint8)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -89,7 +106,10 @@ class DescriptorTable:
 
     # ---- filling ----
     def set(self, slot, desc, angles=None):
-        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        if self.desc_bytes == 32:
+            desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        else:
+            desc = self._rows(desc, "DescriptorTable.set")
         ang = None if angles is None else np.ascontiguousarray(angles, np.float32)
         self.ctx.check(self.lib.afv_table_set(self.handle, int(slot), ptr(desc), ptr(ang), len(desc)), "afv_table_set")
 
@@ -112,7 +132,8 @@ class DescriptorTable:
         self.ctx.check(self.lib.afv_table_set_valid(self.handle, int(slot), ptr(v)), "afv_table_set_valid")
 
     def device_views(self):
-        """zero-copy torch views of the table: desc uint8 [nsets, cap, 32], angle float32 [nsets, cap], n int32 [nsets]"""
+        """zero-copy torch views of the table: desc uint8 [nsets, cap, pitch] (rows zero-padded from desc_bytes), angle float32
+        [nsets, cap], n int32 [nsets]"""
         import torch
         d, a, n = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self.ctx.check(self.lib.afv_table_device_ptrs(self.handle, C.byref(d), C.byref(a), C.byref(n)))
@@ -125,17 +146,29 @@ class DescriptorTable:
             typestr = {torch.uint8: "|u1", torch.float32: "<f4", torch.int32: "<i4"}[dtype]
             h.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (p.value, False), "version": 2}
             return torch.as_tensor(h, device=dev)
-        return (view(d, self.nsets * self.cap * 32, torch.uint8, (self.nsets, self.cap, 32)),
+        return (view(d, self.nsets * self.cap * self.pitch, torch.uint8, (self.nsets, self.cap, self.pitch)),
                 view(a, self.nsets * self.cap * 4, torch.float32, (self.nsets, self.cap)),
                 view(n, self.nsets * 4, torch.int32, (self.nsets,)))
 
     def upload(self, table, angles, counts):
-        """fill every slot from host arrays [nsets, cap, 32] / [nsets, cap] / [nsets]: three bulk copies through the
+        """fill every slot from host arrays [nsets, cap, desc_bytes] / [nsets, cap] / [nsets]: three bulk copies through the
         zero-copy views when torch can wrap the pointers, else one afv_table_set per slot"""
+        if self.desc_bytes != 32:
+            t = np.asarray(table)
+            if t.shape != (self.nsets, self.cap, self.desc_bytes):
+                raise ValueError("DescriptorTable.upload: table must be (%d, %d, %d) uint8, got shape %s" % (self.nsets, self.cap, self.desc_bytes, t.shape))
+            if self.pitch != self.desc_bytes:  # the device rows carry zero padding
+                padded = np.zeros((self.nsets, self.cap, self.pitch), np.uint8)
+                padded[:, :, :self.desc_bytes] = t
+                t_dev = padded
+            else:
+                t_dev = t
+        else:
+            t_dev = table
         try:
             import torch
             d, a, n = self.device_views()
-            d.copy_(torch.from_numpy(np.ascontiguousarray(table, np.uint8)))
+            d.copy_(torch.from_numpy(np.ascontiguousarray(t_dev, np.uint8)))
             a.copy_(torch.from_numpy(np.ascontiguousarray(angles, np.float32)))
             n.copy_(torch.from_numpy(np.ascontiguousarray(counts, np.int32)))
             torch.cuda.synchronize(d.device)
@@ -201,7 +234,10 @@ class DescriptorTable:
         the keyframes in `slots`.  Returns match_f[nslots, frame.N] (keyframe feature per frame feature, -1 = none) and nmatches[nslots]"""
         from ._lib import FrameView
         sl = _i32(slots)
-        desc = np.ascontiguousarray(frame.descriptors, np.uint8).reshape(-1, 32)
+        if self.desc_bytes == 32:
+            desc = np.ascontiguousarray(frame.descriptors, np.uint8).reshape(-1, 32)
+        else:
+            desc = self._rows(frame.descriptors, "DescriptorTable.match_bow_frame")
         ids, sp, flat, nn = frame.csr()
         ids, sp, flat = _i32(ids), _i32(sp), _i32(flat)
         ang = None if frame.angles is None else np.ascontiguousarray(frame.angles, np.float32)

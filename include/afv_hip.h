@@ -202,9 +202,16 @@ int afv_match_bruteforce_pairs_device(afv_ctx *ctx, const uint8_t *d_desc, const
  * per array over xGMI (afv_table_broadcast); every rank then matches its own share of the jobs against its replica.
  * A table belongs to the context it was created on and is destroyed before it. */
 typedef struct afv_table afv_table;
+/* a table of 32-byte binary rows (ORB32) */
 int afv_table_create(afv_ctx *ctx, int nsets, int cap /* <= 4096 */, afv_table **out);
+/* a table of binary rows of desc_bytes = 1 .. 64 bytes (61 AKAZE, 48 BRISK, 64 FREAK ...), stored zero-padded to a pitch of 32 bytes
+ * (desc_bytes <= 32) or 64 bytes (33 .. 64), the rule of resident frames.  Every afv_table_* entry point works at that width with the
+ * reference's rules unchanged; a frame meets the table only when it is binary with the same desc_bytes (else AFV_EUNSUPPORTED).
+ * afv_table_create(ctx, nsets, cap, out) is afv_table_create_bytes(ctx, nsets, cap, 32, out).  Float rows stay out of the table. */
+int afv_table_create_bytes(afv_ctx *ctx, int nsets, int cap /* <= 4096 */, int desc_bytes, afv_table **out);
 void afv_table_destroy(afv_table *t);
-/* upload keyframe `set`: n x 32-byte descriptors, angles[n] in degrees (NULL = zeros).  Host pointers; synchronous. */
+/* upload keyframe `set`: n x desc_bytes descriptors (packed; 32 for afv_table_create), angles[n] in degrees (NULL = zeros).
+ * The library writes the rows' padding (zero).  Host pointers; synchronous. */
 int afv_table_set(afv_table *t, int set, const uint8_t *desc32, const float *angles, int n);
 /* the keyframe's FeatureVector as CSR over ascending node ids (as in afv_match_job); needed by afv_table_match_bow only.
  * The node ids / segment sizes stay on the host too (the merge-join of two FeatureVectors, FeatureMatcher.cc:205-276,
@@ -215,7 +222,8 @@ int afv_table_set_featvec(afv_table *t, int set, const int32_t *node_id, const i
  * :609-613; it changes as the map evolves, so the host re-uploads the n bytes when it does).  NULL = every feature valid (the
  * default).  The brute-force pair entry points take every feature as valid. */
 int afv_table_set_valid(afv_table *t, int set, const uint8_t *valid);
-/* device views for zero-copy callers: d_desc[nsets][cap][32], d_angle[nsets][cap] (float), d_n[nsets] (int32) */
+/* device views for zero-copy callers: d_desc[nsets][cap][pitch] (pitch 32 or 64 bytes, see afv_table_create_bytes; a writer keeps the
+ * padding zero), d_angle[nsets][cap] (float), d_n[nsets] (int32) */
 int afv_table_device_ptrs(afv_table *t, uint8_t **d_desc, float **d_angle, int32_t **d_n);
 /* brute-force SearchByBoW(KF,KF) (FeatureMatcher.cc:561-660 with one node holding everything) of npairs (a, b) slot
  * pairs.  pair arrays are HOST int32; outputs are HOST arrays: match12[npairs][cap] (may be NULL: counts only) and
@@ -239,7 +247,7 @@ int afv_table_match_bow(afv_table *t, const int32_t *pair_a, const int32_t *pair
  * Host pointers.  match_f[nslots][frame->n] = index of the matched keyframe feature per FRAME feature or -1 (may be NULL: counts
  * only); nmatches[nslots]. */
 typedef struct {
-    const uint8_t *desc32; int32_t n;   /* the frame's n x 32-byte descriptors (Frame::mDescriptors) */
+    const uint8_t *desc32; int32_t n;   /* the frame's n x desc_bytes descriptors (Frame::mDescriptors), packed at the table's width */
     const float *angle;                 /* mvKeysUn[i].angle in degrees; required iff check_orientation */
     /* Frame::mFeatVec as CSR over ascending node ids (as in afv_match_job); nnodes == 0: the frame shares no node with anybody */
     const int32_t *node_id; const int32_t *seg_ptr; const int32_t *seg_idx; int32_t nnodes;
@@ -446,15 +454,16 @@ typedef struct {
     int32_t desc_bytes;               /* (ABI 6) bytes of one binary descriptor, 1 .. 64: 32 ORB (0 = 32), 61 AKAZE, 48 BRISK ... - the reference's
                                          matchers dispatch on DescriptorType (FeatureMatcher.cc:1508-1531).  Rows live zero-padded to 8 or 16
                                          dwords in HBM.  A frame that is not 32-byte is filled with afv_frame_set_features (afv_frame_extract
-                                         is the ORB32 extractor; the keyframe TABLE holds 32-byte rows only: afv_table_set_from_frame /
-                                         afv_table_match_bow_frame_h answer AFV_EUNSUPPORTED for it) and serves afv_frame_bow_transform with a
+                                         is the ORB32 extractor; a keyframe TABLE of the same desc_bytes (afv_table_create_bytes) takes it
+                                         in afv_table_set_from_frame / afv_table_match_bow_frame_h, a table of another width answers
+                                         AFV_EUNSUPPORTED) and serves afv_frame_bow_transform with a
                                          vocabulary of the same descriptor size, afv_frame_match_projection / _fuse / _initialization */
     int32_t float_dim;                /* (ABI 6, appended) > 0: the frame holds FLOAT descriptors of float_dim floats (a multiple of 4, <= 1024:
                                          SIFT128, SURF64, KAZE64, R2D2 ...; desc_bytes is ignored): afv_frame_set_features takes the rows as
                                          n x float_dim floats behind its uint8_t pointer, afv_frame_bow_transform wants a float vocabulary of
                                          that dimension (afv_vocab_create_f32), the projection searches and SearchForInitialization use
                                          L2^2 distances (afv_proj_job.float_dim; afv_proj_queries.qdesc = nq x float_dim floats,
-                                         desc_bytes = 4 * float_dim).  Like every frame that is not 32-byte it stays out of the keyframe
+                                         desc_bytes = 4 * float_dim).  Unlike a binary frame it stays out of every keyframe
                                          table: SearchByBoW(KF, F) on float rows is afv_match_bow with AFV_MATCH_FLOAT32 and the frame's
                                          FeatureVector (afv_frame_get_featvec) */
 } afv_frame_params;
@@ -503,7 +512,8 @@ typedef struct {
     int32_t check_orientation, mode;                    /* mode: AFV_PROJ_LOCALMAP / AFV_PROJ_LASTFRAME */
     /* the queries' descriptors by reference instead of by value: a map point's descriptor is a row of the keyframe that observed it
      * (MapPoint::ComputeDistinctDescriptors copies pKF->mDescriptors.row(idx)), so when that keyframe sits in an afv_table the row is
-     * gathered on the device: qref_table + qref_slot[nq] + qref_idx[nq] (qdesc NULL).  8 bytes per query instead of 32. */
+     * gathered on the device: qref_table + qref_slot[nq] + qref_idx[nq] (qdesc NULL).  8 bytes per query instead of desc_bytes.  The table's
+     * desc_bytes must be the frame's (else AFV_EUNSUPPORTED). */
     afv_table *qref_table; const int32_t *qref_slot; const int32_t *qref_idx;
 } afv_proj_queries;
 /* SearchByProjection(F, vpMapPoints, th) (FeatureMatcher.cc:73-154) / SearchByProjection(CurrentFrame, LastFrame, th, mono) (:1291-1402)
