@@ -129,6 +129,7 @@ SYMBOLS = {
     "afv_match_bruteforce_pairs_device": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _i, _vp, _vp, _vp]),
     "afv_table_create": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
     "afv_table_create_bytes": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "afv_table_create_f32": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
     "afv_table_destroy": (None, [_vp]),
     "afv_table_set": (_i, [_vp, _i, _vp, _vp, _i]),
     "afv_table_set_featvec": (_i, [_vp, _i, _vp, _vp, _vp, _i]),

@@ -1743,6 +1743,29 @@ extern "C" int afv_match_l2(afv_ctx *c, const float *desc1, int n1, const float 
 
 // device-resident batch of the float-descriptor matcher (config #3 as a throughput path, like afv_match_bruteforce_pairs_device for
 // ORB32): the key scratch is the Hamming path's grow-only buffer (32 B per row there as well)
+int afv_match_l2_pairs_core(afv_ctx *c, const float *d_desc, const float *d_ang, const int32_t *d_n, int cap, int dim, const int32_t *d_pair_a,
+                            const int32_t *d_pair_b, int npairs, float th_low, float nnratio, int32_t *d_match, int32_t *d_nmatches, hipStream_t s) {
+    const int chunk = std::min(npairs, c->l2_chunk_pairs);  // pairs per launch: grid.y and the scratch stay bounded
+    // the float matcher's own key scratch: the Hamming pair calls keep theirs (d_topk) busy on the context's streams, and a caller
+    // may run the two kinds on different streams of one context
+    const size_t need = (size_t)chunk * cap * 32;
+    if (need > c->l2_bytes) {  // grow-only (first call / larger batch): implies a device sync
+        HIPCHK(c, hipDeviceSynchronize());
+        if (c->d_l2_scratch) (void)hipFree(c->d_l2_scratch);
+        c->d_l2_scratch = nullptr;
+        c->l2_bytes = 0;
+        HIPCHK(c, hipMalloc(&c->d_l2_scratch, need));
+        c->l2_bytes = need;
+    }
+    // chunks reuse the scratch one after the other: same stream, so chunk k + 1 starts after chunk k has read its keys
+    for (int b0 = 0; b0 < npairs; b0 += chunk)
+        if (!afv_launch_match_l2_pairs(d_desc, d_n, cap, dim, d_pair_a, d_pair_b, std::min(chunk, npairs - b0), b0, th_low, nnratio, d_ang, d_match,
+                                       d_nmatches, c->d_l2_scratch, s))
+            return AFV_EUNSUPPORTED;
+    HIPCHK(c, hipGetLastError());
+    return AFV_OK;
+}
+
 extern "C" int afv_match_l2_pairs_device(afv_ctx *c, const float *d_desc, const int32_t *d_n, int cap, int dim, const int32_t *d_pair_a,
                                          const int32_t *d_pair_b, int npairs, float th_low, float nnratio, int32_t *d_match,
                                          int32_t *d_nmatches, void *stream) {
@@ -1752,26 +1775,8 @@ extern "C" int afv_match_l2_pairs_device(afv_ctx *c, const float *d_desc, const 
         if (dim != 64 && dim != 128) return AFV_EUNSUPPORTED;
         if (npairs == 0) return AFV_OK;
         HIPCHK(c, hipSetDevice(c->device));
-        hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-        const int chunk = std::min(npairs, c->l2_chunk_pairs);  // pairs per launch: grid.y and the scratch stay bounded
-        // the float matcher's own key scratch: the Hamming pair calls keep theirs (d_topk) busy on the context's streams, and a caller
-        // may run the two kinds on different streams of one context
-        const size_t need = (size_t)chunk * cap * 32;
-        if (need > c->l2_bytes) {  // grow-only (first call / larger batch): implies a device sync
-            HIPCHK(c, hipDeviceSynchronize());
-            if (c->d_l2_scratch) (void)hipFree(c->d_l2_scratch);
-            c->d_l2_scratch = nullptr;
-            c->l2_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->d_l2_scratch, need));
-            c->l2_bytes = need;
-        }
-        // chunks reuse the scratch one after the other: same stream, so chunk k + 1 starts after chunk k has read its keys
-        for (int b0 = 0; b0 < npairs; b0 += chunk)
-            if (!afv_launch_match_l2_pairs(d_desc, d_n, cap, dim, d_pair_a, d_pair_b, std::min(chunk, npairs - b0), b0, th_low, nnratio, d_match,
-                                           d_nmatches, c->d_l2_scratch, s))
-                return AFV_EUNSUPPORTED;
-        HIPCHK(c, hipGetLastError());
-        return AFV_OK;
+        return afv_match_l2_pairs_core(c, d_desc, nullptr, d_n, cap, dim, d_pair_a, d_pair_b, npairs, th_low, nnratio, d_match, d_nmatches,
+                                       stream ? (hipStream_t)stream : c->stream);
     });
 }
 
@@ -1841,7 +1846,7 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
         if (by_ref) {
             // MapPoint descriptors by reference (rows of a keyframe table): checked here, gathered on the device behind the upload
             const afv_table *qt = dev->qref_table;
-            if (qt->c != c || !dev->qref_slot || !dev->qref_idx || j.float_dim || j.desc_bytes != qt->desc_bytes) return AFV_EINVAL;
+            if (qt->c != c || !dev->qref_slot || !dev->qref_idx || j.float_dim != qt->float_dim || j.desc_bytes != qt->desc_bytes) return AFV_EINVAL;
             for (int q = 0; q < j.nq; ++q) {
                 const int sl = dev->qref_slot[q];
                 if (sl < 0 || sl >= qt->nsets || dev->qref_idx[q] < 0 || dev->qref_idx[q] >= qt->h_n[sl]) return AFV_EINVAL;

@@ -7,7 +7,9 @@
 // that are const after keyframe construction (include/KeyFrame.h:190).  Here they are uploaded ONCE into a table
 // [nsets][cap][pitch] and batches of (a, b) jobs run against it; only pair lists go in and match vectors come out.  Binary descriptors of
 // 1 to 64 bytes: rows zero-padded to a pitch of 32 bytes (up to 32-byte descriptors) or 64 bytes (33 to 64), the rule of resident frames;
-// the padding is zero on both sides of every distance, so it adds nothing.
+// the padding is zero on both sides of every distance, so it adds nothing.  Float descriptors (afv_table_create_f32: SIFT128, SURF64,
+// KAZE64 ...): rows of float_dim floats without padding, the fields of a resident float frame (desc_bytes = 4 * float_dim, words =
+// float_dim); the distance is L2^2 as cv::norm evaluates it (k_match_l2.hip, the W == 0 instantiations of k_match.hip).
 //
 // Multi-GPU: one process per GPU; the table is replicated with ONE ncclBroadcast per array (RCCL over
 // xGMI), jobs are block-partitioned (afv_shard_range), no other data-path collective exists.  RCCL is resolved at run
@@ -58,7 +60,7 @@ static void table_free(afv_table *t) {
 
 static inline size_t table_pitch(const afv_table *t) { return (size_t)t->words * 4; }
 
-static int table_create(afv_ctx *c, int nsets, int cap, int desc_bytes, afv_table **out) {
+static int table_create(afv_ctx *c, int nsets, int cap, int desc_bytes, afv_table **out, int float_dim = 0) {
     if (!c || !out || nsets < 1 || cap < 1 || cap > 4096) return AFV_EINVAL;
     *out = nullptr;
     HIPCHK(c, hipSetDevice(c->device));
@@ -68,7 +70,8 @@ static int table_create(afv_ctx *c, int nsets, int cap, int desc_bytes, afv_tabl
     t->nsets = nsets;
     t->cap = cap;
     t->desc_bytes = desc_bytes;
-    t->words = desc_bytes <= 32 ? 8 : 16;
+    t->words = float_dim ? float_dim : (desc_bytes <= 32 ? 8 : 16);
+    t->float_dim = float_dim;
     hipError_t e = hipMalloc(&t->d_desc, (size_t)nsets * cap * table_pitch(t));
     // rows narrower than their pitch: the padding starts (and, since every writer writes whole padded rows, stays) zero
     if (e == hipSuccess && (size_t)desc_bytes != table_pitch(t)) e = afv_fill(c, t->d_desc, 0, (size_t)nsets * cap * table_pitch(t));
@@ -104,6 +107,11 @@ extern "C" int afv_table_create(afv_ctx *c, int nsets, int cap, afv_table **out)
 extern "C" int afv_table_create_bytes(afv_ctx *c, int nsets, int cap, int desc_bytes, afv_table **out) {
     if (desc_bytes < 1 || desc_bytes > 64) return AFV_EINVAL;
     return table_create(c, nsets, cap, desc_bytes, out);
+}
+
+extern "C" int afv_table_create_f32(afv_ctx *c, int nsets, int cap, int float_dim, afv_table **out) {
+    if (float_dim < 4 || float_dim > 1024 || (float_dim & 3)) return AFV_EINVAL;  // the rule of afv_frame_params.float_dim
+    return table_create(c, nsets, cap, 4 * float_dim, out, float_dim);
 }
 
 extern "C" void afv_table_destroy(afv_table *t) {
@@ -311,7 +319,10 @@ static int table_unpack_meta(afv_table *t, const int32_t *blob, size_t len) {
 }
 
 extern "C" int afv_table_clone(const afv_table *src, afv_table *dst) {
-    if (!src || !dst || src == dst || src->nsets != dst->nsets || src->cap != dst->cap || src->desc_bytes != dst->desc_bytes) return AFV_EINVAL;
+    if (!src || !dst || src == dst || src->nsets != dst->nsets || src->cap != dst->cap) return AFV_EINVAL;
+    // another kind or float dimension (the pitch does not tell: 64 bytes and 16 floats share one); two binary widths: AFV_EINVAL as before
+    if (src->float_dim != dst->float_dim) return AFV_EUNSUPPORTED;
+    if (src->desc_bytes != dst->desc_bytes) return AFV_EINVAL;
     afv_ctx *c = dst->c;
     return guarded(c, [&]() -> int {
         HIPCHK(c, hipSetDevice(src->c->device));
@@ -372,6 +383,10 @@ extern "C" int afv_table_match_pairs_device(afv_table *t, const int32_t *d_pair_
     if (!t || !d_pair_a || !d_pair_b || npairs < 1 || !d_match12 || !d_nmatches) return AFV_EINVAL;
     afv_ctx *c = t->c;
     HIPCHK(c, hipSetDevice(c->device));
+    if (t->float_dim)
+        return afv_match_l2_pairs_core(c, reinterpret_cast<const float *>(t->d_desc), check_orientation ? t->d_angle : nullptr, t->d_n, t->cap,
+                                       t->float_dim, d_pair_a, d_pair_b, npairs, th_low, nnratio, d_match12, d_nmatches,
+                                       stream ? (hipStream_t)stream : c->stream);
     return afv_match_pairs_core(c, t->d_desc, t->d_angle, 1, t->d_n, t->cap, d_pair_a, d_pair_b, npairs, th_low, nnratio,
                                 check_orientation, d_match12, d_nmatches, stream ? (hipStream_t)stream : c->stream, t->words);
 }
@@ -388,8 +403,12 @@ extern "C" int afv_table_match_pairs(afv_table *t, const int32_t *pair_a, const 
     std::memcpy(hp, pair_a, (size_t)npairs * sizeof(int32_t));
     std::memcpy(hp + t->pair_cap, pair_b, (size_t)npairs * sizeof(int32_t));
     HIPCHK(c, hipMemcpyAsync(t->d_pairs, hp, (size_t)t->pair_cap * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    rc = afv_match_pairs_core(c, t->d_desc, t->d_angle, 1, t->d_n, t->cap, t->d_pairs, t->d_pairs + t->pair_cap, npairs, th_low, nnratio,
-                              check_orientation, t->d_out, t->d_nm, c->stream, t->words);
+    if (t->float_dim)
+        rc = afv_match_l2_pairs_core(c, reinterpret_cast<const float *>(t->d_desc), check_orientation ? t->d_angle : nullptr, t->d_n, t->cap,
+                                     t->float_dim, t->d_pairs, t->d_pairs + t->pair_cap, npairs, th_low, nnratio, t->d_out, t->d_nm, c->stream);
+    else
+        rc = afv_match_pairs_core(c, t->d_desc, t->d_angle, 1, t->d_n, t->cap, t->d_pairs, t->d_pairs + t->pair_cap, npairs, th_low, nnratio,
+                                  check_orientation, t->d_out, t->d_nm, c->stream, t->words);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(h_nm, t->d_nm, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (match12)
@@ -459,7 +478,8 @@ static int table_match_bow_impl(afv_table *t, const int32_t *pair_a, const int32
         d.d2 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)bb * cap * table_pitch(t));
         d.n1 = t->h_n[a];
         d.n2 = t->h_n[bb];
-        d.words = t->words;
+        d.words = t->float_dim ? 0 : t->words;
+        d.fdim = t->float_dim;
         d.segs = reinterpret_cast<const Seg *>(c->d_match + segs_off) + seg_first[p];
         d.nseg = seg_first[p + 1] - seg_first[p];
         d.idx1 = t->d_idx + (size_t)a * cap;
@@ -546,7 +566,7 @@ static int table_match_bow_frame_impl(afv_table *t, const int32_t *slots, int ns
     }
     const int nfe = std::max(nf, 1);
     // the frame view's rows are packed at the table's width; the device rows are padded to its pitch
-    const size_t fdesc_off = fr ? 0 : (t->desc_bytes == AFV_DESC_BYTES ? b.put(F->desc32, (size_t)nf * 32) : put_desc(b, F->desc32, nf, t->desc_bytes, t->words));
+    const size_t fdesc_off = fr ? 0 : ((t->float_dim || t->desc_bytes == AFV_DESC_BYTES) ? b.put(F->desc32, (size_t)nf * t->desc_bytes) : put_desc(b, F->desc32, nf, t->desc_bytes, t->words));
     const size_t fang_off = (!fr && check_orientation && nf) ? b.put(F->angle, (size_t)nf * sizeof(float)) : 0;
     const size_t fidx_off = fr ? 0 : b.put(F->nnodes > 0 ? F->seg_idx : nullptr, (size_t)(F->nnodes > 0 ? FV.seg_ptr[F->nnodes] : 0) * sizeof(int32_t));
     const size_t segs_off = b.put(segs.data(), segs.size() * sizeof(Seg));
@@ -569,7 +589,8 @@ static int table_match_bow_frame_impl(afv_table *t, const int32_t *slots, int ns
         d.d2 = fr ? reinterpret_cast<const uint32_t *>(fr->d_desc) : reinterpret_cast<const uint32_t *>(c->d_match + fdesc_off);
         d.n1 = t->h_n[a];
         d.n2 = nf;
-        d.words = t->words;
+        d.words = t->float_dim ? 0 : t->words;
+        d.fdim = t->float_dim;
         d.segs = reinterpret_cast<const Seg *>(c->d_match + segs_off) + seg_first[p];
         d.nseg = seg_first[p + 1] - seg_first[p];
         d.idx1 = t->d_idx + (size_t)a * cap;
@@ -614,7 +635,7 @@ extern "C" int afv_table_match_bow_frame_h(afv_table *t, const int32_t *slots, i
                                            int check_orientation, int32_t *match_f, int32_t *nmatches) {
     if (!t || !slots || nslots < 1 || !f || !nmatches) return AFV_EINVAL;
     if (f->c != t->c || !f->has_features || !f->has_fv) return AFV_EINVAL;  // afv_frame_bow_transform first
-    if (f->float_dim || f->desc_bytes != t->desc_bytes) return AFV_EUNSUPPORTED;  // binary rows of the table's width only
+    if (f->float_dim != t->float_dim || f->desc_bytes != t->desc_bytes) return AFV_EUNSUPPORTED;  // rows of the table's kind and width / float dimension only
     afv_frame_view view{};
     view.n = f->n;
     return guarded(t->c, [&] { return table_match_bow_frame_impl(t, slots, nslots, &view, th_low, nnratio, check_orientation, match_f, nmatches, f); });
@@ -624,7 +645,7 @@ extern "C" int afv_table_match_bow_frame_h(afv_table *t, const int32_t *slots, i
 // table planes; the FeatureVector's node structure goes host to host
 extern "C" int afv_table_set_from_frame(afv_table *t, int slot, afv_frame *f) {
     if (!t || !f || slot < 0 || slot >= t->nsets || f->c != t->c || !f->has_features) return AFV_EINVAL;
-    if (f->float_dim || f->desc_bytes != t->desc_bytes) return AFV_EUNSUPPORTED;  // binary rows of the table's width only
+    if (f->float_dim != t->float_dim || f->desc_bytes != t->desc_bytes) return AFV_EUNSUPPORTED;  // rows of the table's kind and width / float dimension only
     if (f->n > t->cap) return AFV_ECAPACITY;
     afv_ctx *c = t->c;
     return guarded(c, [&]() -> int {
@@ -742,7 +763,8 @@ static int table_match_tri_impl(afv_table *t, const int32_t *pair_a, const int32
         d.n1 = t->h_n[a];
         d.n2 = t->h_n[bb];
         max_n1 = std::max(max_n1, d.n1);
-        d.words = t->words;
+        d.words = t->float_dim ? 0 : t->words;
+        d.fdim = t->float_dim;
         d.segs = reinterpret_cast<const Seg *>(c->d_match + segs_off) + seg_first[p];
         d.nseg = seg_first[p + 1] - seg_first[p];
         d.idx1 = t->d_idx + (size_t)a * cap;
@@ -930,17 +952,19 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         // ... and its shape: every rank compares it with its own table and ALL ranks learn every verdict (one all-gather of a flag) before any
         // plane moves, so that a table of another shape or row width on any rank is refused everywhere instead of mismatching the
         // lengths of the broadcasts below
-        int32_t flags[7] = {t->d_idx != nullptr, t->d_geo != nullptr, t->d_valid != nullptr, (int32_t)blob.size(), t->nsets, t->cap, t->desc_bytes};
+        // (the kind travels next to the width: 64-byte binary rows and rows of 16 floats have the same pitch and the same byte size)
+        int32_t flags[8] = {t->d_idx != nullptr, t->d_geo != nullptr, t->d_valid != nullptr, (int32_t)blob.size(), t->nsets, t->cap, t->desc_bytes, t->float_dim};
         int32_t *d_flags = nullptr;
         HIPCHK(c, hipMalloc(&d_flags, sizeof(flags) + (size_t)(m->nranks + 1) * sizeof(int32_t)));
-        int32_t *d_ok = d_flags + 7, *d_oks = d_ok + 1;
+        int32_t *d_ok = d_flags + 8, *d_oks = d_ok + 1;
         hipError_t e = hipMemcpyAsync(d_flags, flags, sizeof(flags), hipMemcpyHostToDevice, c->stream);
         int rc = e == hipSuccess ? afv_comm_broadcast(m, d_flags, sizeof(flags), root, c->stream) : AFV_EHIP;
         if (rc == AFV_OK) e = hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream);
         if (rc == AFV_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
         std::vector<int32_t> oks((size_t)m->nranks, 0);
         if (rc == AFV_OK && e == hipSuccess) {
-            const int32_t ok = flags[4] == t->nsets && flags[5] == t->cap && flags[6] == t->desc_bytes;
+            // 1: the root's shape; 2: its nsets and cap, but another kind or float dimension; 0: any other difference
+            const int32_t ok = !(flags[4] == t->nsets && flags[5] == t->cap) ? 0 : (flags[7] != t->float_dim ? 2 : flags[6] == t->desc_bytes);
             e = hipMemcpyAsync(d_ok, &ok, sizeof(ok), hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) rc = afv_comm_allgather(m, d_ok, d_oks, sizeof(int32_t), c->stream);
             if (rc == AFV_OK && e == hipSuccess) e = hipMemcpyAsync(oks.data(), d_oks, oks.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
@@ -949,6 +973,11 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         (void)hipFree(d_flags);
         if (rc) return rc;
         HIPCHK(c, e);
+        for (int32_t ok : oks)
+            if (ok == 2) {
+                c->last_error = "afv_table_broadcast: the tables of the ranks differ in kind (binary / float) or float_dim";
+                return AFV_EUNSUPPORTED;
+            }
         for (int32_t ok : oks)
             if (!ok) {
                 c->last_error = "afv_table_broadcast: the tables of the ranks differ in nsets, cap or desc_bytes";

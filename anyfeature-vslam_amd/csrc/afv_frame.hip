@@ -406,7 +406,7 @@ static int frame_match(afv_frame *f, const afv_proj_queries *caller_q, int kind,
         std::memcpy(&q, caller_q, std::min<size_t>(ss, sizeof(q)));
         if (q.nq < 0 || q.nq > 65535) return AFV_EINVAL;
         if (q.nq > 0 && q.desc_bytes != f->desc_bytes && !q.qref_table) return AFV_EINVAL;
-        if (q.qref_table && (f->float_dim || f->desc_bytes != q.qref_table->desc_bytes)) return AFV_EUNSUPPORTED;  // rows of another width / kind
+        if (q.qref_table && (f->float_dim != q.qref_table->float_dim || f->desc_bytes != q.qref_table->desc_bytes)) return AFV_EUNSUPPORTED;  // rows of another width / kind
         ProjFeatureSide S;
         frame_side(f, S);
         if (kind == AFV_KIND_FUSE && !use_inf_gate) S.inf = nullptr;

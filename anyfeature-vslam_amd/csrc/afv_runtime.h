@@ -90,7 +90,8 @@ extern "C" int afv_launch_match_l2_tiled(const float *d1, int n1, const float *d
                                          float th, float ratio, int *out, int *nmatches, void *scratch, int ntiles, int cols_per_tile,
                                          hipStream_t stream);
 extern "C" int afv_launch_match_l2_pairs(const float *desc, const int *nset, int cap, int dim, const int *pa, const int *pb, int npairs,
-                                         int pair_base, float th, float ratio, int *out, int *nmatches, void *scratch, hipStream_t stream);
+                                         int pair_base, float th, float ratio, const float *ang, int *out, int *nmatches, void *scratch,
+                                         hipStream_t stream);
 extern "C" void afv_launch_match_init(const DevProjJob *jobs, int njobs, int max_nq, size_t wg_lds, const DevProjJob *one, int *ticket,
                                       hipStream_t stream);
 
@@ -433,6 +434,7 @@ struct afv_table {
     afv_ctx *c = nullptr;
     int nsets = 0, cap = 0;
     int desc_bytes = 32, words = 8;  // descriptor size and dwords per zero-padded row: 8 up to 32 bytes, 16 up to 64 (afv_table_create_bytes)
+    int float_dim = 0;               // > 0: rows of float_dim floats (afv_table_create_f32): desc_bytes = 4 * float_dim, words = float_dim, no padding - the fields of a float frame
     uint8_t *d_desc = nullptr;  // [nsets][cap][4 * words]
     float *d_angle = nullptr;   // [nsets][cap]
     int32_t *d_n = nullptr;     // [nsets]
@@ -456,6 +458,10 @@ struct afv_table {
 int afv_match_pairs_core(afv_ctx *c, const uint8_t *d_desc, const float *d_ang, int ang_stride, const int32_t *d_n, int cap,
                          const int32_t *d_pair_a, const int32_t *d_pair_b, int npairs, float th_low, float nnratio,
                          int check_orientation, int32_t *d_match, int32_t *d_nmatches, hipStream_t s, int words);
+// chunked launches of the float pair matcher (k_match_l2.hip) behind afv_match_l2_pairs_device and the pair entry points of a float table;
+// d_ang != null: ang[set][cap] in degrees, the rotation histogram is applied
+int afv_match_l2_pairs_core(afv_ctx *c, const float *d_desc, const float *d_ang, const int32_t *d_n, int cap, int dim, const int32_t *d_pair_a,
+                            const int32_t *d_pair_b, int npairs, float th_low, float nnratio, int32_t *d_match, int32_t *d_nmatches, hipStream_t s);
 void afv_shared_segments(const afv_match_job &j, std::vector<Seg> &segs);
 int afv_check_resolve_guard(afv_ctx *c, const int32_t *nmatches, int n);
 void afv_table_release_all(afv_ctx *c);  // afv_destroy: tables / communicators still alive die with their context

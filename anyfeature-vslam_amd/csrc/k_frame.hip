@@ -249,11 +249,29 @@ __global__ __launch_bounds__(256) void k_frame_gather(const uint8_t *__restrict_
     out[Q * q + h] = v;
 }
 
-// words: dwords per row of the table (8 or 16)
+// rows of any number of 16-byte quads (a float row: float_dim / 4): a thread per 16 bytes, the divisions by the launch-invariant quad
+// count as afv_udiv
+__global__ __launch_bounds__(256) void k_frame_gather_rt(const uint8_t *__restrict__ table, const int *__restrict__ nset, int nsets, int cap,
+                                                         const int *__restrict__ slot, const int *__restrict__ idx, int nq, int quads, DivMagic dv,
+                                                         uint4 *__restrict__ out, int *__restrict__ bad) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nq * quads) return;
+    const int q = (int)afv_udiv((uint32_t)t, dv), h = t - q * quads;
+    const int s = slot[q], i = idx[q];
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (s >= 0 && s < nsets && i >= 0 && i < min(nset[s], cap)) v = reinterpret_cast<const uint4 *>(table + ((size_t)s * cap + i) * quads * 16)[h];
+    else if (h == 0 && bad) atomicOr(bad, 1);
+    out[t] = v;
+}
+
+// words: dwords per row of the table (8 or 16; a float table: float_dim, a multiple of 4)
 extern "C" void afv_launch_frame_gather(const uint8_t *table, const int *nset, int nsets, int cap, const int *slot, const int *idx, int nq,
                                         void *out, int *bad, int words, hipStream_t stream) {
     if (nq <= 0) return;
-    if (words == 16)
+    if (words != 8 && words != 16)
+        hipLaunchKernelGGL(k_frame_gather_rt, dim3((words / 4 * nq + 255) / 256), dim3(256), 0, stream, table, nset, nsets, cap, slot, idx, nq,
+                           words / 4, afv_div_magic((uint32_t)(words / 4)), reinterpret_cast<uint4 *>(out), bad);
+    else if (words == 16)
         hipLaunchKernelGGL(k_frame_gather<4>, dim3((4 * nq + 255) / 256), dim3(256), 0, stream, table, nset, nsets, cap, slot, idx, nq,
                            reinterpret_cast<uint4 *>(out), bad);
     else
@@ -373,10 +391,11 @@ extern "C" void afv_launch_featvec_build(const int *leaf, const int *nid, const 
 // ---------------- k_table_promote ----------------
 // the frame's arrays into slot `set` of the table planes (descriptors as rows of Q x 16 bytes = the frame's zero-padded rows, angle,
 // x / y / sigma2 / mvuRight, FeatureVector body, validity = 1, count): one launch instead of nine small copies
+// Q = 0: `quads` at run time (a float row: float_dim / 4)
 template <int Q>
-__global__ __launch_bounds__(256) void k_table_promote(PromoteArgs A) {
+__global__ __launch_bounds__(256) void k_table_promote(PromoteArgs A, int quads) {
     const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t < Q * A.n) A.t_desc[t] = A.f_desc[t];
+    if (t < (Q ? Q : quads) * A.n) A.t_desc[t] = A.f_desc[t];
     if (t < A.n) {
         A.t_angle[t] = A.f_angle[t];
         if (A.t_x) {
@@ -391,10 +410,11 @@ __global__ __launch_bounds__(256) void k_table_promote(PromoteArgs A) {
     if (t == 0) *A.t_n = A.n;
 }
 
-// words: dwords per descriptor row of the frame and the table (8 or 16)
+// words: dwords per descriptor row of the frame and the table (8 or 16; float rows: float_dim, a multiple of 4)
 extern "C" void afv_launch_table_promote(const void *args, int n, int cap, int words, hipStream_t stream) {
     const PromoteArgs &A = *reinterpret_cast<const PromoteArgs *>(args);
     const int work = std::max(std::max(words / 4 * n, cap), 1);
-    if (words == 16) hipLaunchKernelGGL(k_table_promote<4>, dim3((work + 255) / 256), dim3(256), 0, stream, A);
-    else hipLaunchKernelGGL(k_table_promote<2>, dim3((work + 255) / 256), dim3(256), 0, stream, A);
+    if (words != 8 && words != 16) hipLaunchKernelGGL(k_table_promote<0>, dim3((work + 255) / 256), dim3(256), 0, stream, A, words / 4);
+    else if (words == 16) hipLaunchKernelGGL(k_table_promote<4>, dim3((work + 255) / 256), dim3(256), 0, stream, A, 4);
+    else hipLaunchKernelGGL(k_table_promote<2>, dim3((work + 255) / 256), dim3(256), 0, stream, A, 2);
 }

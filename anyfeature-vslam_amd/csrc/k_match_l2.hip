@@ -108,6 +108,75 @@ __global__ __launch_bounds__(L2T) void k_l2_topk_pairs(const float *__restrict__
                       keys + (size_t)blockIdx.y * cap * L2K, blockIdx.x, 0);
 }
 
+// Table form for rows that do not fit in a lane's registers next to the accumulators (256 floats), and for every dimension that is a
+// multiple of 4 at run time (DIM = 0: SURF-like 36, 200 ...).  The summation order is part of the result, so the dimension is cut into
+// parts of L2_PART_Q float4s and the running DOUBLE of every (row, column) is carried from one part to the next: a lane holds one part of
+// its row in registers, walks its wave's columns of the staged chunk, and parks the partial sums in LDS (a slot per wave, column and lane:
+// written and read back by the same lane, so no barrier) until the last part narrows them to float.  The chunk shrinks with the dimension
+// so that the staged columns stay within L2_STAGE_FLOATS.
+#define L2_PART_Q 32
+#define L2_STAGE_FLOATS (L2_CHUNK * 256)
+template <int DIM>
+__global__ __launch_bounds__(L2T) void k_l2_topk_pairs_split(const float *__restrict__ desc, const int *__restrict__ nset, int cap, int dim_rt,
+                                                             const int *__restrict__ pa, const int *__restrict__ pb, int pair_base,
+                                                             unsigned long long *__restrict__ keys) {
+    static_assert(DIM % (4 * L2_PART_Q) == 0 && DIM * L2_CHUNK <= L2_STAGE_FLOATS, "whole parts, and a full chunk of columns fits the stage");
+    __shared__ float4 s_col[L2_STAGE_FLOATS / 4];
+    __shared__ double s_part[L2T / 64][L2_CHUNK / (L2T / 64)][64];
+    __shared__ unsigned long long s_keys[L2T / 64][64][L2K];
+    const int dim = DIM ? DIM : dim_rt, nq = dim >> 2;
+    const int chunk = DIM ? L2_CHUNK : min(L2_CHUNK, (L2_STAGE_FLOATS / dim) & ~(L2T / 64 - 1));  // >= 8 columns at 1024 floats
+    const int p = pair_base + blockIdx.y, sa = pa[p], sb = pb[p];
+    const int n1 = min(nset[sa], cap), n2 = min(nset[sb], cap);
+    if ((int)blockIdx.x * 64 >= n1) return;  // uniform
+    const float *d1 = desc + (size_t)sa * cap * dim, *d2 = desc + (size_t)sb * cap * dim;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int row = blockIdx.x * 64 + lane;
+    const float4 *ap = reinterpret_cast<const float4 *>(d1 + (size_t)min(row, n1 - 1) * dim);
+    unsigned long long k[L2K] = {L2_NO_KEY, L2_NO_KEY, L2_NO_KEY, L2_NO_KEY};
+    for (int cb = 0; cb < n2; cb += chunk) {
+        const int nc = min(chunk, n2 - cb);
+        __syncthreads();
+        const float4 *src = reinterpret_cast<const float4 *>(d2 + (size_t)cb * dim);
+        for (int i = tid; i < nc * nq; i += L2T) s_col[i] = src[i];
+        __syncthreads();
+        for (int q0 = 0; q0 < nq; q0 += L2_PART_Q) {
+            const int nqp = DIM ? L2_PART_Q : min(L2_PART_Q, nq - q0);  // uniform
+            const bool last = q0 + L2_PART_Q >= nq;
+            float4 a[L2_PART_Q];
+#pragma unroll
+            for (int i = 0; i < L2_PART_Q; ++i)
+                if (DIM || i < nqp) a[i] = ap[q0 + i];
+            for (int c = wv, j = 0; c < nc; c += L2T / 64, ++j) {
+                double s = q0 ? s_part[wv][j][lane] : 0.0;
+                const float4 *bp = s_col + c * nq + q0;
+#pragma unroll
+                for (int i = 0; i < L2_PART_Q; ++i) {
+                    if (DIM || i < nqp) {
+                        const float4 b = bp[i];
+                        const double v0 = (double)(a[i].x - b.x), v1 = (double)(a[i].y - b.y), v2 = (double)(a[i].z - b.z),
+                                     v3 = (double)(a[i].w - b.w);
+                        s += v0 * v0 + v1 * v1 + v2 * v2 + v3 * v3;
+                    }
+                }
+                if (last) l2_insert(k, ((unsigned long long)__float_as_uint((float)s) << 32) | (unsigned)(cb + c));
+                else s_part[wv][j][lane] = s;
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < L2K; ++s) s_keys[wv][lane][s] = k[s];
+    __syncthreads();
+    if (wv == 0 && row < n1) {
+#pragma unroll
+        for (int w = 1; w < L2T / 64; ++w)
+#pragma unroll
+            for (int s = 0; s < L2K; ++s) l2_insert(k, s_keys[w][lane][s]);
+#pragma unroll
+        for (int s = 0; s < L2K; ++s) keys[((size_t)blockIdx.y * cap + row) * L2K + s] = k[s];
+    }
+}
+
 // one wave per row: fold the column tiles' keys into the row's 4 best (written over the row's first slot)
 __global__ __launch_bounds__(L2T) void k_l2_merge(int n1, int ntiles, unsigned long long *__restrict__ keys) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * (L2T / 64) + (threadIdx.x >> 6);
@@ -150,11 +219,25 @@ __device__ __forceinline__ float l2_exact(const float *a, const float *b, int di
     return (float)s;
 }
 
+// FeatureMatcher.cc:1587-1599, rotFactor = 1/30 (:1579-1585): the bin rule of k_match.hip
+__device__ __forceinline__ int l2_rotation_bin(float a1, float a2) {
+    const float rot_factor = 1.0f / 30.0f;
+    float rot = a1 - a2;
+    if (rot < 0.0f) rot += 360.0f;
+    int bin = (int)roundf(rot * rot_factor);
+    if (bin == 30) bin = 0;
+    return bin;
+}
+
+// ORI: the rotation histogram of SearchByBoW (FeatureMatcher.cc:578, 638, 657) over ang1[row] / ang2[column].  It never influences the greedy
+// walk (a removed match leaves its column taken), so the whole workgroup builds it after the walk, as k_match_resolve does.
+template <bool ORI>
 __device__ __forceinline__ void l2_resolve_body(const float *__restrict__ d1, int n1, const float *__restrict__ d2, int n2,
                                                 int dim, const uint8_t *__restrict__ valid1,
                                                 const uint8_t *__restrict__ valid2, float th, float ratio, int ntiles,
                                                 const unsigned long long *__restrict__ keys, int *__restrict__ out,
-                                                int *__restrict__ nmatches) {
+                                                int *__restrict__ nmatches, const float *__restrict__ ang1 = nullptr,
+                                                const float *__restrict__ ang2 = nullptr) {
     __shared__ uint32_t s_matched[L2_MAX_SIDE / 32];
     __shared__ int s_claim[L2_MAX_SIDE];
     __shared__ int s_nvalid2;
@@ -170,10 +253,10 @@ __device__ __forceinline__ void l2_resolve_body(const float *__restrict__ d1, in
     for (int row = tid; row < n1; row += L2T) out[row] = -1;
     __threadfence_block();
     __syncthreads();
-    if (wv != 0) return;
+    if (!ORI && wv != 0) return;
     const bool lists_complete = s_nvalid2 <= L2K;
     int nm = 0, pos = 0;
-    while (pos < n1) {
+    while (wv == 0 && pos < n1) {
         const int q = pos + lane;
         const bool act = q < n1 && (!valid1 || valid1[q]);
         unsigned long long k[L2K] = {L2_NO_KEY, L2_NO_KEY, L2_NO_KEY, L2_NO_KEY};
@@ -280,26 +363,66 @@ __device__ __forceinline__ void l2_resolve_body(const float *__restrict__ d1, in
             pos += stop;
         }
     }
-    if (lane == 0) *nmatches = nm;
+    if constexpr (!ORI) {
+        if (lane == 0) *nmatches = nm;
+    } else {
+        __shared__ int s_hist[32], s_keep[3], s_nm;
+        if (tid < 32) s_hist[tid] = 0;
+        if (tid == 0) s_nm = nm;  // (wave 0 walked)
+        __threadfence_block();  // the walk's out[] stores, read below by the other waves
+        __syncthreads();
+        for (int i = tid; i < n1; i += L2T) {
+            const int c = out[i];
+            if (c >= 0) atomicAdd(&s_hist[l2_rotation_bin(ang1[i], ang2[c])], 1);
+        }
+        __syncthreads();
+        if (tid == 0) {  // computeThreeMaxima (FeatureMatcher.cc:1631-1668)
+            int i1 = -1, i2 = -1, i3 = -1, max1 = 0, max2 = 0, max3 = 0;
+            for (int i = 0; i < 30; ++i) {
+                const int sz = s_hist[i];
+                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
+                else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
+                else if (sz > max3) { max3 = sz; i3 = i; }
+            }
+            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+            s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3;
+        }
+        __syncthreads();
+        const int i1 = s_keep[0], i2 = s_keep[1], i3 = s_keep[2];
+        int dropped = 0;
+        for (int i = tid; i < n1; i += L2T) {  // the rows a thread visited above: its own out[] entries
+            const int c = out[i];
+            if (c >= 0) {
+                const int bin = l2_rotation_bin(ang1[i], ang2[c]);
+                if (bin != i1 && bin != i2 && bin != i3) { out[i] = -1; ++dropped; }
+            }
+        }
+        if (dropped) atomicSub(&s_nm, dropped);
+        __syncthreads();
+        if (tid == 0) *nmatches = s_nm;
+    }
 }
 __global__ __launch_bounds__(L2T) void k_l2_resolve(const float *__restrict__ d1, int n1, const float *__restrict__ d2, int n2,
                                                     int dim, const uint8_t *__restrict__ valid1,
                                                     const uint8_t *__restrict__ valid2, float th, float ratio, int ntiles,
                                                     unsigned long long *__restrict__ keys, int *__restrict__ out,
                                                     int *__restrict__ nmatches) {
-    l2_resolve_body(d1, n1, d2, n2, dim, valid1, valid2, th, ratio, ntiles, keys, out, nmatches);
+    l2_resolve_body<false>(d1, n1, d2, n2, dim, valid1, valid2, th, ratio, ntiles, keys, out, nmatches);
 }
-// one workgroup per pair; out[pair][cap] (rows >= n1 of a pair are set to -1 as well)
+// one workgroup per pair; out[pair][cap] (rows >= n1 of a pair are set to -1 as well); ORI: ang[set][cap] in degrees
+template <bool ORI>
 __global__ __launch_bounds__(L2T) void k_l2_resolve_pairs(const float *__restrict__ desc, const int *__restrict__ nset, int cap, int dim,
                                                           const int *__restrict__ pa, const int *__restrict__ pb, int pair_base, float th,
                                                           float ratio, const unsigned long long *__restrict__ keys, int *__restrict__ out,
-                                                          int *__restrict__ nmatches) {
+                                                          int *__restrict__ nmatches, const float *__restrict__ ang) {
     const int p = pair_base + blockIdx.x, sa = pa[p], sb = pb[p];
     const int n1 = min(nset[sa], cap), n2 = min(nset[sb], cap);
     int *o = out + (size_t)p * cap;
     for (int row = n1 + (int)threadIdx.x; row < cap; row += L2T) o[row] = -1;
-    l2_resolve_body(desc + (size_t)sa * cap * dim, n1, desc + (size_t)sb * cap * dim, n2, dim, nullptr, nullptr, th, ratio, 1,
-                    keys + (size_t)blockIdx.x * cap * L2K, o, nmatches + p);
+    l2_resolve_body<ORI>(desc + (size_t)sa * cap * dim, n1, desc + (size_t)sb * cap * dim, n2, dim, nullptr, nullptr, th, ratio, 1,
+                         keys + (size_t)blockIdx.x * cap * L2K, o, nmatches + p, ORI ? ang + (size_t)sa * cap : nullptr,
+                         ORI ? ang + (size_t)sb * cap : nullptr);
 }
 
 extern "C" size_t afv_match_l2_scratch_bytes(int n1, int n2, int *ntiles_out, int *cols_per_tile_out) {
@@ -333,16 +456,24 @@ extern "C" int afv_launch_match_l2_tiled(const float *d1, int n1, const float *d
     return 1;
 }
 
-// batch over a device-resident table (dim 64 / 128, cap <= L2_MAX_SIDE): pairs [pair_base, pair_base + npairs); `scratch` holds
-// npairs * cap * L2K keys.  Returns 0 if the shape is not supported.
+// batch over a device-resident table (cap <= L2_MAX_SIDE): pairs [pair_base, pair_base + npairs); `scratch` holds npairs * cap * L2K keys.
+// dim 64 / 128: the row in registers; 256 and every other multiple of 4 up to 1024: the split form.  ang != null: the rotation histogram
+// over ang[set][cap].  Returns 0 if the shape is not supported.
 extern "C" int afv_launch_match_l2_pairs(const float *desc, const int *nset, int cap, int dim, const int *pa, const int *pb, int npairs,
-                                         int pair_base, float th, float ratio, int *out, int *nmatches, void *scratch, hipStream_t stream) {
-    if ((dim != 64 && dim != 128) || cap < 1 || cap > L2_MAX_SIDE || npairs < 1) return 0;
+                                         int pair_base, float th, float ratio, const float *ang, int *out, int *nmatches, void *scratch,
+                                         hipStream_t stream) {
+    if (dim < 4 || dim > 1024 || (dim & 3) || cap < 1 || cap > L2_MAX_SIDE || npairs < 1) return 0;
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(scratch);
     const dim3 grid((cap + 63) / 64, npairs);
     if (dim == 128) hipLaunchKernelGGL(k_l2_topk_pairs<128>, grid, dim3(L2T), 0, stream, desc, nset, cap, pa, pb, pair_base, keys);
-    else hipLaunchKernelGGL(k_l2_topk_pairs<64>, grid, dim3(L2T), 0, stream, desc, nset, cap, pa, pb, pair_base, keys);
-    hipLaunchKernelGGL(k_l2_resolve_pairs, dim3(npairs), dim3(L2T), 0, stream, desc, nset, cap, dim, pa, pb, pair_base, th, ratio, keys, out,
-                       nmatches);
+    else if (dim == 64) hipLaunchKernelGGL(k_l2_topk_pairs<64>, grid, dim3(L2T), 0, stream, desc, nset, cap, pa, pb, pair_base, keys);
+    else if (dim == 256) hipLaunchKernelGGL(k_l2_topk_pairs_split<256>, grid, dim3(L2T), 0, stream, desc, nset, cap, dim, pa, pb, pair_base, keys);
+    else hipLaunchKernelGGL(k_l2_topk_pairs_split<0>, grid, dim3(L2T), 0, stream, desc, nset, cap, dim, pa, pb, pair_base, keys);
+    if (ang)
+        hipLaunchKernelGGL(k_l2_resolve_pairs<true>, dim3(npairs), dim3(L2T), 0, stream, desc, nset, cap, dim, pa, pb, pair_base, th, ratio, keys,
+                           out, nmatches, ang);
+    else
+        hipLaunchKernelGGL(k_l2_resolve_pairs<false>, dim3(npairs), dim3(L2T), 0, stream, desc, nset, cap, dim, pa, pb, pair_base, th, ratio, keys,
+                           out, nmatches, ang);
     return 1;
 }

@@ -70,11 +70,28 @@ def shard_range(n_units, rank, world):
 
 class DescriptorTable:
     """`desc_bytes`: width of the binary rows, 1 .. 64 (32 = ORB32, 61 = AKAZE61, 48 = BRISK48 ...).  The device keeps them zero-padded to
-    `pitch` = 32 (up to 32 bytes) or 64 bytes; host arrays in and out are `desc_bytes` wide."""
+    `pitch` = 32 (up to 32 bytes) or 64 bytes; host arrays in and out are `desc_bytes` wide.
+    `float_dim` (instead of `desc_bytes`): a table of float rows (128 = SIFT128, 64 = SURF64 / KAZE64 ...), a multiple of 4 from 4 to 1024;
+    host arrays and the device view are float32 of shape (n, float_dim), `desc_bytes` = `pitch` = 4 * float_dim, distances are L2^2."""
 
-    def __init__(self, ctx, nsets, cap, desc_bytes=32):
+    def __init__(self, ctx, nsets, cap, desc_bytes=None, float_dim=None):
         self.ctx, self.lib = ctx, ctx.lib
         self.nsets, self.cap = int(nsets), int(cap)
+        if desc_bytes is not None and float_dim is not None:
+            raise ValueError("desc_bytes and float_dim exclude each other: a table holds binary rows or float rows")
+        self.float_dim = 0
+        if float_dim is not None:
+            if (isinstance(float_dim, bool) or not isinstance(float_dim, (int, np.integer)) or not 4 <= int(float_dim) <= 1024
+                    or int(float_dim) % 4):
+                raise ValueError("float_dim must be a multiple of 4 in 4..1024, got %r" % (float_dim,))
+            self.float_dim = int(float_dim)
+            self.desc_bytes = self.pitch = 4 * self.float_dim
+            h = C.c_void_p()
+            ctx.check(self.lib.afv_table_create_f32(ctx.handle, self.nsets, self.cap, self.float_dim, C.byref(h)), "afv_table_create_f32")
+            self.handle = h
+            return
+        if desc_bytes is None:
+            desc_bytes = 32
         if isinstance(desc_bytes, bool) or not isinstance(desc_bytes, (int, np.integer)) or not 1 <= int(desc_bytes) <= 64:
             raise ValueError("desc_bytes must be an integer in 1..64, got %r" % (desc_bytes,))
         self.desc_bytes = int(desc_bytes)
@@ -87,8 +104,13 @@ class DescriptorTable:
         self.handle = h
 
     def _rows(self, desc, what):
-        """host rows as a contiguous (n, desc_bytes) uint8 array; a row of another width raises before any library call"""
+        """host rows as a contiguous (n, desc_bytes) uint8 array - (n, float_dim) float32 for a float table; a row of another width or
+        kind raises before any library call"""
         a = np.asarray(desc)
+        if self.float_dim:
+            if a.ndim != 2 or a.shape[1] != self.float_dim or a.dtype != np.float32:
+                raise ValueError("%s: rows must be (n, %d) float32 for this table, got shape %s %s" % (what, self.float_dim, a.shape, a.dtype))
+            return np.ascontiguousarray(a)
         if a.ndim != 2 or a.shape[1] != self.desc_bytes:
             raise ValueError("%s: rows must be (n, %d) uint8 for this table, got shape %s" % (what, self.desc_bytes, a.shape))
         return np.ascontiguousarray(a, np.uint8)
@@ -106,7 +128,7 @@ class DescriptorTable:
 
     # ---- filling ----
     def set(self, slot, desc, angles=None):
-        if self.desc_bytes == 32:
+        if self.desc_bytes == 32 and not self.float_dim:
             desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         else:
             desc = self._rows(desc, "DescriptorTable.set")
@@ -133,7 +155,7 @@ class DescriptorTable:
 
     def device_views(self):
         """zero-copy torch views of the table: desc uint8 [nsets, cap, pitch] (rows zero-padded from desc_bytes), angle float32
-        [nsets, cap], n int32 [nsets]"""
+        [nsets, cap], n int32 [nsets]; a float table: desc float32 [nsets, cap, float_dim]"""
         import torch
         d, a, n = C.c_void_p(), C.c_void_p(), C.c_void_p()
         self.ctx.check(self.lib.afv_table_device_ptrs(self.handle, C.byref(d), C.byref(a), C.byref(n)))
@@ -146,14 +168,20 @@ class DescriptorTable:
             typestr = {torch.uint8: "|u1", torch.float32: "<f4", torch.int32: "<i4"}[dtype]
             h.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (p.value, False), "version": 2}
             return torch.as_tensor(h, device=dev)
-        return (view(d, self.nsets * self.cap * self.pitch, torch.uint8, (self.nsets, self.cap, self.pitch)),
+        return (view(d, self.nsets * self.cap * self.pitch, torch.float32, (self.nsets, self.cap, self.float_dim)) if self.float_dim else
+                view(d, self.nsets * self.cap * self.pitch, torch.uint8, (self.nsets, self.cap, self.pitch)),
                 view(a, self.nsets * self.cap * 4, torch.float32, (self.nsets, self.cap)),
                 view(n, self.nsets * 4, torch.int32, (self.nsets,)))
 
     def upload(self, table, angles, counts):
         """fill every slot from host arrays [nsets, cap, desc_bytes] / [nsets, cap] / [nsets]: three bulk copies through the
         zero-copy views when torch can wrap the pointers, else one afv_table_set per slot"""
-        if self.desc_bytes != 32:
+        if self.float_dim:
+            t_dev = np.asarray(table)
+            if t_dev.shape != (self.nsets, self.cap, self.float_dim) or t_dev.dtype != np.float32:
+                raise ValueError("DescriptorTable.upload: table must be (%d, %d, %d) float32, got shape %s %s"
+                                 % (self.nsets, self.cap, self.float_dim, t_dev.shape, t_dev.dtype))
+        elif self.desc_bytes != 32:
             t = np.asarray(table)
             if t.shape != (self.nsets, self.cap, self.desc_bytes):
                 raise ValueError("DescriptorTable.upload: table must be (%d, %d, %d) uint8, got shape %s" % (self.nsets, self.cap, self.desc_bytes, t.shape))
@@ -168,7 +196,7 @@ class DescriptorTable:
         try:
             import torch
             d, a, n = self.device_views()
-            d.copy_(torch.from_numpy(np.ascontiguousarray(t_dev, np.uint8)))
+            d.copy_(torch.from_numpy(np.ascontiguousarray(t_dev, np.float32 if self.float_dim else np.uint8)))
             a.copy_(torch.from_numpy(np.ascontiguousarray(angles, np.float32)))
             n.copy_(torch.from_numpy(np.ascontiguousarray(counts, np.int32)))
             torch.cuda.synchronize(d.device)
@@ -234,7 +262,7 @@ class DescriptorTable:
         the keyframes in `slots`.  Returns match_f[nslots, frame.N] (keyframe feature per frame feature, -1 = none) and nmatches[nslots]"""
         from ._lib import FrameView
         sl = _i32(slots)
-        if self.desc_bytes == 32:
+        if self.desc_bytes == 32 and not self.float_dim:
             desc = np.ascontiguousarray(frame.descriptors, np.uint8).reshape(-1, 32)
         else:
             desc = self._rows(frame.descriptors, "DescriptorTable.match_bow_frame")

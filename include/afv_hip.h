@@ -49,7 +49,8 @@ enum {
  * another revision must not call into the library (check once: afv_abi_version() == AFV_ABI_VERSION).
  *   5  (round 5) afv_proj_job / afv_tri_job / afv_table_tri_job start with struct_size; frame grids hold at most 8192 cells (was 65536)
  *   6  (round 6) afv_orb_detect / afv_orb_compute; afv_frame_params.desc_bytes; afv_vocab_create_f32 / afv_bow_transform_f32; afv_proj_job.float_dim; grids / frames whose one-workgroup build does not fit the
- *      LDS are refused with AFV_EUNSUPPORTED at creation instead of failing at the first launch */
+ *      LDS are refused with AFV_EUNSUPPORTED at creation instead of failing at the first launch
+ *      (still 6: afv_table_create_bytes, then afv_table_create_f32 were added as exports; no record changed) */
 #define AFV_ABI_VERSION 6
 int afv_abi_version(void);
 
@@ -207,10 +208,20 @@ int afv_table_create(afv_ctx *ctx, int nsets, int cap /* <= 4096 */, afv_table *
 /* a table of binary rows of desc_bytes = 1 .. 64 bytes (61 AKAZE, 48 BRISK, 64 FREAK ...), stored zero-padded to a pitch of 32 bytes
  * (desc_bytes <= 32) or 64 bytes (33 .. 64), the rule of resident frames.  Every afv_table_* entry point works at that width with the
  * reference's rules unchanged; a frame meets the table only when it is binary with the same desc_bytes (else AFV_EUNSUPPORTED).
- * afv_table_create(ctx, nsets, cap, out) is afv_table_create_bytes(ctx, nsets, cap, 32, out).  Float rows stay out of the table. */
+ * afv_table_create(ctx, nsets, cap, out) is afv_table_create_bytes(ctx, nsets, cap, 32, out). */
 int afv_table_create_bytes(afv_ctx *ctx, int nsets, int cap /* <= 4096 */, int desc_bytes, afv_table **out);
+/* a table of FLOAT rows (SIFT128, SURF64, KAZE64, R2D2-128 ...): float_dim floats per row, a multiple of 4 from 4 to 1024 (the rule of
+ * afv_frame_params.float_dim; anything else is AFV_EINVAL), pitch 4 * float_dim bytes, no padding.  Every afv_table_* entry point works on
+ * it with the conventions of a float frame: afv_table_set takes n x float_dim floats behind its uint8_t pointer, afv_frame_view.desc32 of
+ * afv_table_match_bow_frame points to n x float_dim floats, afv_table_device_ptrs gives d_desc[nsets][cap][float_dim] floats.  The
+ * distance is L2^2 as cv::norm(a, b, NORM_L2SQR) evaluates it (Feature_sift128.cpp:132-134); th_low / nnratio apply to it as it stands.
+ * A frame meets the table only when it is a float frame of the same float_dim; a binary frame against a float table, a float frame
+ * against a binary table or a float table of another float_dim, and afv_table_clone / afv_table_broadcast between tables of different
+ * kind or float_dim answer AFV_EUNSUPPORTED before any data moves. */
+int afv_table_create_f32(afv_ctx *ctx, int nsets, int cap /* <= 4096 */, int float_dim, afv_table **out);
 void afv_table_destroy(afv_table *t);
-/* upload keyframe `set`: n x desc_bytes descriptors (packed; 32 for afv_table_create), angles[n] in degrees (NULL = zeros).
+/* upload keyframe `set`: n x desc_bytes descriptors (packed; 32 for afv_table_create; a float table: n x float_dim floats), angles[n] in
+ * degrees (NULL = zeros).
  * The library writes the rows' padding (zero).  Host pointers; synchronous. */
 int afv_table_set(afv_table *t, int set, const uint8_t *desc32, const float *angles, int n);
 /* the keyframe's FeatureVector as CSR over ascending node ids (as in afv_match_job); needed by afv_table_match_bow only.
@@ -223,7 +234,7 @@ int afv_table_set_featvec(afv_table *t, int set, const int32_t *node_id, const i
  * default).  The brute-force pair entry points take every feature as valid. */
 int afv_table_set_valid(afv_table *t, int set, const uint8_t *valid);
 /* device views for zero-copy callers: d_desc[nsets][cap][pitch] (pitch 32 or 64 bytes, see afv_table_create_bytes; a writer keeps the
- * padding zero), d_angle[nsets][cap] (float), d_n[nsets] (int32) */
+ * padding zero; a float table: [nsets][cap][float_dim] floats), d_angle[nsets][cap] (float), d_n[nsets] (int32) */
 int afv_table_device_ptrs(afv_table *t, uint8_t **d_desc, float **d_angle, int32_t **d_n);
 /* brute-force SearchByBoW(KF,KF) (FeatureMatcher.cc:561-660 with one node holding everything) of npairs (a, b) slot
  * pairs.  pair arrays are HOST int32; outputs are HOST arrays: match12[npairs][cap] (may be NULL: counts only) and
@@ -463,9 +474,9 @@ typedef struct {
                                          n x float_dim floats behind its uint8_t pointer, afv_frame_bow_transform wants a float vocabulary of
                                          that dimension (afv_vocab_create_f32), the projection searches and SearchForInitialization use
                                          L2^2 distances (afv_proj_job.float_dim; afv_proj_queries.qdesc = nq x float_dim floats,
-                                         desc_bytes = 4 * float_dim).  Unlike a binary frame it stays out of every keyframe
-                                         table: SearchByBoW(KF, F) on float rows is afv_match_bow with AFV_MATCH_FLOAT32 and the frame's
-                                         FeatureVector (afv_frame_get_featvec) */
+                                         desc_bytes = 4 * float_dim).  It meets a keyframe table of float rows of the same float_dim
+                                         (afv_table_create_f32) in afv_table_set_from_frame / afv_table_match_bow_frame_h / qref_table;
+                                         a binary table or another float_dim answers AFV_EUNSUPPORTED */
 } afv_frame_params;
 int afv_frame_create(afv_ctx *ctx, const afv_frame_params *params, afv_frame **out);
 void afv_frame_destroy(afv_frame *f);
@@ -513,7 +524,7 @@ typedef struct {
     /* the queries' descriptors by reference instead of by value: a map point's descriptor is a row of the keyframe that observed it
      * (MapPoint::ComputeDistinctDescriptors copies pKF->mDescriptors.row(idx)), so when that keyframe sits in an afv_table the row is
      * gathered on the device: qref_table + qref_slot[nq] + qref_idx[nq] (qdesc NULL).  8 bytes per query instead of desc_bytes.  The table's
-     * desc_bytes must be the frame's (else AFV_EUNSUPPORTED). */
+     * kind and desc_bytes / float_dim must be the frame's (else AFV_EUNSUPPORTED). */
     afv_table *qref_table; const int32_t *qref_slot; const int32_t *qref_idx;
 } afv_proj_queries;
 /* SearchByProjection(F, vpMapPoints, th) (FeatureMatcher.cc:73-154) / SearchByProjection(CurrentFrame, LastFrame, th, mono) (:1291-1402)
