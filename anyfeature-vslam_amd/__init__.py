@@ -9,6 +9,7 @@ Layout:
   extractor.py   FeatureExtractorSettings / FeatureExtractor_orb32 mirror (reference: Feature_orb32.{h,cpp})
   matcher.py     FeatureMatcher mirror (reference: FeatureMatcher.{h,cc})
   frame.py       the device-resident Frame (reference: Frame.{h,cc} as far as the front end reads it)
+  database.py    KeyFrameDatabase mirror over the keyframe table (reference: KeyFrameDatabase.{h,cc}, LoopClosing.cc:137-157)
   synth.py       bit-reproducible synthetic inputs
 """
 from . import _lib, synth  # noqa: F401
@@ -17,6 +18,7 @@ from .extractor import (CovarianceMethod, FeatureExtractorSettings, FeatureExtra
 from .vocabulary import Vocabulary  # noqa: F401
 from .frame import Frame  # noqa: F401
 from . import akaze, table  # noqa: F401
+from .database import KeyFrameDatabase  # noqa: F401
 from .akaze import AkazeContext  # noqa: F401
 from .matcher import (FeatureMatcher, FeatureView, FrameGridView, ProjectionQueries, ComputeDistinctiveDescriptors,  # noqa: F401
                       DescriptorDistance_orb32, DescriptorDistance_sift128)

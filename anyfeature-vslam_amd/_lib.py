@@ -100,6 +100,15 @@ class ProjQueries(C.Structure):
                 ("qref_table", C.c_void_p), ("qref_slot", C.c_void_p), ("qref_idx", C.c_void_p)]
 
 
+class BowQuery(C.Structure):
+    """afv_bow_query: the query BowVector of afv_table_score_bow - a table slot, a resident frame or host arrays"""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("slot", C.c_int32), ("n", C.c_int32), ("frame", C.c_void_p),
+                ("word", C.c_void_p), ("value", C.c_void_p)]
+
+
+BOW_QUERY_SLOT, BOW_QUERY_FRAME, BOW_QUERY_HOST = 0, 1, 2
+
+
 def sized(struct):
     """a job record with its struct_size filled in"""
     obj = struct()
@@ -183,6 +192,11 @@ SYMBOLS = {
     "afv_table_set_from_frame": (_i, [_vp, _i, _vp]),
     "afv_table_match_bow_frame_h": (_i, [_vp, _vp, _i, _vp, _f, _f, _i, _vp, _vp]),
     "afv_set_projection_resolve": (_i, [_vp, _i]),
+    "afv_vocab_set_weights": (_i, [_vp, _vp, _vp, _vp]),
+    "afv_bow_vector": (_i, [_vp, _vp, _vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
+    "afv_frame_get_bowvec": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "afv_table_set_bowvec": (_i, [_vp, _i, _vp, _vp, _i]),
+    "afv_table_score_bow": (_i, [_vp, C.POINTER(BowQuery), _i, _vp, _vp, _vp, _vp]),
     "afv_hamming256": (_i, [_vp, _vp]),
     # include/afv_akaze.h
     "afv_akaze_default_params": (None, [_vp]),

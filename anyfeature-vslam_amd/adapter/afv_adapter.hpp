@@ -24,9 +24,12 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <algorithm>
 #include <exception>
+#include <functional>
 #include <map>
 #include <memory>
+#include <set>
 #include <utility>
 #include <vector>
 
@@ -732,6 +735,206 @@ class VocabularyHip {
     std::vector<double> weight;
     std::vector<int32_t> word_id;
     afv_vocab *voc = nullptr;
+};
+
+// ---- KeyFrameDatabase (reference include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:40-309; LoopClosing.cc:137-157) over a keyframe
+// table that holds the keyframes' BowVectors (afv_table_set_bowvec / afv_table_set_from_frame).  Words in common and Vocabulary::score
+// of the query against every keyframe of the database come from ONE afv_table_score_bow call; the reference's float arithmetic (0.8f,
+// 0.75f, the covisibility accumulation) stays here.  The covisibility graph is the caller's: GetConnectedKeyFrames comes in as a list,
+// GetBestCovisibilityKeyFrames(10) as a function.  Keyframes are named by their table slot.  The candidate order is the reference's:
+// (smallest shared word, add sequence) = the order its inverted-file walk meets the keyframes.  KeyFrame::mRelocScore outlives a query
+// (KeyFrameDatabase.cc:273-276 reads it for neighbours this query did not score): kept per slot, 0 until first scored. ----
+class KeyFrameDatabase {
+  public:
+    using Covisibles = std::function<std::vector<int>(int)>;
+    KeyFrameDatabase(afv_ctx *ctx_, afv_table *table_, int nsets_) : ctx(ctx_), table(table_), nsets(nsets_), seq((size_t)nsets_, -1), reloc_score((size_t)nsets_, 0.0f) {}
+
+    void add(int slot) {  // :40-46
+        if (slot >= 0 && slot < nsets && seq[(size_t)slot] < 0) seq[(size_t)slot] = next++;
+    }
+    void erase(int slot) {  // :48-67
+        if (slot >= 0 && slot < nsets) seq[(size_t)slot] = -1;
+    }
+    void clear() { std::fill(seq.begin(), seq.end(), -1L); }  // :69-73
+
+    // DetectRelocalizationCandidates(Frame *F) (:199-309): the frame's resident BowVector is the query (VocabularyHip::transform(DeviceFrame &...)
+    // on a vocabulary with weights ran before), or a host BowVector
+    std::vector<int> DetectRelocalizationCandidates(DeviceFrame &F, const Covisibles &best_covisibles) {
+        afv_bow_query q{};
+        q.struct_size = sizeof(q);
+        q.kind = AFV_BOW_QUERY_FRAME;
+        q.frame = F.handle();
+        return reloc(q, best_covisibles);
+    }
+    std::vector<int> DetectRelocalizationCandidates(const BowVector &bow, const Covisibles &best_covisibles) {
+        std::vector<int32_t> w;
+        std::vector<double> v;
+        return reloc(host_query(bow, w, v), best_covisibles);
+    }
+
+    // DetectLoopCandidates(pKF, minScore) (:76-197); connected = pKF->GetConnectedKeyFrames()
+    std::vector<int> DetectLoopCandidates(int slot, float minScore, const std::vector<int> &connected, const Covisibles &best_covisibles) {
+        std::vector<uint8_t> mask = members();
+        for (int s : connected)
+            if (s >= 0 && s < nsets) mask[(size_t)s] = 0;
+        afv_bow_query q = slot_query(slot);
+        run(q, mask);
+        std::vector<int> sharing = sharing_words(mask);
+        if (sharing.empty()) return {};
+        const int minCommonWords = min_common(sharing);
+        std::vector<uint8_t> scored((size_t)nsets, 0);
+        std::vector<float> loop_score((size_t)nsets, 0.0f);
+        std::vector<std::pair<float, int>> lScoreAndMatch;
+        for (int s : sharing)
+            if (common[(size_t)s] > minCommonWords) {
+                const float si = (float)score[(size_t)s];
+                loop_score[(size_t)s] = si;
+                scored[(size_t)s] = 1;
+                if (si >= minScore) lScoreAndMatch.emplace_back(si, s);
+            }
+        if (lScoreAndMatch.empty()) return {};
+        std::vector<std::pair<float, int>> lAccScoreAndMatch;
+        float bestAccScore = minScore;
+        for (const auto &it : lScoreAndMatch) {
+            float bestScore = it.first, accScore = it.first;
+            int best = it.second;
+            for (int k2 : best_covisibles(it.second))
+                if (k2 >= 0 && k2 < nsets && scored[(size_t)k2]) {  // mnLoopQuery == this query && mnLoopWords > minCommonWords
+                    accScore += loop_score[(size_t)k2];
+                    if (loop_score[(size_t)k2] > bestScore) {
+                        best = k2;
+                        bestScore = loop_score[(size_t)k2];
+                    }
+                }
+            lAccScoreAndMatch.emplace_back(accScore, best);
+            if (accScore > bestAccScore) bestAccScore = accScore;
+        }
+        return retain(lAccScoreAndMatch, bestAccScore);
+    }
+
+    // the reference score of LoopClosing::DetectLoop (LoopClosing.cc:142-155): the lowest score to a (not bad) covisible keyframe
+    float min_score_to_connected(int slot, const std::vector<int> &connected) {
+        float minScore = 1;
+        if (connected.empty()) return minScore;
+        std::vector<uint8_t> mask((size_t)nsets, 0);
+        for (int s : connected)
+            if (s >= 0 && s < nsets) mask[(size_t)s] = 1;
+        afv_bow_query q = slot_query(slot);
+        run(q, mask);
+        for (int s : connected) {
+            if (s < 0 || s >= nsets) continue;
+            const float sc = (float)score[(size_t)s];
+            if (sc < minScore) minScore = sc;
+        }
+        return minScore;
+    }
+
+    // Vocabulary::score of the last query against every slot (doubles, as DBoW2 returns them), -1 counts for slots left out
+    const std::vector<double> &last_scores() const { return score; }
+    const std::vector<int32_t> &last_common() const { return common; }
+
+  private:
+    std::vector<uint8_t> members() const {
+        std::vector<uint8_t> mask((size_t)nsets, 0);
+        for (int s = 0; s < nsets; ++s) mask[(size_t)s] = seq[(size_t)s] >= 0;
+        return mask;
+    }
+    static afv_bow_query slot_query(int slot) {
+        afv_bow_query q{};
+        q.struct_size = sizeof(q);
+        q.kind = AFV_BOW_QUERY_SLOT;
+        q.slot = slot;
+        return q;
+    }
+    static afv_bow_query host_query(const BowVector &bow, std::vector<int32_t> &w, std::vector<double> &v) {
+        for (const auto &kv : bow) {
+            w.push_back((int32_t)kv.first);
+            v.push_back(kv.second);
+        }
+        afv_bow_query q{};
+        q.struct_size = sizeof(q);
+        q.kind = AFV_BOW_QUERY_HOST;
+        q.n = (int32_t)w.size();
+        q.word = w.data();
+        q.value = v.data();
+        return q;
+    }
+    void run(const afv_bow_query &q, const std::vector<uint8_t> &mask) {
+        common.assign((size_t)nsets, -1);
+        score.assign((size_t)nsets, 0.0);
+        first.assign((size_t)nsets, -1);
+        const int rc = afv_table_score_bow(table, &q, 1, mask.data(), common.data(), score.data(), first.data());
+        if (rc != AFV_OK) fatal("afv_table_score_bow", rc, ctx);
+    }
+    // lKFsSharingWords in the order the inverted-file walk builds it
+    std::vector<int> sharing_words(const std::vector<uint8_t> &mask) const {
+        std::vector<int> sharing;
+        for (int s = 0; s < nsets; ++s)
+            if (mask[(size_t)s] && seq[(size_t)s] >= 0 && common[(size_t)s] > 0) sharing.push_back(s);
+        std::sort(sharing.begin(), sharing.end(), [&](int a, int b) {
+            return first[(size_t)a] != first[(size_t)b] ? first[(size_t)a] < first[(size_t)b] : seq[(size_t)a] < seq[(size_t)b];
+        });
+        return sharing;
+    }
+    int min_common(const std::vector<int> &sharing) const {
+        int maxCommonWords = 0;
+        for (int s : sharing)
+            if (common[(size_t)s] > maxCommonWords) maxCommonWords = common[(size_t)s];
+        return (int)(maxCommonWords * 0.8f);  // int minCommonWords = maxCommonWords*0.8f
+    }
+    std::vector<int> reloc(const afv_bow_query &q, const Covisibles &best_covisibles) {
+        const std::vector<uint8_t> mask = members();
+        run(q, mask);
+        std::vector<int> sharing = sharing_words(mask);
+        if (sharing.empty()) return {};
+        const int minCommonWords = min_common(sharing);
+        std::vector<uint8_t> in_query((size_t)nsets, 0);
+        for (int s : sharing) in_query[(size_t)s] = 1;
+        std::vector<std::pair<float, int>> lScoreAndMatch;
+        for (int s : sharing)
+            if (common[(size_t)s] > minCommonWords) {
+                const float si = (float)score[(size_t)s];
+                reloc_score[(size_t)s] = si;
+                lScoreAndMatch.emplace_back(si, s);
+            }
+        if (lScoreAndMatch.empty()) return {};
+        std::vector<std::pair<float, int>> lAccScoreAndMatch;
+        float bestAccScore = 0;
+        for (const auto &it : lScoreAndMatch) {
+            float bestScore = it.first, accScore = bestScore;
+            int best = it.second;
+            for (int k2 : best_covisibles(it.second)) {
+                if (k2 < 0 || k2 >= nsets || !in_query[(size_t)k2]) continue;  // mnRelocQuery != F->mnId
+                accScore += reloc_score[(size_t)k2];
+                if (reloc_score[(size_t)k2] > bestScore) {
+                    best = k2;
+                    bestScore = reloc_score[(size_t)k2];
+                }
+            }
+            lAccScoreAndMatch.emplace_back(accScore, best);
+            if (accScore > bestAccScore) bestAccScore = accScore;
+        }
+        return retain(lAccScoreAndMatch, bestAccScore);
+    }
+    static std::vector<int> retain(const std::vector<std::pair<float, int>> &lAccScoreAndMatch, float bestAccScore) {
+        const float minScoreToRetain = 0.75f * bestAccScore;
+        std::set<int> spAlreadyAddedKF;
+        std::vector<int> out;
+        for (const auto &it : lAccScoreAndMatch)
+            if (it.first > minScoreToRetain && !spAlreadyAddedKF.count(it.second)) {
+                out.push_back(it.second);
+                spAlreadyAddedKF.insert(it.second);
+            }
+        return out;
+    }
+    afv_ctx *ctx;
+    afv_table *table;
+    int nsets;
+    long next = 0;
+    std::vector<long> seq;  // add sequence per slot, -1 = not in the database
+    std::vector<float> reloc_score;
+    std::vector<int32_t> common, first;
+    std::vector<double> score;
 };
 
 }  // namespace afv

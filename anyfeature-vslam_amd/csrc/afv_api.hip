@@ -2235,6 +2235,81 @@ extern "C" int afv_vocab_set_stopped(afv_ctx *c, afv_vocab *v, const uint8_t *st
     return AFV_OK;
 }
 
+// word weights: what DBoW2 transform adds to the BowVector (k_bowvec.hip)
+extern "C" int afv_vocab_set_weights(afv_ctx *c, afv_vocab *v, const double *weight, const int32_t *word_id) {
+    if (!c || !v || (weight && !word_id)) return AFV_EINVAL;
+    const int nn = v->dev.nnodes;
+    int max_word = -1;
+    if (weight) {  // a word id names one node
+        for (int i = 0; i < nn; ++i) {
+            if (word_id[i] < -1) return AFV_EINVAL;
+            max_word = std::max(max_word, word_id[i]);
+        }
+        if (max_word >= nn) return AFV_EINVAL;
+    }
+    return guarded(c, [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (void *p : {(void *)v->d_weight, (void *)v->d_word_id, (void *)v->d_word_weight})
+            if (p) (void)hipFree(p);
+        v->d_weight = v->d_word_weight = nullptr;
+        v->d_word_id = nullptr;
+        if (!weight) return AFV_OK;
+        std::vector<double> by_word((size_t)max_word + 1, 0.0);
+        std::vector<uint8_t> seen((size_t)max_word + 1, 0);
+        for (int i = 0; i < nn; ++i)
+            if (word_id[i] >= 0) {
+                if (seen[(size_t)word_id[i]]) return AFV_EINVAL;
+                seen[(size_t)word_id[i]] = 1;
+                by_word[(size_t)word_id[i]] = weight[i];
+            }
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&v->d_weight), (size_t)nn * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&v->d_word_id), (size_t)nn * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&v->d_word_weight), std::max<size_t>(by_word.size(), 1) * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(v->d_weight, weight, (size_t)nn * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(v->d_word_id, word_id, (size_t)nn * sizeof(int32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess && !by_word.empty()) e = hipMemcpy(v->d_word_weight, by_word.data(), by_word.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            for (void *p : {(void *)v->d_weight, (void *)v->d_word_id, (void *)v->d_word_weight})
+                if (p) (void)hipFree(p);
+            v->d_weight = v->d_word_weight = nullptr;
+            v->d_word_id = nullptr;
+        }
+        HIPCHK(c, e);
+        return AFV_OK;
+    });
+}
+
+extern "C" int afv_bow_vector(afv_ctx *c, const afv_vocab *v, const int32_t *leaf_node, int n, int32_t *word, double *value, int32_t *n_out) {
+    if (!c || !v || !n_out || n < 0 || n > AFV_BOW_MAX_ENTRIES || (n > 0 && (!leaf_node || !word || !value))) return AFV_EINVAL;
+    if (!v->d_weight) return AFV_EINVAL;  // afv_vocab_set_weights first
+    for (int i = 0; i < n; ++i)
+        if (leaf_node[i] < 0 || leaf_node[i] >= v->dev.nnodes) return AFV_EINVAL;
+    *n_out = 0;
+    if (n == 0) return AFV_OK;
+    return guarded(c, [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        Blob b(c);
+        const size_t leaf_off = b.put(leaf_node, (size_t)n * 4);
+        const size_t in_bytes = b.h.size();
+        const size_t n_off = b.reserve_scratch(16), word_off = b.reserve_scratch((size_t)n * 4), val_off = b.reserve_scratch((size_t)n * 8);
+        const int rc = ensure_match_buffer(c, b.h.size());
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+        afv_launch_bowvec_build(reinterpret_cast<const int *>(c->d_match + leaf_off), n, v->d_weight, v->d_word_id, v->d_word_weight,
+                                reinterpret_cast<int32_t *>(c->d_match + word_off), reinterpret_cast<double *>(c->d_match + val_off),
+                                reinterpret_cast<int *>(c->d_match + n_off), c->stream);
+        HIPCHK(c, hipGetLastError());
+        // the entries land in the arena first: the caller's arrays hold n entries, the kernel wrote at most that many
+        HIPCHK(c, b.fetch(n_out, n_off, 4, c->stream));
+        HIPCHK(c, b.fetch(word, word_off, (size_t)n * 4, c->stream));
+        HIPCHK(c, b.fetch(value, val_off, (size_t)n * 8, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        b.finish();
+        return AFV_OK;
+    });
+}
+
 extern "C" void afv_vocab_destroy(afv_ctx *c, afv_vocab *v) {
     if (!v) return;
     if (c) {
@@ -2243,6 +2318,9 @@ extern "C" void afv_vocab_destroy(afv_ctx *c, afv_vocab *v) {
     }
     if (v->d_rec) (void)hipFree(v->d_rec);
     if (v->d_stopped) (void)hipFree(v->d_stopped);
+    if (v->d_weight) (void)hipFree(v->d_weight);
+    if (v->d_word_id) (void)hipFree(v->d_word_id);
+    if (v->d_word_weight) (void)hipFree(v->d_word_weight);
     delete v;
 }
 

@@ -49,7 +49,7 @@ static std::vector<afv_comm *> g_comms;
 static void table_free(afv_table *t) {
     if (!t) return;
     if (t->c) (void)hipSetDevice(t->c->device);
-    void *ptrs[] = {t->d_desc, t->d_angle, t->d_n, t->d_idx, t->d_geo, t->d_valid, t->d_pairs, t->d_out, t->d_nm};
+    void *ptrs[] = {t->d_desc, t->d_angle, t->d_n, t->d_idx, t->d_geo, t->d_valid, t->d_pairs, t->d_out, t->d_nm, t->d_bow_word, t->d_bow_value, t->d_bow_n};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (t->h_pin) (void)hipHostFree(t->h_pin);
@@ -91,6 +91,8 @@ static int table_create(afv_ctx *c, int nsets, int cap, int desc_bytes, afv_tabl
         t->fv.resize((size_t)nsets);
         t->has_fv.assign((size_t)nsets, 0);
         t->has_geo.assign((size_t)nsets, 0);
+        t->h_bow_n.assign((size_t)nsets, 0);
+        t->has_bow.assign((size_t)nsets, 0);
         t->fv_body_on_device.assign((size_t)nsets, 0);
         std::lock_guard<std::mutex> g(g_reg_mutex);
         g_tables.push_back(t);
@@ -154,6 +156,9 @@ extern "C" int afv_table_set(afv_table *t, int set, const uint8_t *desc32, const
     t->has_fv[set] = 0;
     t->fv_body_on_device[set] = 0;
     t->has_geo[set] = 0;
+    t->has_bow[set] = 0;
+    t->h_bow_n[set] = 0;
+    if (t->d_bow_n) HIPCHK(c, hipMemsetAsync(t->d_bow_n + set, 0, sizeof(int32_t), c->stream));
     if (t->d_valid) HIPCHK(c, hipMemsetAsync(t->d_valid + (size_t)set * t->cap, 1, (size_t)t->cap, c->stream));
     HIPCHK(c, hipMemcpyAsync(t->d_n + set, &t->h_n[set], sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -237,6 +242,47 @@ extern "C" int afv_table_set_valid(afv_table *t, int set, const uint8_t *valid) 
     return AFV_OK;
 }
 
+// BowVector planes: allocated together on first use, counts zero
+static int table_ensure_bow(afv_table *t) {
+    if (t->d_bow_word) return AFV_OK;
+    afv_ctx *c = t->c;
+    const size_t plane = (size_t)t->nsets * t->cap;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->d_bow_word), plane * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_bow_value), plane * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&t->d_bow_n), (size_t)t->nsets * sizeof(int32_t));
+    if (e == hipSuccess) e = afv_fill(c, t->d_bow_n, 0, (size_t)t->nsets * sizeof(int32_t));
+    if (e != hipSuccess) {
+        for (void *p : {(void *)t->d_bow_word, (void *)t->d_bow_value, (void *)t->d_bow_n})
+            if (p) (void)hipFree(p);
+        t->d_bow_word = t->d_bow_n = nullptr;
+        t->d_bow_value = nullptr;
+    }
+    HIPCHK(c, e);
+    return AFV_OK;
+}
+
+extern "C" int afv_table_set_bowvec(afv_table *t, int set, const int32_t *word, const double *value, int n) {
+    if (!t || set < 0 || set >= t->nsets || n < 0 || n > t->cap || (n > 0 && (!word || !value))) return AFV_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (word[i] < 0 || (i > 0 && word[i] <= word[i - 1])) return AFV_EINVAL;  // ascending and unique: what the score kernel searches
+    afv_ctx *c = t->c;
+    return guarded(c, [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        const int rc = table_ensure_bow(t);
+        if (rc) return rc;
+        const int32_t n32 = n;
+        if (n) {
+            HIPCHK(c, hipMemcpyAsync(t->d_bow_word + (size_t)set * t->cap, word, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(t->d_bow_value + (size_t)set * t->cap, value, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        }
+        HIPCHK(c, hipMemcpyAsync(t->d_bow_n + set, &n32, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // the sources were pageable
+        t->h_bow_n[set] = n;
+        t->has_bow[set] = 1;
+        return AFV_OK;
+    });
+}
+
 extern "C" int afv_table_device_ptrs(afv_table *t, uint8_t **d_desc, float **d_angle, int32_t **d_n) {
     if (!t) return AFV_EINVAL;
     if (d_desc) *d_desc = t->d_desc;
@@ -269,8 +315,8 @@ extern "C" int afv_table_sync_counts(afv_table *t) {  // after a broadcast / ext
 }
 
 // ---- replica image: everything a replica needs besides the device planes (host-side FeatureVector structure + per-set flags).
-// Layout (int32): [nsets] then per set {has_fv, has_geo, nnodes, node_id[nnodes], seg_ptr[nnodes + 1] (absent when nnodes == 0)}.
-// The feature indices themselves travel with the d_idx plane. ----
+// Layout (int32): [nsets] then per set {has_fv, has_geo, has_bow, bow_n, nnodes, node_id[nnodes], seg_ptr[nnodes + 1] (absent when nnodes == 0)}.
+// The feature indices themselves travel with the d_idx plane, the BowVector entries with the BowVector planes. ----
 static void table_pack_meta(const afv_table *t, std::vector<int32_t> &blob) {
     blob.clear();
     blob.push_back(t->nsets);
@@ -278,6 +324,8 @@ static void table_pack_meta(const afv_table *t, std::vector<int32_t> &blob) {
         const HostFeatVec &f = t->fv[s];
         blob.push_back(t->has_fv[s]);
         blob.push_back(t->has_geo[s]);
+        blob.push_back(t->has_bow[s]);
+        blob.push_back(t->h_bow_n[s]);
         blob.push_back((int32_t)f.node_id.size());
         blob.insert(blob.end(), f.node_id.begin(), f.node_id.end());
         blob.insert(blob.end(), f.seg_ptr.begin(), f.seg_ptr.end());
@@ -291,9 +339,10 @@ static int table_unpack_meta(afv_table *t, const int32_t *blob, size_t len) {
     size_t pos = 1;
     std::vector<int32_t> idx_row((size_t)t->cap);
     for (int s = 0; s < t->nsets; ++s) {
-        if (pos + 3 > len) return AFV_EINVAL;
-        const int has_fv = blob[pos], has_geo = blob[pos + 1], nnodes = blob[pos + 2];
-        pos += 3;
+        if (pos + 5 > len) return AFV_EINVAL;
+        const int has_fv = blob[pos], has_geo = blob[pos + 1], has_bow = blob[pos + 2], bow_n = blob[pos + 3], nnodes = blob[pos + 4];
+        pos += 5;
+        if (bow_n < 0 || bow_n > t->cap || ((has_bow || bow_n) && !t->d_bow_word)) return AFV_EINVAL;
         if (nnodes < 0 || pos + (size_t)nnodes + (nnodes ? (size_t)nnodes + 1 : 0) > len) return AFV_EINVAL;
         HostFeatVec f;
         f.node_id.assign(blob + pos, blob + pos + nnodes);
@@ -314,6 +363,8 @@ static int table_unpack_meta(afv_table *t, const int32_t *blob, size_t len) {
         t->fv_body_on_device[s] = 0;
         t->has_fv[s] = has_fv != 0;
         t->has_geo[s] = has_geo != 0;
+        t->has_bow[s] = has_bow != 0;
+        t->h_bow_n[s] = bow_n;
     }
     return pos == len ? AFV_OK : AFV_EINVAL;
 }
@@ -332,6 +383,15 @@ extern "C" int afv_table_clone(const afv_table *src, afv_table *dst) {
         if (src->d_idx && !dst->d_idx) HIPCHK(c, hipMalloc(&dst->d_idx, plane * sizeof(int32_t)));
         if (src->d_geo && !dst->d_geo) HIPCHK(c, hipMalloc(&dst->d_geo, 4 * plane * sizeof(float)));
         if (src->d_valid && !dst->d_valid) HIPCHK(c, hipMalloc(&dst->d_valid, plane));
+        if (src->d_bow_word) {
+            const int rcb = table_ensure_bow(dst);
+            if (rcb) return rcb;
+            HIPCHK(c, afv_copy_dd(c, dst->d_bow_word, src->d_bow_word, plane * sizeof(int32_t)));
+            HIPCHK(c, afv_copy_dd(c, dst->d_bow_value, src->d_bow_value, plane * sizeof(double)));
+            HIPCHK(c, afv_copy_dd(c, dst->d_bow_n, src->d_bow_n, (size_t)dst->nsets * sizeof(int32_t)));
+        } else if (dst->d_bow_n) {
+            HIPCHK(c, afv_fill(c, dst->d_bow_n, 0, (size_t)dst->nsets * sizeof(int32_t)));
+        }
         HIPCHK(c, afv_copy_dd(c, dst->d_desc, src->d_desc, plane * table_pitch(dst)));
         HIPCHK(c, afv_copy_dd(c, dst->d_angle, src->d_angle, plane * sizeof(float)));
         HIPCHK(c, afv_copy_dd(c, dst->d_n, src->d_n, (size_t)dst->nsets * sizeof(int32_t)));
@@ -341,7 +401,8 @@ extern "C" int afv_table_clone(const afv_table *src, afv_table *dst) {
         else if (dst->d_valid) HIPCHK(c, afv_fill(c, dst->d_valid, 1, plane));
         for (int s = 0; s < dst->nsets; ++s) {  // nothing of the destination's previous content survives
             dst->fv[s] = HostFeatVec();
-            dst->has_fv[s] = dst->has_geo[s] = 0;
+            dst->has_fv[s] = dst->has_geo[s] = dst->has_bow[s] = 0;
+            dst->h_bow_n[s] = 0;
             dst->fv_body_on_device[s] = 0;
         }
         int rc = afv_table_sync_counts(dst);
@@ -641,6 +702,94 @@ extern "C" int afv_table_match_bow_frame_h(afv_table *t, const int32_t *slots, i
     return guarded(t->c, [&] { return table_match_bow_frame_impl(t, slots, nslots, &view, th_low, nnratio, check_orientation, match_f, nmatches, f); });
 }
 
+// Words in common and Vocabulary::score of nq query BowVectors against the slots: ONE launch of k_score_bow over (slot groups, queries).
+// What travels: the query records (host-array queries with their entries), one state byte per slot; the results come back [nq][nsets].
+static int table_score_bow_impl(afv_table *t, const afv_bow_query *caller_q, int nq, const uint8_t *slot_mask, int32_t *common, double *score,
+                                int32_t *first_common) {
+    afv_ctx *c = t->c;
+    std::vector<afv_bow_query> q;
+    if (!afv_load_jobs(caller_q, nq, sizeof(afv_bow_query), q)) return AFV_EINVAL;
+    const int nsets = t->nsets, cap = t->cap;
+    // which slots are scored: 1 = holds features and a BowVector
+    std::vector<uint8_t> state((size_t)nsets, 0);
+    for (int s = 0; s < nsets; ++s) {
+        if (slot_mask && !slot_mask[s]) continue;
+        if (t->h_n[s] <= 0) continue;
+        if (!t->has_bow[s]) {
+            if (!slot_mask) continue;  // a sweep reports the slot as absent; naming it is an error
+            c->last_error = "afv_table_score_bow: set " + std::to_string(s) + " holds features but no BowVector (afv_table_set_bowvec)";
+            return AFV_EINVAL;
+        }
+        state[(size_t)s] = 1;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    Blob b(c);
+    std::vector<DevBowQuery> dq((size_t)nq);
+    std::vector<size_t> host_word_off((size_t)nq, 0), host_val_off((size_t)nq, 0);
+    for (int i = 0; i < nq; ++i) {
+        const afv_bow_query &Q = q[(size_t)i];
+        DevBowQuery &D = dq[(size_t)i];
+        D = DevBowQuery{nullptr, nullptr, 0, 0};
+        if (Q.kind == AFV_BOW_QUERY_SLOT) {
+            if (Q.slot < 0 || Q.slot >= nsets || !t->has_bow[Q.slot]) {
+                c->last_error = "afv_table_score_bow: query slot " + std::to_string(Q.slot) + " has no BowVector";
+                return AFV_EINVAL;
+            }
+            D.word = t->d_bow_word + (size_t)Q.slot * cap;
+            D.value = t->d_bow_value + (size_t)Q.slot * cap;
+            D.n = t->h_bow_n[Q.slot];
+        } else if (Q.kind == AFV_BOW_QUERY_FRAME) {
+            if (!Q.frame || Q.frame->c != c || !Q.frame->has_bow) return AFV_EINVAL;  // afv_frame_bow_transform on a vocabulary with weights first
+            D.word = Q.frame->d_bow_word;
+            D.value = Q.frame->d_bow_value;
+            D.n = Q.frame->bow_n;
+        } else if (Q.kind == AFV_BOW_QUERY_HOST) {
+            if (Q.n < 0 || Q.n > AFV_BOW_MAX_ENTRIES || (Q.n > 0 && (!Q.word || !Q.value))) return AFV_EINVAL;
+            for (int k = 0; k < Q.n; ++k)
+                if (Q.word[k] < 0 || (k > 0 && Q.word[k] <= Q.word[k - 1])) return AFV_EINVAL;
+            host_word_off[(size_t)i] = b.put(Q.word, (size_t)Q.n * sizeof(int32_t));
+            host_val_off[(size_t)i] = b.put(Q.value, (size_t)Q.n * sizeof(double));
+            D.n = Q.n;
+        } else {
+            return AFV_EINVAL;
+        }
+    }
+    const bool any_scored = std::find(state.begin(), state.end(), (uint8_t)1) != state.end();
+    if (any_scored && !t->d_bow_word) return AFV_EINVAL;
+    const size_t state_off = b.put(state.data(), (size_t)nsets);
+    const size_t q_off = b.reserve((size_t)nq * sizeof(DevBowQuery));
+    const size_t in_bytes = b.h.size();
+    const size_t cells = (size_t)nq * nsets;
+    const size_t score_off = b.reserve_scratch(cells * sizeof(double)), common_off = b.reserve_scratch(cells * sizeof(int32_t));
+    const size_t first_off = first_common ? b.reserve_scratch(cells * sizeof(int32_t)) : 0;
+    const int rc = ensure_match_buffer(c, b.h.size());
+    if (rc) return rc;
+    for (int i = 0; i < nq; ++i)
+        if (q[(size_t)i].kind == AFV_BOW_QUERY_HOST) {
+            dq[(size_t)i].word = reinterpret_cast<const int32_t *>(c->d_match + host_word_off[(size_t)i]);
+            dq[(size_t)i].value = reinterpret_cast<const double *>(c->d_match + host_val_off[(size_t)i]);
+        }
+    std::memcpy(b.h.data() + q_off, dq.data(), (size_t)nq * sizeof(DevBowQuery));
+    HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+    afv_launch_score_bow(reinterpret_cast<const DevBowQuery *>(c->d_match + q_off), nq, t->d_bow_word, t->d_bow_value, t->d_bow_n,
+                         c->d_match + state_off, nsets, cap, reinterpret_cast<int32_t *>(c->d_match + common_off),
+                         reinterpret_cast<double *>(c->d_match + score_off),
+                         first_common ? reinterpret_cast<int32_t *>(c->d_match + first_off) : nullptr, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, b.fetch(common, common_off, cells * sizeof(int32_t), c->stream));
+    HIPCHK(c, b.fetch(score, score_off, cells * sizeof(double), c->stream));
+    if (first_common) HIPCHK(c, b.fetch(first_common, first_off, cells * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    b.finish();
+    return AFV_OK;
+}
+
+extern "C" int afv_table_score_bow(afv_table *t, const afv_bow_query *q, int nq, const uint8_t *slot_mask, int32_t *common, double *score,
+                                   int32_t *first_common) {
+    if (!t || !q || nq < 1 || nq > 65535 || !common || !score) return AFV_EINVAL;
+    return guarded(t->c, [&] { return table_score_bow_impl(t, q, nq, slot_mask, common, score, first_common); });
+}
+
 // KeyFrame::KeyFrame(Frame &F, ...) (src/KeyFrame.cc:36-60) on the device: one kernel copies the frame's arrays into the slot's rows of the
 // table planes; the FeatureVector's node structure goes host to host
 extern "C" int afv_table_set_from_frame(afv_table *t, int slot, afv_frame *f) {
@@ -683,6 +832,23 @@ extern "C" int afv_table_set_from_frame(afv_table *t, int slot, afv_frame *f) {
             t->has_fv[slot] = 1;
         }
         t->has_geo[slot] = 1;
+        // the BowVector comes along like the FeatureVector (a frame without one leaves the slot without one)
+        t->has_bow[slot] = 0;
+        t->h_bow_n[slot] = 0;
+        if (f->has_bow) {
+            const int rcb = table_ensure_bow(t);
+            if (rcb) return rcb;
+            if (f->bow_n > t->cap) return AFV_ECAPACITY;
+            if (f->bow_n) {
+                HIPCHK(c, hipMemcpyAsync(t->d_bow_word + (size_t)slot * t->cap, f->d_bow_word, (size_t)f->bow_n * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+                HIPCHK(c, hipMemcpyAsync(t->d_bow_value + (size_t)slot * t->cap, f->d_bow_value, (size_t)f->bow_n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            }
+            HIPCHK(c, hipMemcpyAsync(t->d_bow_n + slot, f->d_bow_n, sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+            t->h_bow_n[slot] = f->bow_n;
+            t->has_bow[slot] = 1;
+        } else if (t->d_bow_n) {
+            HIPCHK(c, hipMemsetAsync(t->d_bow_n + slot, 0, sizeof(int32_t), c->stream));
+        }
         return AFV_OK;
     });
 }
@@ -953,10 +1119,11 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         // plane moves, so that a table of another shape or row width on any rank is refused everywhere instead of mismatching the
         // lengths of the broadcasts below
         // (the kind travels next to the width: 64-byte binary rows and rows of 16 floats have the same pitch and the same byte size)
-        int32_t flags[8] = {t->d_idx != nullptr, t->d_geo != nullptr, t->d_valid != nullptr, (int32_t)blob.size(), t->nsets, t->cap, t->desc_bytes, t->float_dim};
+        int32_t flags[9] = {t->d_idx != nullptr, t->d_geo != nullptr, t->d_valid != nullptr, (int32_t)blob.size(), t->nsets, t->cap, t->desc_bytes, t->float_dim,
+                            t->d_bow_word != nullptr};
         int32_t *d_flags = nullptr;
         HIPCHK(c, hipMalloc(&d_flags, sizeof(flags) + (size_t)(m->nranks + 1) * sizeof(int32_t)));
-        int32_t *d_ok = d_flags + 8, *d_oks = d_ok + 1;
+        int32_t *d_ok = d_flags + 9, *d_oks = d_ok + 1;
         hipError_t e = hipMemcpyAsync(d_flags, flags, sizeof(flags), hipMemcpyHostToDevice, c->stream);
         int rc = e == hipSuccess ? afv_comm_broadcast(m, d_flags, sizeof(flags), root, c->stream) : AFV_EHIP;
         if (rc == AFV_OK) e = hipMemcpyAsync(flags, d_flags, sizeof(flags), hipMemcpyDeviceToHost, c->stream);
@@ -988,6 +1155,10 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         if (flags[0] && !t->d_idx) HIPCHK(c, hipMalloc(&t->d_idx, plane * sizeof(int32_t)));
         if (flags[1] && !t->d_geo) HIPCHK(c, hipMalloc(&t->d_geo, 4 * plane * sizeof(float)));
         if (flags[2] && !t->d_valid) HIPCHK(c, hipMalloc(&t->d_valid, plane));
+        if (flags[8]) {
+            const int rcb = table_ensure_bow(t);
+            if (rcb) return rcb;
+        }
         int32_t *d_meta = nullptr;
         HIPCHK(c, hipMalloc(&d_meta, (size_t)flags[3] * sizeof(int32_t)));
         struct Free { void *p; ~Free() { (void)hipFree(p); } } free_meta{d_meta};
@@ -999,6 +1170,9 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         if (!rc && flags[0]) rc = afv_comm_broadcast(m, t->d_idx, plane * sizeof(int32_t), root, c->stream);
         if (!rc && flags[1]) rc = afv_comm_broadcast(m, t->d_geo, 4 * plane * sizeof(float), root, c->stream);
         if (!rc && flags[2]) rc = afv_comm_broadcast(m, t->d_valid, plane, root, c->stream);
+        if (!rc && flags[8]) rc = afv_comm_broadcast(m, t->d_bow_word, plane * sizeof(int32_t), root, c->stream);
+        if (!rc && flags[8]) rc = afv_comm_broadcast(m, t->d_bow_value, plane * sizeof(double), root, c->stream);
+        if (!rc && flags[8]) rc = afv_comm_broadcast(m, t->d_bow_n, (size_t)t->nsets * sizeof(int32_t), root, c->stream);
         if (!rc) rc = afv_comm_broadcast(m, d_meta, (size_t)flags[3] * sizeof(int32_t), root, c->stream);
         if (rc) {
             (void)hipStreamSynchronize(c->stream);
@@ -1011,8 +1185,10 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         // receivers: nothing of the previous content survives; counts first, then the FeatureVectors against them
         for (int s = 0; s < t->nsets; ++s) {
             t->fv[s] = HostFeatVec();
-            t->has_fv[s] = t->has_geo[s] = 0;
+            t->has_fv[s] = t->has_geo[s] = t->has_bow[s] = 0;
+            t->h_bow_n[s] = 0;
         }
+        if (!flags[8] && t->d_bow_n) HIPCHK(c, afv_fill(c, t->d_bow_n, 0, (size_t)t->nsets * sizeof(int32_t)));
         if (!flags[2] && t->d_valid) HIPCHK(c, afv_fill(c, t->d_valid, 1, plane));
         rc = afv_table_sync_counts(t);
         if (rc) return rc;

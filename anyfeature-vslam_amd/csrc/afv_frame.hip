@@ -77,6 +77,7 @@ extern "C" int afv_frame_create(afv_ctx *c, const afv_frame_params *params, afv_
         const size_t o_n = take(16), o_cptr = take((ncell + 1) * 4), o_cent = take((size_t)cap * 16);
         const size_t o_leaf = take((size_t)cap * 4), o_nid = take((size_t)cap * 4), o_seg = take((size_t)cap * 4), o_oct = take((size_t)cap);
         const size_t o_dense = take((size_t)cap * 4);
+        const size_t o_bword = take((size_t)cap * 4), o_bval = take((size_t)cap * 8);
         hipError_t e = hipMalloc(reinterpret_cast<void **>(&f->d_block), off);
         if (e == hipSuccess) e = hipMemsetAsync(f->d_block, 0, off, c->stream);
         if (e != hipSuccess) {
@@ -98,6 +99,9 @@ extern "C" int afv_frame_create(afv_ctx *c, const afv_frame_params *params, afv_
         f->d_seg_idx = reinterpret_cast<int *>(B + o_seg);
         f->d_oct0 = B + o_oct;
         f->d_dense = reinterpret_cast<int *>(B + o_dense);
+        f->d_bow_word = reinterpret_cast<int32_t *>(B + o_bword);
+        f->d_bow_value = reinterpret_cast<double *>(B + o_bval);
+        f->d_bow_n = f->d_n + 2;
         try {
             c->frames.push_back(f);
             std::lock_guard<std::mutex> lk(g_frames_mutex);
@@ -159,6 +163,7 @@ static int frame_launch_grid(afv_frame *f, bool soa, bool copy_xy, bool use_tab,
 int afv_frame_after_extract(afv_frame *f, hipStream_t s) {
     f->has_features = true;
     f->has_fv = false;
+    f->has_bow = false;
     f->has_grid = false;
     const int rc = frame_launch_grid(f, true, !f->p.distorted, true, true, !f->p.distorted, true, s);
     if (rc) return rc;
@@ -203,6 +208,7 @@ extern "C" int afv_frame_set_features(afv_frame *f, const afv_keypoint *kps, con
         f->n = n;
         f->has_features = true;
         f->has_fv = false;
+        f->has_bow = false;
         f->has_grid = false;
         const int rc = frame_launch_grid(f, true, !f->p.distorted, size == nullptr, u_right == nullptr, !f->p.distorted, false, s);
         if (rc) return rc;
@@ -275,12 +281,15 @@ extern "C" int afv_frame_bow_transform(afv_frame *f, const afv_vocab *v, int lev
         hipStream_t s = c->stream;
         const int n = f->n;
         f->has_fv = false;
+        f->has_bow = false;
+        f->bow_n = 0;
         f->fv_node_id.clear();
         f->fv_seg_ptr.clear();
         f->fv_total = 0;
         if (nnodes_out) *nnodes_out = 0;
         if (n == 0) {
             f->has_fv = true;
+            f->has_bow = v->d_weight != nullptr;  // an empty BowVector
             return AFV_OK;
         }
         // results for the host: leaf / node ids / sort keys land in the pinned arena, written by the kernel that builds the body
@@ -308,6 +317,12 @@ extern "C" int afv_frame_bow_transform(afv_frame *f, const afv_vocab *v, int lev
         afv_launch_featvec_build(f->d_leaf, f->d_nid, f->d_dense, n, f->cap, width, v->dev.stopped, f->d_seg_idx, zc ? h_kept : f->d_nkept,
                                  zc ? h_leaf : nullptr, zc ? h_nid : nullptr, zc ? h_dense : nullptr, s);
         HIPCHK(c, hipGetLastError());
+        int *h_bow_n = h_kept + 1;
+        if (v->d_weight) {  // the BowVector, built where the leaves are (k_bowvec.hip)
+            afv_launch_bowvec_build(f->d_leaf, n, v->d_weight, v->d_word_id, v->d_word_weight, f->d_bow_word, f->d_bow_value, f->d_bow_n, s);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(h_bow_n, f->d_bow_n, sizeof(int), hipMemcpyDeviceToHost, s));
+        }
         if (!zc) {
             HIPCHK(c, hipMemcpyAsync(h_leaf, f->d_leaf, (size_t)n * 4, hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipMemcpyAsync(h_nid, f->d_nid, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -342,6 +357,11 @@ extern "C" int afv_frame_bow_transform(afv_frame *f, const afv_vocab *v, int lev
         }
         f->fv_total = kept;
         f->has_fv = true;
+        if (v->d_weight) {
+            if (*h_bow_n < 0 || *h_bow_n > n) return AFV_EHIP;
+            f->bow_n = *h_bow_n;
+            f->has_bow = true;
+        }
         if (nnodes_out) *nnodes_out = (int32_t)f->fv_node_id.size();
         return AFV_OK;
     });
@@ -360,6 +380,19 @@ extern "C" int afv_frame_get_featvec(afv_frame *f, int32_t *node_id, int32_t *se
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipMemcpy(seg_idx, f->d_seg_idx, (size_t)f->fv_total * 4, hipMemcpyDeviceToHost));
+    }
+    return AFV_OK;
+}
+
+extern "C" int afv_frame_get_bowvec(afv_frame *f, int32_t *word, double *value, int32_t *n_out) {
+    if (!f || !n_out || !f->has_bow) return AFV_EINVAL;  // afv_frame_bow_transform on a vocabulary with weights first
+    afv_ctx *c = f->c;
+    *n_out = f->bow_n;
+    if (f->bow_n > 0 && (word || value)) {
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (word) HIPCHK(c, hipMemcpy(word, f->d_bow_word, (size_t)f->bow_n * 4, hipMemcpyDeviceToHost));
+        if (value) HIPCHK(c, hipMemcpy(value, f->d_bow_value, (size_t)f->bow_n * 8, hipMemcpyDeviceToHost));
     }
     return AFV_OK;
 }

@@ -99,6 +99,19 @@ extern "C" void afv_launch_bow_transform(const DevVocab *v, const uint32_t *desc
                                          int *node_at_level, int *rank_at_level, hipStream_t stream);
 extern "C" int afv_launch_bow_transform_f32(const DevVocab *v, const float *desc, int n, int dim, int levelsup, int *leaf_node, int *node_at_level,
                                             int *rank_at_level, hipStream_t stream);
+// BowVector / L1 score kernels (k_bowvec.hip)
+struct DevBowQuery {
+    const int32_t *word;
+    const double *value;
+    int n;
+    int pad;
+};
+extern "C" void afv_launch_bowvec_build(const int *leaf, int n, const double *weight, const int32_t *word_id, const double *word_weight,
+                                        int32_t *out_word, double *out_value, int *out_n, hipStream_t stream);
+extern "C" void afv_launch_score_bow(const DevBowQuery *q, int nq, const int32_t *bow_word, const double *bow_value, const int32_t *bow_n,
+                                     const uint8_t *slot_state, int nsets, int cap, int32_t *common, double *score, int32_t *first_common,
+                                     hipStream_t stream);
+#define AFV_BOW_MAX_ENTRIES 8192  // entries of one BowVector the kernels take (= AFV_MAX_SIDE, the largest frame)
 struct afv_vocab {
     DevVocab dev{};
     int desc_bytes = 32;
@@ -107,6 +120,9 @@ struct afv_vocab {
     uint8_t *d_stopped = nullptr;
     std::vector<uint8_t> h_stopped;  // host copy of the stop list (empty: none)
     std::vector<int> depth_width;    // nodes per depth (index = depth, 0 = the root)
+    double *d_weight = nullptr;      // [nnodes] by DBoW2 node id (afv_vocab_set_weights; nullptr: the vocabulary builds no BowVectors)
+    int32_t *d_word_id = nullptr;    // [nnodes] word id of a leaf, -1 for inner nodes
+    double *d_word_weight = nullptr; // [largest word id + 1] the leaf weights again, by word id
 };
 
 // the device-resident Frame (afv_frame.hip)
@@ -129,6 +145,12 @@ struct afv_frame {
     // host side of the FeatureVector: node structure for the merge-join
     std::vector<int32_t> fv_node_id, fv_seg_ptr;
     int fv_total = 0;
+    // the BowVector (afv_frame_bow_transform on a vocabulary with weights): entries ascending by word id
+    int32_t *d_bow_word = nullptr;   // [cap]
+    double *d_bow_value = nullptr;   // [cap]
+    int *d_bow_n = nullptr;
+    bool has_bow = false;
+    int bow_n = 0;
 };
 
 #define AFV_MAX_SIDE 8192
@@ -445,6 +467,12 @@ struct afv_table {
     std::vector<HostFeatVec> fv;
     std::vector<uint8_t> has_fv, has_geo;  // per set: afv_table_set_featvec / afv_table_set_geometry called since the last afv_table_set
     std::vector<uint8_t> fv_body_on_device;  // per set: the FeatureVector body came from a frame (afv_table_set_from_frame): no host copy yet
+    // BowVector planes (afv_table_set_bowvec / afv_table_set_from_frame), lazily allocated together
+    int32_t *d_bow_word = nullptr;  // [nsets][cap] word ids ascending
+    double *d_bow_value = nullptr;  // [nsets][cap]
+    int32_t *d_bow_n = nullptr;     // [nsets]
+    std::vector<int32_t> h_bow_n;
+    std::vector<uint8_t> has_bow;   // per set: a BowVector was stored since the last afv_table_set
     // grow-only device buffers of the pair entry points + their pinned host image
     int32_t *d_pairs = nullptr;  // [2][pair_cap]
     int32_t *d_out = nullptr;    // [pair_cap][cap]

@@ -120,6 +120,15 @@ class Frame:
         stays on the device with the frame"""
         return vocabulary.vectors_from_nodes(*self.bow_transform_nodes(vocabulary, levelsup))
 
+    def bowvec(self):
+        """the resident BowVector ComputeBoW / bow_transform_nodes left on the device (a vocabulary with word weights): (word ids
+        ascending int32, L1-normalised values float64)"""
+        cap = max(self.N, 1)
+        word = np.zeros(cap, np.int32); value = np.zeros(cap, np.float64)
+        m = C.c_int32(0)
+        self.ctx.check(self.lib.afv_frame_get_bowvec(self.handle, ptr(word), ptr(value), C.byref(m)), "afv_frame_get_bowvec")
+        return word[:m.value].copy(), value[:m.value].copy()
+
     def featvec(self):
         """the resident FeatureVector as [(node_id, [feature indices])]"""
         n, nn = self.N, getattr(self, "_nnodes", 0)

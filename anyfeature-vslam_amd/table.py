@@ -140,6 +140,13 @@ class DescriptorTable:
         self.ctx.check(self.lib.afv_table_set_featvec(self.handle, int(slot), ptr(node_id), ptr(seg_ptr), ptr(seg_idx), len(node_id)),
                        "afv_table_set_featvec")
 
+    def set_bowvec(self, slot, word, value):
+        """KeyFrame::mBowVec of a slot: word ids ascending and unique, values float64 (Vocabulary.transform / Frame.bowvec)"""
+        word, value = _i32(word), np.ascontiguousarray(value, np.float64)
+        if len(word) != len(value):
+            raise ValueError("DescriptorTable.set_bowvec: %d words, %d values" % (len(word), len(value)))
+        self.ctx.check(self.lib.afv_table_set_bowvec(self.handle, int(slot), ptr(word), ptr(value), len(word)), "afv_table_set_bowvec")
+
     def set_geometry(self, slot, x, y, sigma2, u_right=None):
         """mvKeysUn positions and GetKeyPt1DSigma2 of a slot; u_right = KeyFrame::mvuRight of a stereo keyframe (None: monocular)"""
         x, y, s = (np.ascontiguousarray(v, np.float32) for v in (x, y, sigma2))
@@ -289,6 +296,36 @@ class DescriptorTable:
         self.ctx.check(self.lib.afv_table_match_bow_frame_h(self.handle, ptr(sl), len(sl), frame.handle, float(th_low), float(nnratio),
                                                             int(bool(check_orientation)), ptr(m), ptr(nm)), "afv_table_match_bow_frame_h")
         return m, nm
+
+    def score_bow(self, queries, slot_mask=None, want_first=True):
+        """words in common and Vocabulary::score (DBoW2 L1) of every query against the slots, one launch (afv_table_score_bow).
+        queries: a list whose items are an int (the BowVector of that slot), a frame.Frame (its resident BowVector) or a (word, value)
+        pair of host arrays.  slot_mask: uint8 [nsets] or None = every slot.  Returns common int32 [nq, nsets] (-1 = empty / masked /
+        no BowVector), score float64 [nq, nsets], first_common int32 [nq, nsets] (None when want_first is False)"""
+        from ._lib import BOW_QUERY_FRAME, BOW_QUERY_HOST, BOW_QUERY_SLOT, BowQuery
+        nq = len(queries)
+        rec = (BowQuery * max(nq, 1))()
+        keep = []
+        for r, q in zip(rec, queries):
+            r.struct_size = C.sizeof(BowQuery)
+            if isinstance(q, (int, np.integer)):
+                r.kind, r.slot = BOW_QUERY_SLOT, int(q)
+            elif hasattr(q, "handle"):
+                r.kind, r.frame = BOW_QUERY_FRAME, q.handle
+            else:
+                word, value = _i32(q[0]), np.ascontiguousarray(q[1], np.float64)
+                if len(word) != len(value):
+                    raise ValueError("DescriptorTable.score_bow: %d words, %d values" % (len(word), len(value)))
+                keep += [word, value]
+                r.kind, r.n = BOW_QUERY_HOST, len(word)
+                r.word, r.value = (word.ctypes.data, value.ctypes.data) if len(word) else (None, None)
+        mask = None if slot_mask is None else np.ascontiguousarray(slot_mask, np.uint8)
+        if mask is not None and mask.shape != (self.nsets,):
+            raise ValueError("DescriptorTable.score_bow: slot_mask must have one byte per slot")
+        common = np.zeros((nq, self.nsets), np.int32); score = np.zeros((nq, self.nsets), np.float64)
+        first = np.zeros((nq, self.nsets), np.int32) if want_first else None
+        self.ctx.check(self.lib.afv_table_score_bow(self.handle, rec, nq, ptr(mask), ptr(common), ptr(score), ptr(first)), "afv_table_score_bow")
+        return common, score, first
 
     def match_triangulation(self, pair_a, pair_b, F12, epipoles, th_low, has_mp1=None, has_mp2=None, only_stereo=False):
         """SearchForTriangulation per pair.  F12: [npairs, 9] (row-major), epipoles: [npairs, 2]; has_mp1/2: per pair uint8

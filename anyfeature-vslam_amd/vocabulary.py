@@ -81,6 +81,9 @@ class Vocabulary:
             stopped[~self.is_leaf] = 0
             if stopped.any():
                 self.ctx.check(self.ctx.lib.afv_vocab_set_stopped(self.ctx.handle, h, ptr(stopped)), "afv_vocab_set_stopped")
+            # the word weights: with them the device builds BowVectors (afv_frame_bow_transform, afv_bow_vector)
+            weight, word_id = np.ascontiguousarray(self.weight, np.float64), np.ascontiguousarray(self.word_id, np.int32)
+            self.ctx.check(self.ctx.lib.afv_vocab_set_weights(self.ctx.handle, h, ptr(weight), ptr(word_id)), "afv_vocab_set_weights")
         return self._handle
 
     def close(self):
@@ -99,6 +102,17 @@ class Vocabulary:
         self.ctx.check(rc, "afv_bow_transform")
         return leaf[:n], nid[:n]
 
+    def bow_vector(self, leaf):
+        """the BowVector of the features whose leaves the descent returned, built on the device (afv_bow_vector): (word ids ascending
+        int32, L1-normalised values float64) - DBoW2 transform's addWeight / normalize(L1), parity unpinned"""
+        leaf = np.ascontiguousarray(leaf, np.int32)
+        n = len(leaf)
+        word = np.zeros(max(n, 1), np.int32); value = np.zeros(max(n, 1), np.float64)
+        m = C.c_int32(0)
+        h = self._device()
+        self.ctx.check(self.ctx.lib.afv_bow_vector(self.ctx.handle, h, ptr(leaf), n, ptr(word), ptr(value), C.byref(m)), "afv_bow_vector")
+        return word[:m.value].copy(), value[:m.value].copy()
+
     def transform(self, descriptors, levelsup=4):
         """Vocabulary::transform(mDescriptors, mBowVec, mFeatVec) (Vocabulary.cpp:156-206): returns
         (BowVector {word_id: weight}, L1-normalised (TF-IDF weighting, L1 scoring: the ORB-SLAM vocabulary settings),
@@ -113,13 +127,16 @@ class Vocabulary:
         bow = {}
         for wid, ww in zip(self.word_id[leaf[keep]].tolist(), w[keep].tolist()):
             bow[wid] = bow.get(wid, 0.0) + ww          # BowVector::addWeight
-        s = sum(abs(v) for v in bow.values())
+        bow = dict(sorted(bow.items()))                # std::map: every walk over a BowVector is in ascending word order
+        s = 0.0
+        for v in bow.values():                         # BowVector::normalize(L1): norm += fabs(value), one addition per entry, map order
+            s = s + abs(v)                             # (not sum(): its order was the features' and newer Pythons compensate the sum)
         if s > 0:
-            bow = {kk: vv / s for kk, vv in bow.items()}   # BowVector::normalize(L1)
+            bow = {kk: vv / s for kk, vv in bow.items()}
         fv = {}
         for i in np.nonzero(keep)[0].tolist():
             fv.setdefault(int(nid[i]), []).append(i)   # FeatureVector::addFeature, features arrive in ascending order
-        return dict(sorted(bow.items())), sorted(fv.items())
+        return bow, sorted(fv.items())
 
     # ---- synthetic vocabulary for tests (no ORBvoc.txt offline) ----
     @classmethod

@@ -554,6 +554,47 @@ int afv_table_match_bow_frame_h(afv_table *t, const int32_t *slots, int nslots, 
  *   fixed-point workgroup) */
 int afv_set_projection_resolve(afv_ctx *ctx, int engine);
 
+/* ---- place recognition: BowVectors and DBoW2 L1 scores (the arithmetic under KeyFrameDatabase::DetectLoopCandidates /
+ * DetectRelocalizationCandidates, src/KeyFrameDatabase.cc:76-309, Vocabulary::score, src/Vocabulary.cpp:132-153, and the minScore loop of
+ * LoopClosing.cc:137-157).  DBoW2 is an empty submodule in the reference: BowVector::addWeight / normalize(L1) and L1Scoring::score follow
+ * upstream DBoW2 - parity unpinned.  New symbols and records only: AFV_ABI_VERSION stays 6. ----
+ *
+ * Word weights of a (binary or float) vocabulary, by DBoW2 node id: weight[nnodes] (TF-IDF node weights, read at the leaves) and
+ * word_id[nnodes] (-1 for inner nodes).  With weights set, afv_frame_bow_transform also builds the frame's BowVector on the device and
+ * afv_bow_vector works; weight == NULL removes them.  A vocabulary without weights behaves as before everywhere. */
+int afv_vocab_set_weights(afv_ctx *ctx, afv_vocab *v, const double *weight, const int32_t *word_id);
+/* DBoW2 transform's BowVector from the leaves afv_bow_transform[_f32] returned (n <= 8192): a feature whose leaf weight is not > 0 adds
+ * nothing; value[w] grows by one addition of weight[w] per feature; norm = sum of fabs(value) in ascending word order; every value is
+ * divided by it when norm > 0.  Entries ascending by word id; word / value hold up to n entries.  IEEE double throughout. */
+int afv_bow_vector(afv_ctx *ctx, const afv_vocab *v, const int32_t *leaf_node, int n, int32_t *word, double *value, int32_t *n_out);
+/* the BowVector afv_frame_bow_transform built (vocabulary with weights; AFV_EINVAL otherwise): up to the frame's cap entries */
+int afv_frame_get_bowvec(afv_frame *f, int32_t *word, double *value, int32_t *n_out);
+/* BowVector of keyframe `slot` from host arrays: ascending, unique word ids >= 0, n <= cap (else AFV_EINVAL).  afv_table_set on the slot
+ * forgets it; afv_table_set_from_frame brings the frame's along; afv_table_clone / afv_table_broadcast ship it. */
+int afv_table_set_bowvec(afv_table *t, int slot, const int32_t *word, const double *value, int n);
+
+#define AFV_BOW_QUERY_SLOT 0  /* the BowVector of table slot `slot` (LoopClosing) */
+#define AFV_BOW_QUERY_FRAME 1 /* the BowVector of resident frame `frame` (relocalisation: nothing is uploaded) */
+#define AFV_BOW_QUERY_HOST 2  /* host arrays word[n] (ascending, unique) / value[n], n <= 8192 */
+typedef struct afv_bow_query {
+    uint32_t struct_size; /* sizeof(afv_bow_query) of the caller's build */
+    int32_t kind;
+    int32_t slot;
+    int32_t n;
+    afv_frame *frame;
+    const int32_t *word;
+    const double *value;
+} afv_bow_query;
+/* nq queries against the slots of the table in ONE launch.  slot_mask[nsets] != NULL: only slots with a non-zero byte (naming a slot that
+ * holds features but no BowVector is AFV_EINVAL); NULL: every slot.  Per (query, slot), row-major [nq][nsets]:
+ *   common        words present in both vectors (mnLoopWords / mnRelocWords); -1 for an empty, masked-out or BowVector-less slot
+ *   first_common  the smallest shared word id, -1 when there is none (may be NULL)
+ *   score         L1Scoring::score(query, slot): over the shared words in ascending order s += fabs(v - w) - fabs(v) - fabs(w) (v: query,
+ *                 w: slot; left to right), result -s / 2.0; 0.0 when nothing is shared or the slot is absent
+ * A query slot / frame without BowVector is AFV_EINVAL. */
+int afv_table_score_bow(afv_table *t, const afv_bow_query *q, int nq, const uint8_t *slot_mask, int32_t *common, double *score,
+                        int32_t *first_common);
+
 /* DescriptorDistance_orb32 on the host (utility for adapters / tests) */
 int afv_hamming256(const uint8_t *a, const uint8_t *b);
 
