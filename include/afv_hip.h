@@ -370,7 +370,20 @@ typedef struct {
        distances in 16 bits). */
     int32_t float_dim;
 } afv_proj_job;
-/* assign = concatenation over jobs of int32[n]: index of the query assigned to feature i (F.pts[i] = pMP) or -1 */
+/* Job batches (njobs > 1; afv_match_projection, afv_match_fuse and afv_match_initialization alike; tests/test_gpu_proj_scenes.py):
+ *   - every job is answered as if it had been sent alone: the jobs share nothing but the call;
+ *   - the outputs follow each other in job order without padding: job k's slice starts at the sum of the earlier jobs' lengths, where a
+ *     job's length is n (feature-indexed) for afv_match_projection and nq (query-indexed) for afv_match_fuse / _initialization;
+ *     nmatches / nfound has one entry per job.  A job with n == 0 or nq == 0 is legal anywhere in the array (an empty slice / a slice
+ *     of -1, count 0);
+ *   - the jobs of one call may differ in everything: n, nq, the grid, the mode, check_orientation, occupancy masks, stereo fields,
+ *     the width of binary rows (1 .. 64 bytes) and binary next to float rows (float_dim).  The engine of the ordered phase is chosen
+ *     per CALL: the fixed point runs when the tables of the call's largest job fit the LDS of one workgroup, else every job of the
+ *     call takes the ordered walk; one float job in an afv_match_initialization call sends the whole call to the ordered walk.  The
+ *     answers do not depend on the engine;
+ *   - limits, per job: n <= 8192, nq <= 65535, grid_cols * grid_rows <= 8192, desc_bytes <= 64, float_dim a multiple of 4 <= 1024.
+ *     One job outside them refuses the whole call with AFV_EINVAL before anything is launched or written.
+ * assign = concatenation over jobs of int32[n]: index of the query assigned to feature i (F.pts[i] = pMP) or -1 */
 int afv_match_projection(afv_ctx *ctx, const afv_proj_job *jobs, int njobs, int32_t *assign, int32_t *nmatches);
 /* matching core of FeatureMatcher::Fuse(pKF, vpMapPoints, th) (src/FeatureMatcher.cc:794-940) over
  * KeyFrame::GetFeaturesInArea (src/KeyFrame.cc:613-652): per map point the most similar keypoint of the window that lies in

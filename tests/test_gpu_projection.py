@@ -11,7 +11,7 @@ def proj_engine(request, gpu_ctx):
     point and the one-wavefront ordered walk of rounds 1-4 must give the same answers as the oracle"""
     gpu_ctx.check(gpu_ctx.lib.afv_set_projection_resolve(gpu_ctx.handle, request.param), "afv_set_projection_resolve")
     yield request.param
-    gpu_ctx.lib.afv_set_projection_resolve(gpu_ctx.handle, 2)
+    gpu_ctx.check(gpu_ctx.lib.afv_set_projection_resolve(gpu_ctx.handle, 2), "afv_set_projection_resolve")
 
 
 def _scene(afv, gpu_ctx, seed, shift, radius_scale, perm=True):
