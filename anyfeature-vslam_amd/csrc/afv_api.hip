@@ -1342,6 +1342,7 @@ static int validate_job(const afv_match_job &j, bool need_angles) {
         if (total > nf[s]) return AFV_EINVAL;  // a feature sits in exactly one node
         for (int i = 0; i < total; ++i)
             if (idxs[s][i] < 0 || idxs[s][i] >= nf[s]) return AFV_EINVAL;
+        if (afv_featvec_lists_twice(idxs[s], total, nf[s])) return AFV_EINVAL;  // ... and is listed once: total <= n alone lets (0, 0) pass
     }
     return AFV_OK;
 }

@@ -182,6 +182,7 @@ extern "C" int afv_table_set_featvec(afv_table *t, int set, const int32_t *node_
         if (total > n) return AFV_EINVAL;
         for (int i = 0; i < total; ++i)
             if (seg_idx[i] < 0 || seg_idx[i] >= n) return AFV_EINVAL;
+        if (afv_featvec_lists_twice(seg_idx, total, n)) return AFV_EINVAL;
     }
     return guarded(c, [&]() -> int {
         HIPCHK(c, hipSetDevice(c->device));
@@ -356,6 +357,7 @@ static int table_unpack_meta(afv_table *t, const int32_t *blob, size_t len) {
                 HIPCHK(c, hipMemcpy(idx_row.data(), t->d_idx + (size_t)s * t->cap, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost));
                 for (int i = 0; i < total; ++i)
                     if (idx_row[i] < 0 || idx_row[i] >= t->h_n[s]) return AFV_EINVAL;
+                if (afv_featvec_lists_twice(idx_row.data(), total, t->h_n[s])) return AFV_EINVAL;
                 f.seg_idx.assign(idx_row.begin(), idx_row.begin() + total);
             }
         }
@@ -613,6 +615,7 @@ static int table_match_bow_frame_impl(afv_table *t, const int32_t *slots, int ns
             if (FV.seg_ptr[k + 1] < FV.seg_ptr[k] || (k > 0 && FV.node_id[k] <= FV.node_id[k - 1])) return AFV_EINVAL;
         for (int i = 0; i < total; ++i)
             if (F->seg_idx[i] < 0 || F->seg_idx[i] >= nf) return AFV_EINVAL;
+        if (afv_featvec_lists_twice(F->seg_idx, total, nf)) return AFV_EINVAL;
     }
     HIPCHK(c, hipSetDevice(c->device));
     Blob b(c);

@@ -491,6 +491,19 @@ int afv_match_pairs_core(afv_ctx *c, const uint8_t *d_desc, const float *d_ang, 
 int afv_match_l2_pairs_core(afv_ctx *c, const float *d_desc, const float *d_ang, const int32_t *d_n, int cap, int dim, const int32_t *d_pair_a,
                             const int32_t *d_pair_b, int npairs, float th_low, float nnratio, int32_t *d_match, int32_t *d_nmatches, hipStream_t s);
 void afv_shared_segments(const afv_match_job &j, std::vector<Seg> &segs);
+// a FeatureVector lists every feature at most once (DBoW2 puts a feature into the one node it descends through): the per-node kernels
+// rely on it - their "taken" flags are indexed by the position inside a node, and two nodes may not write one output slot.  True when
+// idx[0 .. total) (already checked to lie in [0, n)) holds an index twice.  O(total), a bitmap of n bits
+inline bool afv_featvec_lists_twice(const int32_t *idx, int total, int n) {
+    std::vector<uint64_t> seen(((size_t)std::max(n, 0) + 63) / 64, 0);
+    for (int i = 0; i < total; ++i) {
+        uint64_t &w = seen[(size_t)idx[i] >> 6];
+        const uint64_t bit = 1ull << (idx[i] & 63);
+        if (w & bit) return true;
+        w |= bit;
+    }
+    return false;
+}
 int afv_check_resolve_guard(afv_ctx *c, const int32_t *nmatches, int n);
 void afv_table_release_all(afv_ctx *c);  // afv_destroy: tables / communicators still alive die with their context
 void afv_frame_release_all(afv_ctx *c);  // ... and so do its frames

@@ -103,6 +103,12 @@ class FeatureView:
                     ptrs[i + 1] = ptrs[i] + len(idx)
                 flat = (np.concatenate([np.asarray(idx, np.int32) for _, idx in self.featvec])
                         if self.featvec else np.zeros(0, np.int32))
+                # DBoW2 lists a feature in ONE node; the library refuses a FeatureVector that lists one twice (AFV_EINVAL) - say which
+                # feature before anything crosses the C boundary
+                inside = flat[(flat >= 0) & (flat < self.N)]
+                twice = np.nonzero(np.bincount(inside, minlength=1) > 1)[0]
+                if len(twice):
+                    raise _lib.AfvError(_lib.EINVAL, "FeatureView: feature %d is listed more than once in the FeatureVector" % int(twice[0]))
                 self._csr = (ids, ptrs, np.ascontiguousarray(flat, np.int32), len(self.featvec))
         return self._csr
 
