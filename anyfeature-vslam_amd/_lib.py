@@ -109,6 +109,15 @@ class BowQuery(C.Structure):
 BOW_QUERY_SLOT, BOW_QUERY_FRAME, BOW_QUERY_HOST = 0, 1, 2
 
 
+class VocabTrainParams(C.Structure):
+    """afv_vocab_train_params: DBoW2 Vocabulary::create on the device (binary descriptors)"""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_int32), ("L", C.c_int32), ("desc_bytes", C.c_int32), ("seed", C.c_uint64),
+                ("max_iters", C.c_int32), ("n_init", C.c_int32), ("init_centres", C.c_void_p)]
+
+
+VOCAB_TRAIN_MAX_ROWS = 1 << 26
+
+
 def sized(struct):
     """a job record with its struct_size filled in"""
     obj = struct()
@@ -197,6 +206,12 @@ SYMBOLS = {
     "afv_frame_get_bowvec": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_table_set_bowvec": (_i, [_vp, _i, _vp, _vp, _i]),
     "afv_table_score_bow": (_i, [_vp, C.POINTER(BowQuery), _i, _vp, _vp, _vp, _vp]),
+    "afv_vocab_train": (_i, [_vp, C.POINTER(VocabTrainParams), _vp, C.c_int64, _vp, _i, C.POINTER(_vp)]),
+    "afv_vocab_train_device": (_i, [_vp, C.POINTER(VocabTrainParams), _vp, _sz, C.c_int64, _vp, _i, C.POINTER(_vp)]),
+    "afv_vocab_tree_nnodes": (_i, [_vp]),
+    "afv_vocab_tree_get": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "afv_vocab_tree_stats": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "afv_vocab_tree_destroy": (None, [_vp]),
     "afv_hamming256": (_i, [_vp, _vp]),
     # include/afv_akaze.h
     "afv_akaze_default_params": (None, [_vp]),

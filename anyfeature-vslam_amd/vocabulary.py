@@ -67,6 +67,65 @@ class Vocabulary:
     def size(self):
         return int(self.is_leaf.sum())
 
+    # ---- DBoW2 TemplatedVocabulary::create on the device (afv_vocab_train; binary descriptors, TF-IDF weights) ----
+    @classmethod
+    def create(cls, training_features, k=10, L=6, seed=0, ctx=None, max_iters=0, init_centres=None, image_ptr=None, pitch=None, desc_bytes=None):
+        """Vocabulary::create(training_features) (createVocabulary.cpp:292-301) restated from upstream DBoW2 - parity unpinned; the
+        semantics are those of tests/_voctrain_ref.py (seeding from a counter-based generator keyed by `seed` and the path; an emptied
+        cluster keeps its centre).  training_features: a list of uint8 arrays [m_i, desc_bytes], one per image (empty ones allowed), or a
+        device tensor of uint8 rows ([n, pitch] or flat with `pitch`; the first `desc_bytes` of a row count, default all) and image_ptr
+        [nimages + 1] - then nothing leaves the device.  max_iters caps the rounds of a node (0: none); init_centres [<= k, desc_bytes]
+        replaces the seeding of the root.  Returns an ordinary Vocabulary; .train_stats holds the rounds, rows and seconds per level, the
+        image counts Ni per node and whether a node stopped at max_iters."""
+        from .extractor import Context
+        ctx = ctx or Context()
+        prm = _lib.sized(_lib.VocabTrainParams)
+        prm.k, prm.L, prm.seed, prm.max_iters = int(k), int(L), int(seed) & ((1 << 64) - 1), int(max_iters)
+        init = None
+        if init_centres is not None:
+            init = np.ascontiguousarray(init_centres, np.uint8)
+            if init.ndim != 2:
+                raise ValueError("init_centres: [n_init, desc_bytes]")
+            prm.n_init, prm.init_centres = init.shape[0], init.ctypes.data
+        tree = C.c_void_p()
+        if image_ptr is None:
+            imgs = [np.ascontiguousarray(f, np.uint8) for f in training_features]
+            widths = {f.shape[1] for f in imgs if f.ndim == 2 and len(f)}
+            if len(widths) != 1:
+                raise ValueError("training_features: uint8 rows of one width, at least one row")
+            prm.desc_bytes = widths.pop()
+            iptr = np.zeros(len(imgs) + 1, np.int32)
+            iptr[1:] = np.cumsum([len(f) for f in imgs])
+            rows = np.ascontiguousarray(np.concatenate([f.reshape(-1, prm.desc_bytes) for f in imgs if len(f)]), np.uint8)
+            rc = ctx.lib.afv_vocab_train(ctx.handle, C.byref(prm), ptr(rows), len(rows), ptr(iptr), len(imgs), C.byref(tree))
+        else:
+            import torch
+            t = training_features
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+                raise ValueError("training_features with image_ptr: a contiguous uint8 device tensor")
+            iptr = np.ascontiguousarray(image_ptr, np.int32)
+            row_pitch = int(pitch if pitch is not None else t.shape[-1])
+            prm.desc_bytes = int(desc_bytes if desc_bytes is not None else row_pitch)
+            if t.numel() < int(iptr[-1]) * row_pitch:
+                raise ValueError("training_features holds fewer rows than image_ptr names")
+            torch.cuda.synchronize(t.device)  # the rows must be there: the library works on its own stream
+            rc = ctx.lib.afv_vocab_train_device(ctx.handle, C.byref(prm), C.c_void_p(t.data_ptr()), row_pitch, int(iptr[-1]), ptr(iptr),
+                                                len(iptr) - 1, C.byref(tree))
+        ctx.check(rc, "afv_vocab_train")
+        try:
+            n = ctx.lib.afv_vocab_tree_nnodes(tree)
+            parent = np.zeros(n, np.int32); desc = np.zeros((n, prm.desc_bytes), np.uint8); leaf = np.zeros(n, np.uint8)
+            weight = np.zeros(n, np.float64); ni = np.zeros(n, np.int32)
+            ctx.check(ctx.lib.afv_vocab_tree_get(tree, ptr(parent), ptr(desc), ptr(leaf), ptr(weight), ptr(ni)), "afv_vocab_tree_get")
+            rounds = np.zeros(prm.L, np.int32); rows_l = np.zeros(prm.L, np.int64); secs = np.zeros(prm.L, np.float64)
+            capped = C.c_int32(0)
+            ctx.check(ctx.lib.afv_vocab_tree_stats(tree, ptr(rounds), ptr(rows_l), ptr(secs), C.byref(capped)), "afv_vocab_tree_stats")
+        finally:
+            ctx.lib.afv_vocab_tree_destroy(tree)
+        voc = cls(prm.k, prm.L, parent, desc, weight, leaf.astype(bool), ctx)
+        voc.train_stats = {"rounds": rounds, "rows": rows_l, "seconds": secs, "capped": bool(capped.value), "ni": ni, "parent": parent}
+        return voc
+
     def _device(self):
         if self._handle is None:
             from .extractor import Context

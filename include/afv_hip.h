@@ -608,6 +608,49 @@ typedef struct afv_bow_query {
 int afv_table_score_bow(afv_table *t, const afv_bow_query *q, int nq, const uint8_t *slot_mask, int32_t *common, double *score,
                         int32_t *first_common);
 
+/* ---- vocabulary training on the device: DBoW2 TemplatedVocabulary::create for binary descriptors (the trainer the reference ships as
+ * createVocabulary.py -> src/createVocabulary.cpp: loadBinaryFeatures :122-179, voc.create(features) :292-301, k / L at :50-51, TF_IDF and
+ * L1_NORM at :52-53).  DBoW2 is an empty submodule in the reference: HKmeansStep, initiateClustersKMpp, createWords, setNodeWeights and
+ * FORB::meanValue / distance are restated from upstream DBoW2 - parity unpinned.  tests/_voctrain_ref.py is the normative restatement; every
+ * quantity is an integer, the device is held to bit equality with it.  Two deliberate differences from upstream:
+ *   - a cluster that ends an association round empty KEEPS its previous centre (upstream releases it and the next distance reads an empty
+ *     matrix);
+ *   - the seeding draws come from a counter-based generator instead of rand(): sm = splitmix64, key(root) = sm(seed), key(child at cluster
+ *     position i) = sm(key(parent) ^ (i + 1)); first centre sm(key) % n, draw j: cut = 1 + sm(key + j * 0xD1342543DE82EF95) % dist_sum -
+ *     a pure function of (seed, path, draw), so all nodes of a level train at once.
+ * Weights: TF-IDF, log(nimages / Ni) in double on the host, Ni = images with a feature whose descent (afv_bow_transform's) ends in the word;
+ * Ni == 0 leaves 0.0.  Float vocabularies, the other weighting / scoring enums and the C++ adapter are out of scope.
+ * New symbols and records only: AFV_ABI_VERSION stays 6. ---- */
+#define AFV_VOCAB_TRAIN_MAX_ROWS (1 << 26) /* the largest n afv_vocab_train[_device] takes */
+typedef struct afv_vocab_train_params {
+    uint32_t struct_size;        /* sizeof(afv_vocab_train_params) of the caller's build */
+    int32_t k;                   /* branching factor, 2..32 */
+    int32_t L;                   /* depth levels, 1..10 */
+    int32_t desc_bytes;          /* 1..64 */
+    uint64_t seed;
+    int32_t max_iters;           /* cap on the associate / mean rounds of a node; 0 = unlimited (upstream) */
+    int32_t n_init;              /* rows of init_centres, 1..k (0 with init_centres == NULL) */
+    const uint8_t *init_centres; /* host rows [n_init][desc_bytes] replacing the seeding of the ROOT only (ignored when n <= k); NULL = seed */
+} afv_vocab_train_params;
+typedef struct afv_vocab_tree afv_vocab_tree;
+/* desc: host rows [n][desc_bytes] in image order then feature order; image_ptr[nimages + 1] (image_ptr[0] == 0, non-decreasing,
+ * image_ptr[nimages] == n; empty images are legal).  AFV_EINVAL, before any launch and with *out == NULL, for k outside 2..32, L outside
+ * 1..10, desc_bytes outside 1..64, n < 1 or n > AFV_VOCAB_TRAIN_MAX_ROWS, nimages < 1, an inconsistent image_ptr, n_init outside 1..k. */
+int afv_vocab_train(afv_ctx *ctx, const afv_vocab_train_params *params, const uint8_t *desc, int64_t n, const int32_t *image_ptr, int nimages,
+                    afv_vocab_tree **out);
+/* the same over a device array: row i at d_desc + i * pitch_bytes (pitch_bytes >= desc_bytes), e.g. what afv_orb_extract_batch_device left
+ * behind, compacted.  The work that produced the rows must have completed.  image_ptr stays on the host. */
+int afv_vocab_train_device(afv_ctx *ctx, const afv_vocab_train_params *params, const uint8_t *d_desc, size_t pitch_bytes, int64_t n,
+                           const int32_t *image_ptr, int nimages, afv_vocab_tree **out);
+int afv_vocab_tree_nnodes(const afv_vocab_tree *t); /* nodes in DBoW2 id order, node 0 = the root */
+/* per node, any pointer may be NULL: parent[nnodes] (0 for the root), desc[nnodes][desc_bytes] (zeros for the root), is_leaf[nnodes],
+ * weight[nnodes] (0.0 for inner nodes), ni[nnodes] (-1 for inner nodes) */
+int afv_vocab_tree_get(const afv_vocab_tree *t, int32_t *parent, uint8_t *desc, uint8_t *is_leaf, double *weight, int32_t *ni);
+/* per level (L entries each, any pointer may be NULL): association rounds run (the most any node of the level took; 0: only trivial
+ * nodes or none), rows of the level's non-trivial nodes, host seconds spent; *capped: some node stopped at max_iters unconverged */
+int afv_vocab_tree_stats(const afv_vocab_tree *t, int32_t *rounds, int64_t *rows, double *seconds, int32_t *capped);
+void afv_vocab_tree_destroy(afv_vocab_tree *t);
+
 /* DescriptorDistance_orb32 on the host (utility for adapters / tests) */
 int afv_hamming256(const uint8_t *a, const uint8_t *b);
 
