@@ -13,14 +13,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libafv_hip.so")
 SOURCES = ["k_pyramid.hip", "k_fast.hip", "k_harris.hip", "k_select.hip", "k_describe.hip", "k_match.hip", "k_match_mfma.hip", "k_project.hip", "k_bow.hip", "k_bowvec.hip", "k_match_l2.hip", "k_frame.hip",
-           "afv_api.hip", "afv_comm.hip", "afv_frame.hip", "k_akaze.hip", "k_akaze_detect.hip", "k_akaze_desc.hip", "akaze_api.hip", "k_voctrain.hip", "afv_voctrain.hip"]
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-         "-Wall", "-Wno-unused-function",
-         # no packed-fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 / v_pk_mov_b32), in any kernel: with an operand broadcast
-         # (op_sel) they return wrong lanes 48..63 while an MFMA kernel of another queue shares the SIMD (round 6, DESIGN_LOG;
-         # tools/probes/probe_pk_real.hip).  tests/test_isa_rules.py checks the built code objects.
-         "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-
+           "afv_api.hip", "afv_comm.hip", "afv_match_jobs.hip", "afv_frame.hip", "k_akaze.hip", "k_akaze_detect.hip", "k_akaze_desc.hip", "akaze_api.hip", "k_voctrain.hip", "afv_voctrain.hip"]
+BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
+              "-Wall", "-Wno-unused-function"]
+# no packed-fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 / v_pk_mov_b32), in any kernel: with an operand broadcast
+# (op_sel) they return wrong lanes 48..63 while an MFMA kernel of another queue shares the SIMD (round 6, DESIGN_LOG;
+# tools/probes/probe_pk_real.hip).  tests/test_isa_rules.py checks the built code objects.
+_SWITCH = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FLAGS = BASE_FLAGS + _SWITCH
 
 # Translation units built WITHOUT the target-feature switch.  The switch also moves the register allocator: k_match_topk_mfma<false> grows
 # from 168 to 177 vector registers = from 3 to 2 wavefronts per SIMD (kernel + 11 %, pairs10k 3.49 -> 3.17 M jobs/s: found in round 6's last
@@ -28,14 +28,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # holds integer / MFMA code only - no v_pk_*_f32 either way, which tests/test_isa_rules.py checks on the BUILT code objects of the whole
 # library, this file's included.
 NO_FEATURE_SWITCH = {"k_match_mfma.hip"}
-_SWITCH = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 def _flags_for(source):
-    if source in NO_FEATURE_SWITCH:
-        assert FLAGS[-4:] == _SWITCH
-        return FLAGS[:-4]
-    return FLAGS
+    return BASE_FLAGS if source in NO_FEATURE_SWITCH else FLAGS
 
 
 def _stale(target, deps):

@@ -647,22 +647,10 @@ extern "C" int afv_get_geometry(const afv_ctx *c, afv_geometry *g) {
     return AFV_OK;
 }
 
-// phase 2 of a brute-force pair call.  The workgroup-wide fixed point is the faster form while every pair has a CU to itself (one pair of
-// unrelated frames 23 -> 10 us, of overlapping video frames 61 -> 28 us; 256 overlapping pairs per call: 0.16 against 0.19 ms of
-// resolve tail), but it evaluates every live row in every pass: a batch that fills the chip several times over is throughput-bound
-// and faster with the one-wavefront walk (10 000 jobs: 3.52 M jobs/s against 3.30 M)
-static int resolve_engine_for(const afv_ctx *c, int npairs) {
-    return c->resolve_engine == 2 ? (npairs <= c->resolve_wg_max_pairs ? 1 : 0) : c->resolve_engine;
-}
-
 // ---- the pipeline ----
 // The small-batch ("latency") path: kernels shaped for one or a few frames (Tracking extracts ONE frame per call, Frame.cc:186) -
 // the whole pyramid in one launch, ... - same results bit for bit.  afv_set_small_batch_path: 0 = never, 1 = batches of at most
 // `small_max_frames` frames (default), 2 = always (parity tests).
-static bool small_batch_path(const afv_ctx *c, int nf) {
-    return c->small_mode == 2 || (c->small_mode == 1 && nf <= c->small_max_frames);
-}
-
 // kernels of one contiguous frame range [f0, f0 + nf) on stream s
 // clear_status: this range is the whole call, *d_status is cleared ahead of its kernels (by the one-launch pyramid when there is one)
 // d_desc == nullptr: keypoints only (afv_orb_detect); pyramid_only: nothing behind the pyramid (afv_orb_compute describes given keypoints on it)
@@ -1289,33 +1277,7 @@ extern "C" int afv_debug_blur_level(afv_ctx *c, int frame, int level, uint8_t *o
 }
 
 
-// merge-join of the two FeatureVectors (FeatureMatcher.cc:205-276): list of (range1, range2) for shared node ids
-void afv_shared_segments(const afv_match_job &j, std::vector<Seg> &segs) {
-    segs.clear();
-    if (j.nnodes1 == 0 || j.nnodes2 == 0) {
-        segs.push_back(Seg{0, j.n1, 0, j.n2});
-        return;
-    }
-    int a = 0, b = 0;
-    while (a < j.nnodes1 && b < j.nnodes2) {
-        if (j.node_id1[a] == j.node_id2[b]) {
-            segs.push_back(Seg{j.seg_ptr1[a], j.seg_ptr1[a + 1] - j.seg_ptr1[a], j.seg_ptr2[b], j.seg_ptr2[b + 1] - j.seg_ptr2[b]});
-            ++a;
-            ++b;
-        } else if (j.node_id1[a] < j.node_id2[b]) {
-            ++a;
-        } else {
-            ++b;
-        }
-    }
-}
-
-struct JobOffsets {
-    size_t d1, d2, segs, idx1, idx2, v1, v2, a1, a2, out, nm;
-    int nseg, words, nout, fdim;
-    bool has_idx, has_v1, has_v2, has_ang;
-};
-
+// ---- SearchByBoW / SearchForTriangulation over host arrays: argument checks and the jobs' sides; afv_match_jobs.hip stages and launches ----
 static int validate_job(const afv_match_job &j, bool need_angles) {
     if (j.n1 < 0 || j.n2 < 0 || j.n1 > AFV_MAX_SIDE || j.n2 > AFV_MAX_SIDE) return AFV_EINVAL;
     if ((j.n1 > 0 && !j.desc1) || (j.n2 > 0 && !j.desc2)) return AFV_EINVAL;
@@ -1328,74 +1290,34 @@ static int validate_job(const afv_match_job &j, bool need_angles) {
     if (j.nnodes1 > 0 && (!j.node_id1 || !j.seg_ptr1 || !j.seg_idx1)) return AFV_EINVAL;
     if (j.nnodes2 > 0 && (!j.node_id2 || !j.seg_ptr2 || !j.seg_idx2)) return AFV_EINVAL;
     if (need_angles && j.check_orientation && (!j.angle1 || !j.angle2)) return AFV_EINVAL;
-    // the CSR FeatureVectors size host copies and index descriptors on the device: check them here, O(n)
-    const int32_t *ptrs[2] = {j.seg_ptr1, j.seg_ptr2}, *idxs[2] = {j.seg_idx1, j.seg_idx2}, *ids[2] = {j.node_id1, j.node_id2};
-    const int nn[2] = {j.nnodes1, j.nnodes2}, nf[2] = {j.n1, j.n2};
-    for (int s = 0; s < 2; ++s) {
-        if (nn[s] == 0) continue;
-        if (ptrs[s][0] != 0) return AFV_EINVAL;
-        for (int i = 0; i < nn[s]; ++i) {
-            if (ptrs[s][i + 1] < ptrs[s][i]) return AFV_EINVAL;
-            if (i > 0 && ids[s][i] <= ids[s][i - 1]) return AFV_EINVAL;  // std::map order: strictly ascending node ids
+    // the CSR FeatureVectors size host copies and index descriptors on the device
+    const int rc = afv_featvec_check(j.node_id1, j.seg_ptr1, j.seg_idx1, j.nnodes1, j.n1);
+    return rc ? rc : afv_featvec_check(j.node_id2, j.seg_ptr2, j.seg_idx2, j.nnodes2, j.n2);
+}
+
+// the two sides of a host-array job, appended to B.sides
+static void push_job_sides(MatchBatch &B, const afv_match_job &j, bool tri) {
+    const bool guided = j.nnodes1 > 0 && j.nnodes2 > 0;  // else brute force: no node structure, no index arrays on either side
+    const bool frame2 = !tri && (j.mode & ~AFV_MATCH_FLOAT32) == AFV_MATCH_KF_FRAME;
+    MatchSide s[2];
+    for (int k = 0; k < 2; ++k) {
+        s[k].desc_bytes = j.desc_bytes;
+        s[k].fdim = (j.mode & AFV_MATCH_FLOAT32) ? j.desc_bytes / 4 : 0;
+        s[k].words = s[k].fdim ? s[k].fdim : (j.desc_bytes <= 32 ? 8 : 16);
+        s[k].n = k ? j.n2 : j.n1;
+        s[k].rows = k ? j.desc2 : j.desc1;
+        if (guided) {
+            s[k].node_id = k ? j.node_id2 : j.node_id1;
+            s[k].seg_ptr = k ? j.seg_ptr2 : j.seg_ptr1;
+            s[k].idx = k ? j.seg_idx2 : j.seg_idx1;
+            s[k].nnodes = k ? j.nnodes2 : j.nnodes1;
         }
-        const int total = ptrs[s][nn[s]];
-        if (total > nf[s]) return AFV_EINVAL;  // a feature sits in exactly one node
-        for (int i = 0; i < total; ++i)
-            if (idxs[s][i] < 0 || idxs[s][i] >= nf[s]) return AFV_EINVAL;
-        if (afv_featvec_lists_twice(idxs[s], total, nf[s])) return AFV_EINVAL;  // ... and is listed once: total <= n alone lets (0, 0) pass
+        if (!tri && j.check_orientation) s[k].angle = k ? j.angle2 : j.angle1;
     }
-    return AFV_OK;
-}
-
-static void stage_job(Blob &b, const afv_match_job &j, bool tri, JobOffsets &o) {
-    o.fdim = (j.mode & AFV_MATCH_FLOAT32) ? j.desc_bytes / 4 : 0;
-    const int kind = j.mode & ~AFV_MATCH_FLOAT32;
-    o.words = o.fdim ? o.fdim : (j.desc_bytes <= 32 ? 8 : 16);
-    o.d1 = o.fdim ? b.put(j.desc1, (size_t)j.n1 * j.desc_bytes) : put_desc(b, j.desc1, j.n1, j.desc_bytes, o.words);
-    o.d2 = o.fdim ? b.put(j.desc2, (size_t)j.n2 * j.desc_bytes) : put_desc(b, j.desc2, j.n2, j.desc_bytes, o.words);
-    std::vector<Seg> segs;
-    afv_shared_segments(j, segs);
-    o.nseg = (int)segs.size();
-    o.segs = b.put(segs.data(), segs.size() * sizeof(Seg));
-    o.has_idx = j.nnodes1 > 0 && j.nnodes2 > 0;
-    if (o.has_idx) {
-        o.idx1 = b.put(j.seg_idx1, (size_t)j.seg_ptr1[j.nnodes1] * 4);
-        o.idx2 = b.put(j.seg_idx2, (size_t)j.seg_ptr2[j.nnodes2] * 4);
-    }
-    o.has_v1 = j.valid1 != nullptr;
-    o.has_v2 = j.valid2 != nullptr && (tri || kind != AFV_MATCH_KF_FRAME);
-    if (o.has_v1) o.v1 = b.put(j.valid1, (size_t)j.n1);
-    if (o.has_v2) o.v2 = b.put(j.valid2, (size_t)j.n2);
-    o.has_ang = !tri && j.check_orientation;
-    if (o.has_ang) {
-        o.a1 = b.put(j.angle1, (size_t)j.n1 * 4);
-        o.a2 = b.put(j.angle2, (size_t)j.n2 * 4);
-    }
-    o.nout = (!tri && kind == AFV_MATCH_KF_FRAME) ? j.n2 : j.n1;
-}
-
-static void fill_dev_job(DevMatchJob &d, const afv_match_job &j, const JobOffsets &o, uint8_t *base, bool tri) {
-    d.d1 = reinterpret_cast<const uint32_t *>(base + o.d1);
-    d.d2 = reinterpret_cast<const uint32_t *>(base + o.d2);
-    d.n1 = j.n1;
-    d.n2 = j.n2;
-    d.words = o.fdim ? 0 : o.words;
-    d.fdim = o.fdim;
-    d.segs = reinterpret_cast<const Seg *>(base + o.segs);
-    d.nseg = o.nseg;
-    d.idx1 = o.has_idx ? reinterpret_cast<const int *>(base + o.idx1) : nullptr;
-    d.idx2 = o.has_idx ? reinterpret_cast<const int *>(base + o.idx2) : nullptr;
-    d.valid1 = o.has_v1 ? base + o.v1 : nullptr;
-    d.valid2 = o.has_v2 ? base + o.v2 : nullptr;
-    d.ang1 = o.has_ang ? reinterpret_cast<const float *>(base + o.a1) : nullptr;
-    d.ang2 = o.has_ang ? reinterpret_cast<const float *>(base + o.a2) : nullptr;
-    d.ang_stride = 1;
-    d.th = j.th_low;
-    d.ratio = j.nnratio;
-    d.check_ori = tri ? 0 : (j.check_orientation != 0);
-    d.mode = tri ? AFV_MATCH_KF_KF : (j.mode & ~AFV_MATCH_FLOAT32);
-    d.out = reinterpret_cast<int *>(base + o.out);
-    d.nmatches = reinterpret_cast<int *>(base + o.nm);
+    s[0].valid = j.valid1;
+    s[1].valid = frame2 ? nullptr : j.valid2;  // KF-Frame: validity on the keyframe side only (FeatureMatcher.cc:216-232)
+    B.sides.push_back(s[0]);
+    B.sides.push_back(s[1]);
 }
 
 static int afv_match_bow_impl(afv_ctx *c, const afv_match_job *jobs, int njobs, int32_t *out, int32_t *nmatches) {
@@ -1406,135 +1328,17 @@ static int afv_match_bow_impl(afv_ctx *c, const afv_match_job *jobs, int njobs, 
         const int kind = jobs[i].mode & ~AFV_MATCH_FLOAT32;
         if (kind != AFV_MATCH_KF_KF && kind != AFV_MATCH_KF_FRAME) return AFV_EINVAL;
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    {
-        // plain brute-force KF-KF jobs over 32-byte descriptors take the two-phase path of the device pipeline
-        // (parallel top-4 + ordered resolve): stage them as a descriptor table of 2 sets per job
-        bool eligible = true;
-        int cap = 1;
-        for (int i = 0; i < njobs; ++i) {
-            const afv_match_job &j = jobs[i];
-            eligible = eligible && (j.nnodes1 == 0 || j.nnodes2 == 0) && j.mode == AFV_MATCH_KF_KF && j.desc_bytes == 32 &&
-                       !j.valid1 && !j.valid2 && j.n1 <= 4096 && j.n2 <= 4096;
-            cap = std::max(cap, std::max(j.n1, j.n2));
-        }
-        if (eligible) {
-            Blob b(c);
-            const int nsets = 2 * njobs;
-            const size_t desc_off = b.reserve((size_t)nsets * cap * 32);
-            const size_t n_off = b.reserve((size_t)nsets * 4);
-            const size_t pa_off = b.reserve((size_t)njobs * 4), pb_off = b.reserve((size_t)njobs * 4);
-            bool any_ori = false;
-            for (int i = 0; i < njobs; ++i) any_ori = any_ori || jobs[i].check_orientation;
-            const size_t ang_off = any_ori ? b.reserve((size_t)nsets * cap * sizeof(float)) : 0;
-            for (int i = 0; i < njobs; ++i) {
-                const afv_match_job &j = jobs[i];
-                if (j.n1) std::memcpy(b.h.data() + desc_off + (size_t)(2 * i) * cap * 32, j.desc1, (size_t)j.n1 * 32);
-                if (j.n2) std::memcpy(b.h.data() + desc_off + (size_t)(2 * i + 1) * cap * 32, j.desc2, (size_t)j.n2 * 32);
-                int32_t *n = reinterpret_cast<int32_t *>(b.h.data() + n_off);
-                n[2 * i] = j.n1;
-                n[2 * i + 1] = j.n2;
-                reinterpret_cast<int32_t *>(b.h.data() + pa_off)[i] = 2 * i;
-                reinterpret_cast<int32_t *>(b.h.data() + pb_off)[i] = 2 * i + 1;
-                if (any_ori && j.check_orientation) {
-                    float *a1 = reinterpret_cast<float *>(b.h.data() + ang_off) + (size_t)(2 * i) * cap;
-                    std::memcpy(a1, j.angle1, (size_t)j.n1 * sizeof(float));
-                    std::memcpy(a1 + cap, j.angle2, (size_t)j.n2 * sizeof(float));
-                }
-            }
-            const size_t match_off = b.reserve((size_t)njobs * cap * 4), nm_off = b.reserve((size_t)njobs * 4);
-            const int nslices = small_batch_path(c, njobs) ? afv_match_topk_slices(cap, c->match_engine, ((cap + 63) / 64 + 1) / 2) : 1;
-            const size_t topk_off = b.reserve_scratch((size_t)njobs * cap * 32);
-            {
-                const int rc_ = ensure_slice_scratch(c, njobs, cap, nslices);
-                if (rc_) return rc_;
-            }
-            int rc = ensure_match_buffer(c, b.h.size());
-            if (rc) return rc;
-            HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), match_off, hipMemcpyHostToDevice, c->stream));  // inputs only
-            // jobs may differ in mbCheckOrientation / thresholds: launch runs of identical settings
-            int i0 = 0;
-            while (i0 < njobs) {
-                int i1 = i0 + 1;
-                while (i1 < njobs && jobs[i1].th_low == jobs[i0].th_low && jobs[i1].nnratio == jobs[i0].nnratio &&
-                       (jobs[i1].check_orientation != 0) == (jobs[i0].check_orientation != 0))
-                    ++i1;
-                const float *angp = any_ori ? reinterpret_cast<const float *>(c->d_match + ang_off) : nullptr;
-                const int *np_ = reinterpret_cast<const int *>(c->d_match + n_off);
-                const int *pa_ = reinterpret_cast<const int *>(c->d_match + pa_off), *pb_ = reinterpret_cast<const int *>(c->d_match + pb_off);
-                afv_launch_match_topk(c->d_match + desc_off, np_, cap, pa_, pb_, i1 - i0, c->d_match + topk_off, i0, c->match_engine, nslices, c->d_slice, c->d_tickets, 8, c->stream);
-                afv_launch_match_resolve(c->d_match + desc_off, angp, 1, np_, cap, pa_, pb_, i1 - i0, jobs[i0].th_low, jobs[i0].nnratio,
-                                         jobs[i0].check_orientation != 0, reinterpret_cast<int *>(c->d_match + match_off),
-                                         reinterpret_cast<int *>(c->d_match + nm_off), c->d_match + topk_off, i0, resolve_engine_for(c, njobs), 8, c->stream);
-                i0 = i1;
-            }
-            HIPCHK(c, hipGetLastError());
-            size_t acc = 0;
-            for (int i = 0; i < njobs; ++i) {
-                HIPCHK(c, b.fetch(out + acc, match_off + (size_t)i * cap * 4, (size_t)jobs[i].n1 * 4, c->stream));
-                acc += (size_t)jobs[i].n1;
-            }
-            HIPCHK(c, b.fetch(nmatches, nm_off, (size_t)njobs * 4, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            b.finish();
-            return afv_check_resolve_guard(c, nmatches, njobs);
-        }
-    }
-    Blob b(c);
-    std::vector<JobOffsets> offs(njobs);
-    for (int i = 0; i < njobs; ++i) stage_job(b, jobs[i], false, offs[i]);
-    size_t total_out = 0;
-    for (int i = 0; i < njobs; ++i) total_out += (size_t)offs[i].nout;
-    // BoW-guided jobs (more than one shared node) run one wavefront per node; a single-segment job (brute force) keeps
-    // the ordered workgroup-per-job kernel
-    bool per_node = false;
-    for (int i = 0; i < njobs; ++i) per_node = per_node || offs[i].nseg > 1;
-    const size_t out_off = b.reserve(std::max<size_t>(total_out, 1) * 4);
-    const size_t nm_off = b.reserve((size_t)njobs * 4);
-    const size_t jobs_off = b.reserve((size_t)njobs * sizeof(DevMatchJob));
-    std::vector<SegTask> tasks;
-    std::vector<int> bin_off(njobs, 0);
-    size_t tasks_off = 0, hist_off = 0, bins_off = 0, binoff_off = 0;
-    bool any_ori = false;
-    if (per_node) {
-        size_t acc = 0;
-        for (int i = 0; i < njobs; ++i) {
-            for (int sgi = 0; sgi < offs[i].nseg; ++sgi) tasks.push_back(SegTask{i, sgi});
-            bin_off[i] = (int)acc;
-            acc += (size_t)offs[i].nout;
-            any_ori = any_ori || jobs[i].check_orientation;
-        }
-        tasks_off = b.put(tasks.data(), tasks.size() * sizeof(SegTask));
-        hist_off = b.reserve((size_t)njobs * 32 * 4);
-        bins_off = b.reserve(std::max<size_t>(acc, 1));
-        binoff_off = b.put(bin_off.data(), (size_t)njobs * 4);
-    }
-    int rc = ensure_match_buffer(c, b.h.size());
-    if (rc) return rc;
-    size_t acc = 0;
+    bool taken = false;
+    const int rc = afv_match_bow_plain32(c, jobs, njobs, out, nmatches, &taken);
+    if (taken) return rc;
+    MatchBatch B;
+    B.whole_range = true;
     for (int i = 0; i < njobs; ++i) {
-        offs[i].out = out_off + acc * 4;
-        offs[i].nm = nm_off + (size_t)i * 4;
-        acc += (size_t)offs[i].nout;
-        fill_dev_job(reinterpret_cast<DevMatchJob *>(b.h.data() + jobs_off)[i], jobs[i], offs[i], c->d_match, false);
+        const afv_match_job &j = jobs[i];
+        push_job_sides(B, j, false);
+        B.jobs.push_back(MatchJobSpec{2 * i, 2 * i + 1, j.th_low, j.nnratio, j.check_orientation, j.mode & ~AFV_MATCH_FLOAT32});
     }
-    if (per_node) {  // the per-node kernel accumulates: outputs start at -1, counters at 0 (the blob is zero-filled)
-        int32_t *o = reinterpret_cast<int32_t *>(b.h.data() + out_off);
-        for (size_t i = 0; i < total_out; ++i) o[i] = -1;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), b.h.size(), hipMemcpyHostToDevice, c->stream));
-    if (per_node)
-        afv_launch_match_bow_seg(reinterpret_cast<const DevMatchJob *>(c->d_match + jobs_off), njobs, c->d_match + tasks_off,
-                                 (int)tasks.size(), reinterpret_cast<int *>(c->d_match + hist_off), c->d_match + bins_off,
-                                 reinterpret_cast<const int *>(c->d_match + binoff_off), any_ori ? 1 : 0, c->stream);
-    else
-        afv_launch_match_bow(reinterpret_cast<const DevMatchJob *>(c->d_match + jobs_off), njobs, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, b.fetch(out, out_off, total_out * 4, c->stream));
-    HIPCHK(c, b.fetch(nmatches, nm_off, (size_t)njobs * 4, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.finish();
-    return AFV_OK;
+    return afv_match_jobs_run(c, B, out, nmatches);
 }
 extern "C" int afv_match_bow(afv_ctx *c, const afv_match_job *jobs, int njobs, int32_t *out, int32_t *nmatches) {
     return guarded(c, [&] { return afv_match_bow_impl(c, jobs, njobs, out, nmatches); });
@@ -1544,77 +1348,21 @@ static int afv_match_triangulation_impl(afv_ctx *c, const afv_tri_job *caller_jo
     if (!c || !caller_jobs || njobs < 1 || !match12 || !nmatches) return AFV_EINVAL;
     std::vector<afv_tri_job> loaded;
     if (!afv_load_jobs(caller_jobs, njobs, offsetof(afv_tri_job, u_right1), loaded)) return AFV_EINVAL;
-    const afv_tri_job *jobs = loaded.data();
+    MatchBatch B;
+    B.tri = B.whole_range = true;
     for (int i = 0; i < njobs; ++i) {
-        const int rc = validate_job(jobs[i].bow, false);
+        const afv_tri_job &t = loaded[i];
+        const int rc = validate_job(t.bow, false);
         if (rc) return rc;
-        const afv_tri_job &t = jobs[i];
         if ((t.bow.n1 > 0 && (!t.x1 || !t.y1)) || (t.bow.n2 > 0 && (!t.x2 || !t.y2 || !t.sigma2_2))) return AFV_EINVAL;
         if (t.only_stereo != 0 && t.only_stereo != 1) return AFV_EINVAL;
+        push_job_sides(B, t.bow, true);
+        MatchSide &s1 = B.sides[2 * i], &s2 = B.sides[2 * i + 1];
+        s1.x = t.x1, s1.y = t.y1, s1.u_right = t.u_right1;  // u_right: stereo keyframes (FeatureMatcher.cc:705, :727), null = monocular
+        s2.x = t.x2, s2.y = t.y2, s2.sigma2 = t.sigma2_2, s2.u_right = t.u_right2;
+        B.jobs.push_back(MatchJobSpec{2 * i, 2 * i + 1, t.bow.th_low, t.bow.nnratio, 0, AFV_MATCH_KF_KF, t.F12, t.ex, t.ey, t.only_stereo});
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    Blob b(c);
-    std::vector<JobOffsets> offs(njobs);
-    std::vector<size_t> geo_off(njobs * 5), rowseg_off(njobs), ur_off(njobs * 2);
-    for (int i = 0; i < njobs; ++i) {
-        stage_job(b, jobs[i].bow, true, offs[i]);
-        const afv_tri_job &t = jobs[i];
-        geo_off[5 * i + 0] = b.put(t.x1, (size_t)t.bow.n1 * 4);
-        geo_off[5 * i + 1] = b.put(t.y1, (size_t)t.bow.n1 * 4);
-        geo_off[5 * i + 2] = b.put(t.x2, (size_t)t.bow.n2 * 4);
-        geo_off[5 * i + 3] = b.put(t.y2, (size_t)t.bow.n2 * 4);
-        geo_off[5 * i + 4] = b.put(t.sigma2_2, (size_t)t.bow.n2 * 4);
-        ur_off[2 * i + 0] = t.u_right1 ? b.put(t.u_right1, (size_t)t.bow.n1 * 4) : 0;  // stereo keyframes (FeatureMatcher.cc:705, :727)
-        ur_off[2 * i + 1] = t.u_right2 ? b.put(t.u_right2, (size_t)t.bow.n2 * 4) : 0;
-        // feature -> shared node (a feature sits in exactly one node of its FeatureVector)
-        std::vector<Seg> segs;
-        afv_shared_segments(t.bow, segs);
-        std::vector<int> row_seg((size_t)std::max(t.bow.n1, 1), -1);
-        const bool has_idx = t.bow.nnodes1 > 0 && t.bow.nnodes2 > 0;
-        for (size_t sgi = 0; sgi < segs.size(); ++sgi)
-            for (int r = 0; r < segs[sgi].n1; ++r) {
-                const int f = has_idx ? t.bow.seg_idx1[segs[sgi].s1 + r] : segs[sgi].s1 + r;
-                if (f >= 0 && f < t.bow.n1) row_seg[f] = (int)sgi;
-            }
-        rowseg_off[i] = b.put(row_seg.data(), row_seg.size() * 4);
-    }
-    size_t total_out = 0;
-    for (int i = 0; i < njobs; ++i) total_out += (size_t)jobs[i].bow.n1;
-    const size_t out_off = b.reserve(std::max<size_t>(total_out, 1) * 4);
-    const size_t nm_off = b.reserve((size_t)njobs * 4);
-    const size_t jobs_off = b.reserve((size_t)njobs * sizeof(DevTriJob));
-    int rc = ensure_match_buffer(c, b.h.size());
-    if (rc) return rc;
-    size_t acc = 0;
-    for (int i = 0; i < njobs; ++i) {
-        offs[i].out = out_off + acc * 4;
-        offs[i].nm = nm_off + (size_t)i * 4;
-        acc += (size_t)jobs[i].bow.n1;
-        DevTriJob &d = reinterpret_cast<DevTriJob *>(b.h.data() + jobs_off)[i];
-        fill_dev_job(d.m, jobs[i].bow, offs[i], c->d_match, true);
-        d.x1 = reinterpret_cast<const float *>(c->d_match + geo_off[5 * i + 0]);
-        d.y1 = reinterpret_cast<const float *>(c->d_match + geo_off[5 * i + 1]);
-        d.x2 = reinterpret_cast<const float *>(c->d_match + geo_off[5 * i + 2]);
-        d.y2 = reinterpret_cast<const float *>(c->d_match + geo_off[5 * i + 3]);
-        d.sigma2_2 = reinterpret_cast<const float *>(c->d_match + geo_off[5 * i + 4]);
-        std::memcpy(d.F, jobs[i].F12, sizeof(d.F));
-        d.ex = jobs[i].ex;
-        d.ey = jobs[i].ey;
-        d.row_seg = reinterpret_cast<const int *>(c->d_match + rowseg_off[i]);
-        d.u_right1 = jobs[i].u_right1 ? reinterpret_cast<const float *>(c->d_match + ur_off[2 * i + 0]) : nullptr;
-        d.u_right2 = jobs[i].u_right2 ? reinterpret_cast<const float *>(c->d_match + ur_off[2 * i + 1]) : nullptr;
-        d.only_stereo = jobs[i].only_stereo;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), b.h.size(), hipMemcpyHostToDevice, c->stream));
-    int max_n1 = 0;
-    for (int i = 0; i < njobs; ++i) max_n1 = std::max(max_n1, jobs[i].bow.n1);
-    afv_launch_match_tri(reinterpret_cast<const DevTriJob *>(c->d_match + jobs_off), njobs, max_n1, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, b.fetch(match12, out_off, total_out * 4, c->stream));
-    HIPCHK(c, b.fetch(nmatches, nm_off, (size_t)njobs * 4, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.finish();
-    return AFV_OK;
+    return afv_match_jobs_run(c, B, match12, nmatches);
 }
 extern "C" int afv_match_triangulation(afv_ctx *c, const afv_tri_job *jobs, int njobs, int32_t *match12, int32_t *nmatches) {
     return guarded(c, [&] { return afv_match_triangulation_impl(c, jobs, njobs, match12, nmatches); });

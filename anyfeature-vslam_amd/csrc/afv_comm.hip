@@ -170,20 +170,8 @@ extern "C" int afv_table_set_featvec(afv_table *t, int set, const int32_t *node_
     if (!t || set < 0 || set >= t->nsets || nnodes < 0 || (nnodes > 0 && (!node_id || !seg_ptr || !seg_idx))) return AFV_EINVAL;
     afv_ctx *c = t->c;
     const int n = t->h_n[set];
-    // same checks as the host-job path (validate_job): ascending ids, monotone pointers, indices in range, one node per feature
-    int total = 0;
-    if (nnodes > 0) {
-        if (seg_ptr[0] != 0) return AFV_EINVAL;
-        for (int i = 0; i < nnodes; ++i) {
-            if (seg_ptr[i + 1] < seg_ptr[i]) return AFV_EINVAL;
-            if (i > 0 && node_id[i] <= node_id[i - 1]) return AFV_EINVAL;
-        }
-        total = seg_ptr[nnodes];
-        if (total > n) return AFV_EINVAL;
-        for (int i = 0; i < total; ++i)
-            if (seg_idx[i] < 0 || seg_idx[i] >= n) return AFV_EINVAL;
-        if (afv_featvec_lists_twice(seg_idx, total, n)) return AFV_EINVAL;
-    }
+    if (afv_featvec_check(node_id, seg_ptr, seg_idx, nnodes, n)) return AFV_EINVAL;
+    const int total = nnodes ? seg_ptr[nnodes] : 0;
     return guarded(c, [&]() -> int {
         HIPCHK(c, hipSetDevice(c->device));
         if (!t->d_idx) HIPCHK(c, hipMalloc(&t->d_idx, (size_t)t->nsets * t->cap * sizeof(int32_t)));
@@ -355,11 +343,9 @@ static int table_unpack_meta(afv_table *t, const int32_t *blob, size_t len) {
             if (total < 0 || total > t->h_n[s] || !t->d_idx) return AFV_EINVAL;
             if (total) {
                 HIPCHK(c, hipMemcpy(idx_row.data(), t->d_idx + (size_t)s * t->cap, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost));
-                for (int i = 0; i < total; ++i)
-                    if (idx_row[i] < 0 || idx_row[i] >= t->h_n[s]) return AFV_EINVAL;
-                if (afv_featvec_lists_twice(idx_row.data(), total, t->h_n[s])) return AFV_EINVAL;
                 f.seg_idx.assign(idx_row.begin(), idx_row.begin() + total);
             }
+            if (afv_featvec_check(f.node_id.data(), f.seg_ptr.data(), f.seg_idx.data(), nnodes, t->h_n[s])) return AFV_EINVAL;
         }
         t->fv[s] = std::move(f);
         t->fv_body_on_device[s] = 0;
@@ -483,95 +469,53 @@ extern "C" int afv_table_match_pairs(afv_table *t, const int32_t *pair_a, const 
 }
 
 // ---- BoW-guided / triangulation batches over the table: the kernels of k_match.hip with job records that point into
-// the table; per call only the merge-joined segment lists (host work, FeatureMatcher.cc:205-276) are uploaded ----
-static void join_featvecs(const HostFeatVec &A, const HostFeatVec &B, std::vector<Seg> &segs) {
-    size_t a = 0, b = 0;
-    while (a < A.node_id.size() && b < B.node_id.size()) {
-        if (A.node_id[a] == B.node_id[b]) {
-            segs.push_back(Seg{A.seg_ptr[a], A.seg_ptr[a + 1] - A.seg_ptr[a], B.seg_ptr[b], B.seg_ptr[b + 1] - B.seg_ptr[b]});
-            ++a;
-            ++b;
-        } else if (A.node_id[a] < B.node_id[b]) {
-            ++a;
-        } else {
-            ++b;
-        }
+// the table; per call only the merge-joined segment lists (host work, FeatureMatcher.cc:205-276) are uploaded.  The routes below check
+// their arguments and describe the sides; afv_match_jobs.hip stages and launches ----
+// a slot as one side of a job: everything but the FeatureVector's node structure is on the device
+static MatchSide table_side(const afv_table *t, int slot) {
+    const size_t row0 = (size_t)slot * t->cap, plane = (size_t)t->nsets * t->cap;
+    const HostFeatVec &fv = t->fv[slot];
+    MatchSide s;
+    s.on_device = s.valid_on_device = true;
+    s.n = t->h_n[slot];
+    s.desc_bytes = t->desc_bytes, s.words = t->words, s.fdim = t->float_dim;
+    s.rows = t->d_desc + row0 * table_pitch(t);
+    s.idx = t->d_idx + row0;
+    s.idx_host = fv.seg_idx.data();
+    s.valid = t->d_valid ? t->d_valid + row0 : nullptr;  // FeatureMatcher.cc:593-597 / :609-613, :216-222
+    s.angle = t->d_angle + row0;
+    s.node_id = fv.node_id.data(), s.seg_ptr = fv.seg_ptr.data(), s.nnodes = (int)fv.node_id.size();
+    if (t->d_geo) {
+        s.x = t->d_geo + row0, s.y = t->d_geo + plane + row0, s.sigma2 = t->d_geo + 2 * plane + row0;
+        s.u_right = t->d_geo + 3 * plane + row0;  // -1 everywhere for a monocular keyframe (afv_table_set_geometry)
     }
+    return s;
+}
+
+// "no shared node" must not be confused with "FeatureVector never stored" (or, for triangulation, geometry never stored)
+static int check_slot_ready(const afv_table *t, int s, bool need_geo, const char *who) {
+    if (t->h_n[s] > 0 && (!t->has_fv[s] || (need_geo && !t->has_geo[s]))) {
+        t->c->last_error = std::string(who) + ": set " + std::to_string(s) + (need_geo ? " lacks its FeatureVector or geometry"
+                                                                                        : " holds features but no FeatureVector (afv_table_set_featvec)");
+        return AFV_EINVAL;
+    }
+    return AFV_OK;
 }
 
 static int table_match_bow_impl(afv_table *t, const int32_t *pair_a, const int32_t *pair_b, int npairs, float th_low, float nnratio,
                                 int check_orientation, int32_t *match12, int32_t *nmatches) {
-    afv_ctx *c = t->c;
     if (!t->d_idx) return AFV_EINVAL;  // no FeatureVector was ever stored
-    for (int p = 0; p < npairs; ++p)
-        for (int s : {pair_a[p], pair_b[p]})
-            if (t->h_n[s] > 0 && !t->has_fv[s]) {  // "no shared node" must not be confused with "FeatureVector never stored"
-                c->last_error = "afv_table_match_bow: set " + std::to_string(s) + " holds features but no FeatureVector (afv_table_set_featvec)";
-                return AFV_EINVAL;
-            }
-    HIPCHK(c, hipSetDevice(c->device));
-    const int cap = t->cap;
-    Blob b(c);
-    std::vector<Seg> segs;
-    std::vector<SegTask> tasks;
-    std::vector<int> seg_first((size_t)npairs + 1, 0);
+    MatchBatch B;
+    B.per_node = true;
+    B.out_stride = t->cap;
     for (int p = 0; p < npairs; ++p) {
-        const size_t before = segs.size();
-        join_featvecs(t->fv[pair_a[p]], t->fv[pair_b[p]], segs);
-        for (size_t s = before; s < segs.size(); ++s) tasks.push_back(SegTask{p, (int)(s - before)});
-        seg_first[p + 1] = (int)segs.size();
+        for (int s : {pair_a[p], pair_b[p]}) {
+            if (check_slot_ready(t, s, false, "afv_table_match_bow")) return AFV_EINVAL;
+            B.sides.push_back(table_side(t, s));
+        }
+        B.jobs.push_back(MatchJobSpec{2 * p, 2 * p + 1, th_low, nnratio, check_orientation, AFV_MATCH_KF_KF});
     }
-    const size_t segs_off = b.put(segs.data(), segs.size() * sizeof(Seg));
-    const size_t tasks_off = b.put(tasks.data(), tasks.size() * sizeof(SegTask));
-    const size_t jobs_off = b.reserve((size_t)npairs * sizeof(DevMatchJob));
-    const size_t binoff_off = b.reserve((size_t)npairs * sizeof(int));
-    const size_t hist_off = b.reserve((size_t)npairs * 32 * sizeof(int));
-    const size_t nm_off = b.reserve((size_t)npairs * sizeof(int));
-    const size_t in_bytes = b.h.size();
-    const size_t out_off = b.reserve_scratch((size_t)npairs * cap * sizeof(int));
-    const size_t bins_off = b.reserve_scratch((size_t)npairs * cap);
-    int rc = ensure_match_buffer(c, b.h.size());
-    if (rc) return rc;
-    DevMatchJob *J = reinterpret_cast<DevMatchJob *>(b.h.data() + jobs_off);
-    int *bin_off = reinterpret_cast<int *>(b.h.data() + binoff_off);
-    for (int p = 0; p < npairs; ++p) {
-        const int a = pair_a[p], bb = pair_b[p];
-        DevMatchJob &d = J[p];
-        d.d1 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)a * cap * table_pitch(t));
-        d.d2 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)bb * cap * table_pitch(t));
-        d.n1 = t->h_n[a];
-        d.n2 = t->h_n[bb];
-        d.words = t->float_dim ? 0 : t->words;
-        d.fdim = t->float_dim;
-        d.segs = reinterpret_cast<const Seg *>(c->d_match + segs_off) + seg_first[p];
-        d.nseg = seg_first[p + 1] - seg_first[p];
-        d.idx1 = t->d_idx + (size_t)a * cap;
-        d.idx2 = t->d_idx + (size_t)bb * cap;
-        d.valid1 = t->d_valid ? t->d_valid + (size_t)a * cap : nullptr;   // FeatureMatcher.cc:593-597 / :609-613
-        d.valid2 = t->d_valid ? t->d_valid + (size_t)bb * cap : nullptr;
-        d.ang1 = t->d_angle + (size_t)a * cap;
-        d.ang2 = t->d_angle + (size_t)bb * cap;
-        d.ang_stride = 1;
-        d.th = th_low;
-        d.ratio = nnratio;
-        d.check_ori = check_orientation != 0;
-        d.mode = AFV_MATCH_KF_KF;
-        d.out = reinterpret_cast<int *>(c->d_match + out_off) + (size_t)p * cap;
-        d.nmatches = reinterpret_cast<int *>(c->d_match + nm_off) + p;
-        bin_off[p] = p * cap;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_match + out_off, 0xff, (size_t)npairs * cap * sizeof(int), c->stream));  // -1
-    if (!tasks.empty())
-        afv_launch_match_bow_seg(reinterpret_cast<const DevMatchJob *>(c->d_match + jobs_off), npairs, c->d_match + tasks_off,
-                                 (int)tasks.size(), reinterpret_cast<int *>(c->d_match + hist_off), c->d_match + bins_off,
-                                 reinterpret_cast<const int *>(c->d_match + binoff_off), check_orientation ? 1 : 0, c->stream);
-    HIPCHK(c, hipGetLastError());
-    if (match12) HIPCHK(c, b.fetch(match12, out_off, (size_t)npairs * cap * sizeof(int), c->stream));
-    HIPCHK(c, b.fetch(nmatches, nm_off, (size_t)npairs * sizeof(int), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.finish();
-    return AFV_OK;
+    return afv_match_jobs_run(t->c, B, match12, nmatches);
 }
 
 extern "C" int afv_table_match_bow(afv_table *t, const int32_t *pair_a, const int32_t *pair_b, int npairs, float th_low, float nnratio,
@@ -590,100 +534,31 @@ extern "C" int afv_table_match_bow(afv_table *t, const int32_t *pair_a, const in
 // structure on the host side of the handle) and F only carries n
 static int table_match_bow_frame_impl(afv_table *t, const int32_t *slots, int nslots, const afv_frame_view *F, float th_low, float nnratio,
                                       int check_orientation, int32_t *match_f, int32_t *nmatches, const afv_frame *fr = nullptr) {
-    afv_ctx *c = t->c;
     if (!t->d_idx) return AFV_EINVAL;  // no FeatureVector was ever stored
-    const int nf = F->n, cap = t->cap;
+    MatchBatch B;
+    B.per_node = true;
+    B.out_stride = std::max(F->n, 1);
     for (int p = 0; p < nslots; ++p) {
         const int s = slots[p];
         if (s < 0 || s >= t->nsets) return AFV_EINVAL;
-        if (t->h_n[s] > 0 && !t->has_fv[s]) {
-            c->last_error = "afv_table_match_bow_frame: set " + std::to_string(s) + " holds features but no FeatureVector (afv_table_set_featvec)";
-            return AFV_EINVAL;
-        }
+        if (check_slot_ready(t, s, false, "afv_table_match_bow_frame")) return AFV_EINVAL;
+        B.sides.push_back(table_side(t, s));
+        B.jobs.push_back(MatchJobSpec{p, nslots, th_low, nnratio, check_orientation, AFV_MATCH_KF_FRAME});
     }
-    // the frame's FeatureVector: ascending node ids, indices inside the frame
-    HostFeatVec FV;
+    MatchSide f;  // the frame: one side of every job, it travels once; no validity on the frame side (FeatureMatcher.cc:216-222)
+    f.n = F->n;
+    f.desc_bytes = t->desc_bytes, f.words = t->words, f.fdim = t->float_dim;
     if (fr) {
-        FV.node_id = fr->fv_node_id;
-        FV.seg_ptr = fr->fv_seg_ptr;
-    } else if (F->nnodes > 0) {
-        FV.node_id.assign(F->node_id, F->node_id + F->nnodes);
-        FV.seg_ptr.assign(F->seg_ptr, F->seg_ptr + F->nnodes + 1);
-        const int total = FV.seg_ptr[F->nnodes];
-        if (FV.seg_ptr[0] != 0 || total < 0 || total > nf) return AFV_EINVAL;
-        for (int k = 0; k < F->nnodes; ++k)
-            if (FV.seg_ptr[k + 1] < FV.seg_ptr[k] || (k > 0 && FV.node_id[k] <= FV.node_id[k - 1])) return AFV_EINVAL;
-        for (int i = 0; i < total; ++i)
-            if (F->seg_idx[i] < 0 || F->seg_idx[i] >= nf) return AFV_EINVAL;
-        if (afv_featvec_lists_twice(F->seg_idx, total, nf)) return AFV_EINVAL;
+        f.on_device = true;
+        f.rows = fr->d_desc, f.idx = fr->d_seg_idx, f.angle = fr->d_angle;
+        f.node_id = fr->fv_node_id.data(), f.seg_ptr = fr->fv_seg_ptr.data(), f.nnodes = (int)fr->fv_node_id.size();
+    } else {  // the view's rows are packed at the table's width; the runner pads them to its pitch
+        if (afv_featvec_check(F->node_id, F->seg_ptr, F->seg_idx, F->nnodes, F->n)) return AFV_EINVAL;
+        f.rows = F->desc32, f.angle = check_orientation ? F->angle : nullptr;
+        if (F->nnodes > 0) f.node_id = F->node_id, f.seg_ptr = F->seg_ptr, f.idx = F->seg_idx, f.nnodes = F->nnodes;
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    Blob b(c);
-    std::vector<Seg> segs;
-    std::vector<SegTask> tasks;
-    std::vector<int> seg_first((size_t)nslots + 1, 0);
-    for (int p = 0; p < nslots; ++p) {
-        const size_t before = segs.size();
-        join_featvecs(t->fv[slots[p]], FV, segs);
-        for (size_t s = before; s < segs.size(); ++s) tasks.push_back(SegTask{p, (int)(s - before)});
-        seg_first[p + 1] = (int)segs.size();
-    }
-    const int nfe = std::max(nf, 1);
-    // the frame view's rows are packed at the table's width; the device rows are padded to its pitch
-    const size_t fdesc_off = fr ? 0 : ((t->float_dim || t->desc_bytes == AFV_DESC_BYTES) ? b.put(F->desc32, (size_t)nf * t->desc_bytes) : put_desc(b, F->desc32, nf, t->desc_bytes, t->words));
-    const size_t fang_off = (!fr && check_orientation && nf) ? b.put(F->angle, (size_t)nf * sizeof(float)) : 0;
-    const size_t fidx_off = fr ? 0 : b.put(F->nnodes > 0 ? F->seg_idx : nullptr, (size_t)(F->nnodes > 0 ? FV.seg_ptr[F->nnodes] : 0) * sizeof(int32_t));
-    const size_t segs_off = b.put(segs.data(), segs.size() * sizeof(Seg));
-    const size_t tasks_off = b.put(tasks.data(), tasks.size() * sizeof(SegTask));
-    const size_t jobs_off = b.reserve((size_t)nslots * sizeof(DevMatchJob));
-    const size_t binoff_off = b.reserve((size_t)nslots * sizeof(int));
-    const size_t hist_off = b.reserve((size_t)nslots * 32 * sizeof(int));
-    const size_t nm_off = b.reserve((size_t)nslots * sizeof(int));
-    const size_t in_bytes = b.h.size();
-    const size_t out_off = b.reserve_scratch((size_t)nslots * nfe * sizeof(int));
-    const size_t bins_off = b.reserve_scratch((size_t)nslots * nfe);
-    int rc = ensure_match_buffer(c, b.h.size());
-    if (rc) return rc;
-    DevMatchJob *J = reinterpret_cast<DevMatchJob *>(b.h.data() + jobs_off);
-    int *bin_off = reinterpret_cast<int *>(b.h.data() + binoff_off);
-    for (int p = 0; p < nslots; ++p) {
-        const int a = slots[p];
-        DevMatchJob &d = J[p];
-        d.d1 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)a * cap * table_pitch(t));
-        d.d2 = fr ? reinterpret_cast<const uint32_t *>(fr->d_desc) : reinterpret_cast<const uint32_t *>(c->d_match + fdesc_off);
-        d.n1 = t->h_n[a];
-        d.n2 = nf;
-        d.words = t->float_dim ? 0 : t->words;
-        d.fdim = t->float_dim;
-        d.segs = reinterpret_cast<const Seg *>(c->d_match + segs_off) + seg_first[p];
-        d.nseg = seg_first[p + 1] - seg_first[p];
-        d.idx1 = t->d_idx + (size_t)a * cap;
-        d.idx2 = fr ? fr->d_seg_idx : reinterpret_cast<const int *>(c->d_match + fidx_off);
-        d.valid1 = t->d_valid ? t->d_valid + (size_t)a * cap : nullptr;  // FeatureMatcher.cc:216-222
-        d.valid2 = nullptr;
-        d.ang1 = t->d_angle + (size_t)a * cap;
-        d.ang2 = fr ? fr->d_angle : reinterpret_cast<const float *>(c->d_match + fang_off);
-        d.ang_stride = 1;
-        d.th = th_low;
-        d.ratio = nnratio;
-        d.check_ori = check_orientation != 0;
-        d.mode = AFV_MATCH_KF_FRAME;
-        d.out = reinterpret_cast<int *>(c->d_match + out_off) + (size_t)p * nfe;
-        d.nmatches = reinterpret_cast<int *>(c->d_match + nm_off) + p;
-        bin_off[p] = p * nfe;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_match + out_off, 0xff, (size_t)nslots * nfe * sizeof(int), c->stream));  // -1
-    if (!tasks.empty())
-        afv_launch_match_bow_seg(reinterpret_cast<const DevMatchJob *>(c->d_match + jobs_off), nslots, c->d_match + tasks_off,
-                                 (int)tasks.size(), reinterpret_cast<int *>(c->d_match + hist_off), c->d_match + bins_off,
-                                 reinterpret_cast<const int *>(c->d_match + binoff_off), check_orientation ? 1 : 0, c->stream);
-    HIPCHK(c, hipGetLastError());
-    if (match_f && nf) HIPCHK(c, b.fetch(match_f, out_off, (size_t)nslots * nf * sizeof(int), c->stream));
-    HIPCHK(c, b.fetch(nmatches, nm_off, (size_t)nslots * sizeof(int), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.finish();
-    return AFV_OK;
+    B.sides.push_back(f);
+    return afv_match_jobs_run(t->c, B, F->n ? match_f : nullptr, nmatches);
 }
 
 extern "C" int afv_table_match_bow_frame(afv_table *t, const int32_t *slots, int nslots, const afv_frame_view *frame, float th_low,
@@ -873,103 +748,30 @@ static int table_fetch_fv_body(afv_table *t, int slot) {
 
 static int table_match_tri_impl(afv_table *t, const int32_t *pair_a, const int32_t *pair_b, const afv_table_tri_job *caller_geo, int npairs,
                                 int32_t *match12, int32_t *nmatches) {
-    afv_ctx *c = t->c;
-    std::vector<afv_table_tri_job> loaded;
-    if (!afv_load_jobs(caller_geo, npairs, offsetof(afv_table_tri_job, only_stereo), loaded)) return AFV_EINVAL;
-    const afv_table_tri_job *geo = loaded.data();
+    std::vector<afv_table_tri_job> geo;
+    if (!afv_load_jobs(caller_geo, npairs, offsetof(afv_table_tri_job, only_stereo), geo)) return AFV_EINVAL;
     for (int p = 0; p < npairs; ++p) {
         if (geo[p].only_stereo != 0 && geo[p].only_stereo != 1) return AFV_EINVAL;
-        const int rcf = table_fetch_fv_body(t, pair_a[p]);
+        const int rcf = table_fetch_fv_body(t, pair_a[p]);  // the row map of side a reads the body on the host
         if (rcf) return rcf;
     }
     if (!t->d_idx || !t->d_geo) return AFV_EINVAL;
-    for (int p = 0; p < npairs; ++p)
-        for (int s : {pair_a[p], pair_b[p]})
-            if (t->h_n[s] > 0 && (!t->has_fv[s] || !t->has_geo[s])) {
-                c->last_error = "afv_table_match_triangulation: set " + std::to_string(s) + " lacks its FeatureVector or geometry";
-                return AFV_EINVAL;
-            }
-    HIPCHK(c, hipSetDevice(c->device));
-    const int cap = t->cap;
-    const size_t plane = (size_t)t->nsets * cap;
-    Blob b(c);
-    std::vector<Seg> segs;
-    std::vector<int> seg_first((size_t)npairs + 1, 0);
-    std::vector<size_t> rowseg_off((size_t)npairs), m1_off((size_t)npairs, 0), m2_off((size_t)npairs, 0);
-    std::vector<int> row_seg;
+    MatchBatch B;
+    B.tri = true;
+    B.out_stride = t->cap;
     for (int p = 0; p < npairs; ++p) {
-        const HostFeatVec &A = t->fv[pair_a[p]];
-        const size_t before = segs.size();
-        join_featvecs(A, t->fv[pair_b[p]], segs);
-        seg_first[p + 1] = (int)segs.size();
-        const int n1 = t->h_n[pair_a[p]], n2 = t->h_n[pair_b[p]];
-        row_seg.assign((size_t)std::max(n1, 1), -1);  // feature -> shared node (a feature sits in exactly one node)
-        for (size_t s = before; s < segs.size(); ++s)
-            for (int r = 0; r < segs[s].n1; ++r) {
-                const int fi = A.seg_idx[segs[s].s1 + r];
-                if (fi < 0 || fi >= n1) return AFV_EINVAL;  // cannot happen while afv_table_sync_counts drops stale FeatureVectors
-                row_seg[fi] = (int)(s - before);
-            }
-        rowseg_off[p] = b.put(row_seg.data(), row_seg.size() * sizeof(int));
-        if (geo[p].has_mp1 && n1) m1_off[p] = b.put(geo[p].has_mp1, (size_t)n1);
-        if (geo[p].has_mp2 && n2) m2_off[p] = b.put(geo[p].has_mp2, (size_t)n2);
+        const uint8_t *has_mp[2] = {geo[p].has_mp1, geo[p].has_mp2};
+        for (int k = 0; k < 2; ++k) {
+            const int s = k ? pair_b[p] : pair_a[p];
+            if (check_slot_ready(t, s, true, "afv_table_match_triangulation")) return AFV_EINVAL;
+            MatchSide m = table_side(t, s);
+            m.valid = m.n ? has_mp[k] : nullptr;  // host masks "already has a map point" instead of the table's validity plane
+            m.valid_on_device = false;
+            B.sides.push_back(m);
+        }
+        B.jobs.push_back(MatchJobSpec{2 * p, 2 * p + 1, geo[p].th_low, 0.f, 0, AFV_MATCH_KF_KF, geo[p].F12, geo[p].ex, geo[p].ey, geo[p].only_stereo});
     }
-    const size_t segs_off = b.put(segs.data(), segs.size() * sizeof(Seg));
-    const size_t jobs_off = b.reserve((size_t)npairs * sizeof(DevTriJob));
-    const size_t nm_off = b.reserve((size_t)npairs * sizeof(int));
-    const size_t in_bytes = b.h.size();
-    const size_t out_off = b.reserve_scratch((size_t)npairs * cap * sizeof(int));
-    int rc = ensure_match_buffer(c, b.h.size());
-    if (rc) return rc;
-    DevTriJob *J = reinterpret_cast<DevTriJob *>(b.h.data() + jobs_off);
-    int max_n1 = 0;
-    for (int p = 0; p < npairs; ++p) {
-        const int a = pair_a[p], bb = pair_b[p];
-        DevTriJob &T = J[p];
-        DevMatchJob &d = T.m;
-        d.d1 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)a * cap * table_pitch(t));
-        d.d2 = reinterpret_cast<const uint32_t *>(t->d_desc + (size_t)bb * cap * table_pitch(t));
-        d.n1 = t->h_n[a];
-        d.n2 = t->h_n[bb];
-        max_n1 = std::max(max_n1, d.n1);
-        d.words = t->float_dim ? 0 : t->words;
-        d.fdim = t->float_dim;
-        d.segs = reinterpret_cast<const Seg *>(c->d_match + segs_off) + seg_first[p];
-        d.nseg = seg_first[p + 1] - seg_first[p];
-        d.idx1 = t->d_idx + (size_t)a * cap;
-        d.idx2 = t->d_idx + (size_t)bb * cap;
-        d.valid1 = (geo[p].has_mp1 && d.n1) ? c->d_match + m1_off[p] : nullptr;
-        d.valid2 = (geo[p].has_mp2 && d.n2) ? c->d_match + m2_off[p] : nullptr;
-        d.ang1 = d.ang2 = nullptr;
-        d.ang_stride = 1;
-        d.th = geo[p].th_low;
-        d.ratio = 0.f;
-        d.check_ori = 0;
-        d.mode = AFV_MATCH_KF_KF;
-        d.out = reinterpret_cast<int *>(c->d_match + out_off) + (size_t)p * cap;
-        d.nmatches = reinterpret_cast<int *>(c->d_match + nm_off) + p;
-        T.x1 = t->d_geo + (size_t)a * cap;
-        T.y1 = t->d_geo + plane + (size_t)a * cap;
-        T.x2 = t->d_geo + (size_t)bb * cap;
-        T.y2 = t->d_geo + plane + (size_t)bb * cap;
-        T.sigma2_2 = t->d_geo + 2 * plane + (size_t)bb * cap;
-        std::memcpy(T.F, geo[p].F12, sizeof(T.F));
-        T.ex = geo[p].ex;
-        T.ey = geo[p].ey;
-        T.row_seg = reinterpret_cast<const int *>(c->d_match + rowseg_off[p]);
-        T.u_right1 = t->d_geo + 3 * plane + (size_t)a * cap;  // -1 everywhere for a monocular keyframe (afv_table_set_geometry)
-        T.u_right2 = t->d_geo + 3 * plane + (size_t)bb * cap;
-        T.only_stereo = geo[p].only_stereo != 0;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_match + out_off, 0xff, (size_t)npairs * cap * sizeof(int), c->stream));
-    afv_launch_match_tri(reinterpret_cast<const DevTriJob *>(c->d_match + jobs_off), npairs, max_n1, c->stream);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, b.fetch(match12, out_off, (size_t)npairs * cap * sizeof(int), c->stream));
-    HIPCHK(c, b.fetch(nmatches, nm_off, (size_t)npairs * sizeof(int), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.finish();
-    return AFV_OK;
+    return afv_match_jobs_run(t->c, B, match12, nmatches);
 }
 
 extern "C" int afv_table_match_triangulation(afv_table *t, const int32_t *pair_a, const int32_t *pair_b, const afv_table_tri_job *geo,

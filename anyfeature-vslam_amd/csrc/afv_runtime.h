@@ -1,4 +1,4 @@
-// afv_runtime.h — host-side internals shared by the translation units behind the C-ABI (afv_api.hip, afv_comm.hip):
+// afv_runtime.h — host-side internals shared by the translation units behind the C-ABI (afv_api.hip, afv_comm.hip, afv_match_jobs.hip):
 // the context, the pinned staging arena (Blob) and the kernel launcher prototypes.  Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -299,6 +299,15 @@ static inline hipError_t afv_copy_dd(afv_ctx *c, void *dst, const void *src, siz
 
 static inline int cv_round(float v) { return (int)lrintf(v); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// the small-batch ("latency") path: kernels shaped for one or a few frames / pairs; afv_set_small_batch_path
+static inline bool small_batch_path(const afv_ctx *c, int nf) { return c->small_mode == 2 || (c->small_mode == 1 && nf <= c->small_max_frames); }
+// phase 2 of a brute-force pair call.  The workgroup-wide fixed point is the faster form while every pair has a CU to itself (one pair of
+// unrelated frames 23 -> 10 us, of overlapping video frames 61 -> 28 us; 256 overlapping pairs per call: 0.16 against 0.19 ms of
+// resolve tail), but it evaluates every live row in every pass: a batch that fills the chip several times over is throughput-bound
+// and faster with the one-wavefront walk (10 000 jobs: 3.52 M jobs/s against 3.30 M)
+static inline int resolve_engine_for(const afv_ctx *c, int npairs) {
+    return c->resolve_engine == 2 ? (npairs <= c->resolve_wg_max_pairs ? 1 : 0) : c->resolve_engine;
+}
 // the C-ABI never throws: host allocation failures inside the matcher entry points become AFV_ENOMEM
 template <class F>
 static inline int guarded(afv_ctx *c, F &&f) {
@@ -490,20 +499,47 @@ int afv_match_pairs_core(afv_ctx *c, const uint8_t *d_desc, const float *d_ang, 
 // d_ang != null: ang[set][cap] in degrees, the rotation histogram is applied
 int afv_match_l2_pairs_core(afv_ctx *c, const float *d_desc, const float *d_ang, const int32_t *d_n, int cap, int dim, const int32_t *d_pair_a,
                             const int32_t *d_pair_b, int npairs, float th_low, float nnratio, int32_t *d_match, int32_t *d_nmatches, hipStream_t s);
-void afv_shared_segments(const afv_match_job &j, std::vector<Seg> &segs);
-// a FeatureVector lists every feature at most once (DBoW2 puts a feature into the one node it descends through): the per-node kernels
-// rely on it - their "taken" flags are indexed by the position inside a node, and two nodes may not write one output slot.  True when
-// idx[0 .. total) (already checked to lie in [0, n)) holds an index twice.  O(total), a bitmap of n bits
-inline bool afv_featvec_lists_twice(const int32_t *idx, int total, int n) {
-    std::vector<uint64_t> seen(((size_t)std::max(n, 0) + 63) / 64, 0);
-    for (int i = 0; i < total; ++i) {
-        uint64_t &w = seen[(size_t)idx[i] >> 6];
-        const uint64_t bit = 1ull << (idx[i] & 63);
-        if (w & bit) return true;
-        w |= bit;
-    }
-    return false;
-}
+// ---- the BoW-guided matchers and SearchForTriangulation (afv_match_jobs.hip): one staging and launch path behind the host-array, table-slot
+// and frame entry points ----
+// A FeatureVector as CSR over `nnodes` ascending node ids, for a side of n features: seg_ptr[0] == 0, monotone pointers, strictly ascending
+// ids, seg_ptr[nnodes] <= n, every index in [0, n) and listed once (DBoW2 puts a feature into the one node it descends through; the per-node
+// kernels rely on it).  AFV_OK or AFV_EINVAL; O(n)
+int afv_featvec_check(const int32_t *node_id, const int32_t *seg_ptr, const int32_t *seg_idx, int nnodes, int n);
+struct MatchSide {  // where one side of a job lives
+    int n = 0;
+    int desc_bytes = 32, words = 8, fdim = 0;  // row width, dwords per device row, floats per row (0: binary)
+    bool on_device = false;          // rows / idx / angle / geometry are device pointers (table slot, resident frame); else host arrays to stage
+    const uint8_t *rows = nullptr;   // host: n packed rows of desc_bytes
+    const int32_t *idx = nullptr;    // FeatureVector feature indices in node order; null: identity
+    const int32_t *idx_host = nullptr;  // host copy of a device `idx` (the row map of triangulation reads it)
+    const uint8_t *valid = nullptr;  // [n] or null; its own flag: triangulation over the table brings host masks to device rows
+    bool valid_on_device = false;
+    const float *angle = nullptr;
+    const int32_t *node_id = nullptr, *seg_ptr = nullptr;  // host, always
+    int nnodes = 0;
+    const float *x = nullptr, *y = nullptr, *sigma2 = nullptr, *u_right = nullptr;  // triangulation only
+};
+struct MatchJobSpec {  // one job: its sides (indices into MatchBatch::sides) and settings
+    int side1, side2;
+    float th, ratio;
+    int check_ori, mode;  // AFV_MATCH_KF_KF / AFV_MATCH_KF_FRAME
+    const float *F12 = nullptr;  // triangulation: fundamental matrix, epipole, bOnlyStereo
+    float ex = 0, ey = 0;
+    int only_stereo = 0;
+};
+struct MatchBatch {
+    std::vector<MatchSide> sides;  // a side that several jobs name is staged once
+    std::vector<MatchJobSpec> jobs;
+    bool tri = false;          // SearchForTriangulation (else SearchByBoW)
+    bool whole_range = false;  // a side without nodes = one segment over both sides (brute force: host arrays); else no segment (tables)
+    bool per_node = false;     // always the per-node kernel (tables); else only when a job has more than one segment
+    int out_stride = 0;        // > 0: out[njobs][out_stride]; 0: ragged rows of n1 (KF-Frame: n2) ints per job, packed
+};
+// out may be null (counts only); rows start at -1, nmatches[njobs]
+int afv_match_jobs_run(afv_ctx *c, const MatchBatch &B, int32_t *out, int32_t *nmatches);
+// plain brute-force KF-KF jobs over 32-byte rows take the two-phase pair matcher (top-k + resolve over a table of two sets per job);
+// *taken = false: the batch is not of that kind, nothing was done
+int afv_match_bow_plain32(afv_ctx *c, const afv_match_job *jobs, int njobs, int32_t *out, int32_t *nmatches, bool *taken);
 int afv_check_resolve_guard(afv_ctx *c, const int32_t *nmatches, int n);
 void afv_table_release_all(afv_ctx *c);  // afv_destroy: tables / communicators still alive die with their context
 void afv_frame_release_all(afv_ctx *c);  // ... and so do its frames

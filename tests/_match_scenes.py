@@ -387,6 +387,54 @@ def all_constructed():
     return out
 
 
+def every_route_scene():
+    """ONE scene that every route to the BoW-guided kernels can take as it stands (host arrays alone or in a batch, table slots, the table
+    against a host frame view and against a RESIDENT frame): its FeatureVectors are what a small vocabulary (k = 5, L = 2, levelsup = 1)
+    makes of its descriptors, so Frame::ComputeBoW on the device arrives at K2's.  70 and 65 features of 32 bytes: one full wavefront and a
+    ragged tail.  Nodes 1, 2, 3 are shared (25 x 24, 20 x 18, 15 x 15 features), node 4 is on side 1 only (10), node 5 on side 2 only (8);
+    the features of a node are scattered over the index range.  Inside a node, feature j of either side sits ~16 bits from sub-prototype
+    j (the first six share one between two: they compete), sub-prototypes ~56 bits apart; angles differ by 0 (most), 90 or 200 degrees, so
+    the rotation histogram has losers; one feature in ten is masked out on either side.
+    Returns (kfkf Case, kff Case, arguments of afv.Vocabulary but ctx)"""
+    nb, k = 32, 5
+    rnd = lambda sd, m: S.lcg_bytes(sd, max(m, 1) * nb).reshape(max(m, 1), nb)[:m]
+    proto = rnd(7001, k)
+    sizes = ((25, 24), (20, 18), (15, 15), (10, 0), (0, 8))
+    D, A, node = ([], []), ([], []), ([], [])
+    for c, ms in enumerate(sizes):
+        m = max(ms)
+        sub = proto[c] ^ (rnd(7100 + c, m) & rnd(7200 + c, m) & rnd(7300 + c, m))
+        which = [j // 2 if j < 6 else j for j in range(m)]
+        a1 = (S.lcg_states(7400 + c, m) % 360).astype(np.float32)
+        delta = np.choose(S.lcg_states(7500 + c, m) % 20, [200.0] + [90.0] * 3 + [0.0] * 16).astype(np.float32)
+        for side in (0, 1):
+            n = ms[side]
+            sd = 7600 + 10 * c + 5 * side
+            D[side].append(sub[which[:n]] ^ (rnd(sd, n) & rnd(sd + 1, n) & rnd(sd + 2, n) & rnd(sd + 3, n)))
+            A[side].append((a1[:n] + side * delta[:n]) % np.float32(360.0))
+            node[side].extend([c + 1] * n)
+    K = []
+    for side in (0, 1):
+        n = len(node[side])
+        order = np.argsort(S.lcg_states(7700 + side, n), kind="stable")
+        desc = np.ascontiguousarray(np.concatenate(D[side])[order])
+        nid = np.asarray(node[side])[order]
+        dist = np.stack([R.hamming(p, desc) for p in proto], 1)            # what the descent at the root compares
+        assert np.array_equal(dist.argmin(1) + 1, nid) and np.all(np.sort(dist, 1)[:, 1] - dist.min(1) > 20)
+        fv = [(i, np.nonzero(nid == i)[0].tolist()) for i in sorted(set(nid.tolist()))]
+        valid = (S.lcg_bytes(7800 + side, n) > 25).astype(np.uint8)
+        pts = np.stack([100.0 + 3.0 * np.arange(n), np.full(n, 50.0)], 1).astype(np.float32)
+        K.append(afv.FeatureView(desc, fv, valid, np.concatenate(A[side])[order].astype(np.float32), pts, np.ones(n, np.float32), None))
+    assert (K[0].N, K[1].N) == (70, 65) and [i for i, _ in K[0].featvec] == [1, 2, 3, 4] and [i for i, _ in K[1].featvec] == [1, 2, 3, 5]
+    # the vocabulary: root, 5 nodes at depth 1 (the prototypes, ids 1 .. 5), 5 leaves under each; no stopped word
+    parent = [0] + [0] * k + [1 + c for c in range(k) for _ in range(k)]
+    leaves = np.concatenate([proto[c] ^ (rnd(7900 + c, k) & rnd(7950 + c, k) & rnd(7990 + c, k)) for c in range(k)])
+    node_desc = np.concatenate([np.zeros((1, nb), np.uint8), proto, leaves])
+    voc = (k, 2, parent, node_desc, [0.0] + [1.0] * (len(parent) - 1), [False] * (1 + k) + [True] * (k * k))
+    kw = dict(th_low=TH["b32"], nnratio=0.75, check_orientation=True)
+    return Case("every-route-kfkf", "kfkf", K[0], K[1], kw, None), Case("every-route-kff", "kff", K[0], K[1], dict(kw), None), voc
+
+
 def zero_shared(desc, seed):
     """FeatureVectors without a common node id"""
     K1, K2 = clustered(desc, 40, 50, seed, nodes=[(1, 20, None), (2, None, 25), (3, 20, None), (4, None, 25)])

@@ -3,6 +3,8 @@ k_match_bow_finish, the top-4 + resolve path and k_match_tri.  Bar: every output
 (tests/test_match_ref_cpu.py proves on the CPU that the oracle equals the restated reference on these scenes and that each scene reaches
 its rule).  A test walks many scenes and reports the names of ALL that differ.
 """
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -313,3 +315,57 @@ def test_a_feature_listed_twice_is_refused_by_every_entry_point(afv, matcher, gp
         m, nm = table.match_bow_frame([0], _twice(afv, 4, good), 75.0, 0.7, True)
         assert nm[0] == 4 and m[0].tolist() == [0, 1, 2, 3]
         table.close()
+
+
+def test_one_scene_through_every_bow_route(afv, oracle, matcher, gpu_ctx):
+    """MS.every_route_scene (70 x 65 features of 32 bytes, 3 shared nodes and 1 unshared on each side, masks, check_orientation on) through
+    the five routes that end in the BoW-guided kernels: the host-array (KF, KF) job alone; the same job behind a single-segment job with
+    n2 = 0 in one call; table slots of cap 80; the table against a host frame view; the table against a resident frame whose
+    FeatureVector the device computed.  The three (KF, KF) answers equal the oracle's search_by_bow_kf_kf and the two (KF, F) answers
+    its search_by_bow_kf_frame - the two rules differ (th_low strict or not, the frame-side mask, the key of the rotation histogram), so
+    a route is compared with the routes of its own rule - bit for bit on the n entries a layout holds for the job; the padded tail of
+    the table layout is -1; a frame without features leaves match_f alone and counts 0 for every slot"""
+    lib = afv._lib
+    kfkf, kff, voc_args = MS.every_route_scene()
+    K1, K2 = kfkf.K1, kfkf.K2
+    kw = kfkf.kw
+    (want12, n12), (want_f, n_f) = MS.run_oracle(oracle, kfkf), MS.run_oracle(oracle, kff)
+    assert n12 > 30 and n_f > 30 and n12 != n_f
+    got = {}
+    got["host"] = bow_jobs(afv, matcher, [kfkf])[0]
+    none = afv.FeatureView(afv.synth.random_descriptors(5, 7), None, None, np.zeros(7, np.float32))
+    nothing = afv.FeatureView(np.zeros((0, 32), np.uint8), None, None, np.zeros(0, np.float32))
+    other = MS.Case("single-segment-n2-0", "kfkf", none, nothing, dict(kw, check_orientation=False), None)
+    (m_other, n_other), got["batch"] = bow_jobs(afv, matcher, [other, kfkf])
+    assert n_other == 0 and m_other.tolist() == [-1] * 7
+    table = afv.table.DescriptorTable(gpu_ctx, 2, 80)
+    for slot, K in ((0, K1), (1, K2)):
+        table.set(slot, K.descriptors, K.angles)
+        table.set_featvec(slot, *K.csr()[:3])
+        table.set_valid(slot, K.valid)
+    m, nm = table.match_bow([0], [1], kw["th_low"], kw["nnratio"], True)
+    assert m.shape == (1, 80) and np.all(m[0, K1.N:] == -1)
+    got["slots"] = (m[0, :K1.N], int(nm[0]))
+    m, nm = table.match_bow_frame([0], K2, kw["th_low"], kw["nnratio"], True)
+    got["view"] = (m[0], int(nm[0]))
+    voc = afv.Vocabulary(*voc_args, ctx=gpu_ctx)
+    fr = afv.Frame(gpu_ctx)
+    kps = np.zeros(K2.N, afv.KP_DTYPE)
+    kps["x"], kps["y"], kps["size"], kps["angle"] = K2.pts[:, 0], K2.pts[:, 1], 31.0, K2.angles
+    fr.set_features(kps, K2.descriptors)
+    fr.ComputeBoW(voc, levelsup=1)
+    assert fr.featvec() == K2.featvec
+    m, nm = table.match_bow_frame_resident([0], fr, kw["th_low"], kw["nnratio"], True)
+    got["resident"] = (m[0], int(nm[0]))
+    # a frame without features: counts 0 for both slots, match_f untouched
+    view = lib.FrameView(None, 0, None, None, None, None, 0)
+    slots = np.array([0, 1], np.int32)
+    match_f = np.full(8, -7, np.int32)
+    counts = np.full(2, -7, np.int32)
+    gpu_ctx.check(table.lib.afv_table_match_bow_frame(table.handle, lib.ptr(slots), 2, ctypes.byref(view), kw["th_low"], kw["nnratio"], 1,
+                                                      lib.ptr(match_f), lib.ptr(counts)), "afv_table_match_bow_frame")
+    fr.close(); voc.close(); table.close()
+    assert counts.tolist() == [0, 0] and np.all(match_f == -7)
+    bad = [r for r in ("host", "batch", "slots") if got[r][1] != n12 or not np.array_equal(got[r][0], want12)]
+    bad += [r for r in ("view", "resident") if got[r][1] != n_f or not np.array_equal(got[r][0], want_f)]
+    assert bad == []

@@ -76,6 +76,20 @@ def _named(prefix):
     return [c for c in CASES if c.name.startswith(prefix)]
 
 
+def test_the_every_route_scene_needs_its_masks_and_its_histogram(oracle):
+    """MS.every_route_scene: the oracle equals the restatement under both rules, and the answer changes when the masks or the
+    orientation check are taken away - so a route that drops either one shows"""
+    kfkf, kff, _ = MS.every_route_scene()
+    for c in (kfkf, kff):
+        want, n = MS.run_oracle(oracle, c)
+        got, gn = MS.run_ref(c)[:2]
+        assert n == gn and np.array_equal(want, got) and n > 30
+        assert MS.run_oracle(oracle, c._replace(kw=dict(c.kw, check_orientation=False)))[1] > n
+        bare = [MS.afv.FeatureView(K.descriptors, K.featvec, None, K.angles) for K in (c.K1, c.K2)]
+        assert MS.run_oracle(oracle, c._replace(K1=bare[0], K2=bare[1]))[1] > n
+    assert not np.array_equal(MS.run_oracle(oracle, kfkf)[0][:65], MS.run_oracle(oracle, kff)[0])
+
+
 def test_node_shapes_land_where_they_are_meant_to():
     for c in CASES:
         if c.rule is None or c.kind == "tri":
