@@ -85,7 +85,7 @@ struct SelPoint {  // quadtree survivor, level coordinates
     float response;
 };
 
-// ---- k_pyramid_fused (k_pyramid.hip: the whole pyramid of a frame in one launch); plan and device image: afv_api.hip ----
+// ---- k_pyramid_fused (k_pyramid.hip: the whole pyramid of a frame in one launch); plan and device image: afv_extract.hip ----
 // The work plan lives in ONE device buffer ("blob"), written once per geometry, laid out so that a workgroup's share is a flat copy into
 // LDS: [common: one PfLevelC per level][x part of tile column 0][x part of tile column 1] ... [y part of tile row 0] ...
 // x part of tile column tx = per level the region descriptor (need.lo, need.hi inclusive, own.lo, own.hi exclusive; level 0: the source

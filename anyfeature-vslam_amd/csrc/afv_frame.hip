@@ -159,7 +159,7 @@ static int frame_launch_grid(afv_frame *f, bool soa, bool copy_xy, bool use_tab,
     return AFV_OK;
 }
 
-// called by extract_one (afv_api.hip) right after the describe kernel was enqueued with the frame as second destination
+// called by extract_one (afv_extract.hip) right after the describe kernel was enqueued with the frame as second destination
 int afv_frame_after_extract(afv_frame *f, hipStream_t s) {
     f->has_features = true;
     f->has_fv = false;

@@ -1,4 +1,4 @@
-// afv_runtime.h — host-side internals shared by the translation units behind the C-ABI (afv_api.hip, afv_comm.hip, afv_match_jobs.hip):
+// afv_runtime.h — host-side internals shared by the translation units behind the C-ABI (afv_api.hip, afv_extract.hip, afv_comm.hip, afv_match_jobs.hip):
 // the context, the pinned staging arena (Blob) and the kernel launcher prototypes.  Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -545,7 +545,14 @@ void afv_table_release_all(afv_ctx *c);  // afv_destroy: tables / communicators 
 void afv_frame_release_all(afv_ctx *c);  // ... and so do its frames
 int afv_frame_after_extract(afv_frame *f, hipStream_t s);  // afv_frame.hip: k_frame_grid behind the describe kernel of afv_frame_extract
 int afv_extract_into_frame(afv_ctx *c, afv_frame *f, const uint8_t *gray, int width, int height, int stride_bytes, afv_keypoint *kps,
-                           uint8_t *desc32, int cap, int *n_out);  // afv_api.hip: afv_orb_extract with the frame as second destination
+                           uint8_t *desc32, int cap, int *n_out);  // afv_extract.hip: afv_orb_extract with the frame as second destination
+// what afv_create (afv_api.hip) needs from the extractor's geometry (afv_extract.hip): level sizes, quotas and buffer layout of `max_batch`
+// frames of w x h, and the bytes of the pyramid / the elements of a candidate array that layout takes.  Hidden: the library's
+// dynamic symbol table stays as it was when one file held both sides
+#define AFV_LOCAL __attribute__((visibility("hidden")))
+AFV_LOCAL int afv_build_geometry(const afv_orb_params &p, int w, int h, int max_batch, Geo &g);
+AFV_LOCAL size_t afv_geo_pyr_bytes(const Geo &g, int max_batch);
+AFV_LOCAL size_t afv_geo_cand_elems(const Geo &g, int max_batch);
 // the host side of E12 (FeatureExtractor.cpp:132-172): keyPtsSize of octave `o` as afv_orb_size_sigma computes it
 float afv_size_of_octave(const afv_ctx *c, int octave);
 // projection searches over a feature side that is already on the device (afv_frame.hip) share the staging / launch code of the host-pointer

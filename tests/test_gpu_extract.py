@@ -452,6 +452,112 @@ def test_host_batch_pipeline_chunks(afv, oracle, pinned):
     ctx.close()
 
 
+def _image_forms(imgs, pad=37):
+    """the same images as the host entry points may meet them: {name: (keep-alive, [address per image], stride_bytes, page-locked)}.
+    The tight forms are one stacked array, so consecutive frames are contiguous in memory."""
+    import torch
+    h, w = imgs[0].shape
+    tight = np.ascontiguousarray(np.stack(imgs))
+    wide = np.full((len(imgs), h, w + pad), 255, np.uint8)   # the padding must never be read as pixels
+    wide[:, :, :w] = tight
+    p_tight = torch.from_numpy(tight).pin_memory()
+    p_wide = torch.from_numpy(wide).pin_memory()
+    assert p_tight.is_pinned() and p_wide.is_pinned()
+    n = len(imgs)
+    return {
+        "pageable-tight": (tight, [tight[i].ctypes.data for i in range(n)], w, False),
+        "pageable-strided": (wide, [wide[i].ctypes.data for i in range(n)], w + pad, False),
+        "pinned-tight": (p_tight, [p_tight[i].data_ptr() for i in range(n)], w, True),
+        "pinned-strided": (p_wide, [p_wide[i].data_ptr() for i in range(n)], w + pad, True),
+    }
+
+
+def test_every_host_entry_stages_the_same_image(afv, oracle):
+    """Every entry point that takes a HOST image (afv_orb_extract, afv_orb_detect, afv_orb_compute, afv_frame_extract, afv_orb_extract_batch as
+    one chunk and as chunks over the copy lane) brings it to the device the same way whatever memory it lies in: pageable or page-locked,
+    tight rows or rows with a stride - the C entry points are called directly, the Python wrapper would copy strided rows.  320 x 240: the
+    staging pitch equals the width (one linear copy); 199 x 151: it does not (2-D copies).  Bit-exact against the oracle on the tight image."""
+    import ctypes as C
+    lib = afv._lib.load()
+    ECAP = afv._lib.ECAPACITY
+    ctx = afv.Context(max_width=333, max_height=251, max_batch=3)
+    cap = ctx.cap
+    vp = C.c_void_p
+
+    def same(k, d, n, want, what):
+        wk, wd = want
+        assert n == len(wk), what
+        assert k[:n].tobytes() == wk.tobytes(), what
+        if d is not None:
+            assert np.array_equal(d[:n], wd), what
+
+    def batch(addrs, stride, w, h, cap_):
+        nf = len(addrs)
+        kps = np.zeros((nf, cap_), afv.KP_DTYPE); desc = np.zeros((nf, cap_, 32), np.uint8); n = np.full(nf, -1, np.int32)
+        arr = (vp * nf)(*addrs)
+        rc = lib.afv_orb_extract_batch(ctx.handle, arr, nf, w, h, stride, afv._lib.ptr(kps), afv._lib.ptr(desc), cap_, afv._lib.ptr(n))
+        return rc, kps, desc, n
+
+    for (w, h, seed) in [(320, 240, 6), (199, 151, 8)]:
+        imgs = [afv.synth.corners_frame(seed + 100 * i, w, h) for i in range(3)]
+        want = [oracle.orb_extract(im) for im in imgs]
+        assert all(len(wk) > 8 for wk, _ in want)
+        forms = _image_forms(imgs)
+        frame = afv.Frame(ctx, max_x=float(w), max_y=float(h))
+        for name, (keep, addrs, stride, pinned) in forms.items():
+            what = (w, h, name)
+            a0 = vp(addrs[0])
+            # ---- afv_orb_extract, also with too little room ----
+            kps = np.zeros(cap, afv.KP_DTYPE); desc = np.zeros((cap, 32), np.uint8); n = C.c_int(-1)
+            assert lib.afv_orb_extract(ctx.handle, a0, w, h, stride, afv._lib.ptr(kps), afv._lib.ptr(desc), cap, C.byref(n)) == 0, what
+            same(kps, desc, n.value, want[0], what + ("extract",))
+            small = len(want[0][0]) // 2
+            kps = np.zeros(small, afv.KP_DTYPE); desc = np.zeros((small, 32), np.uint8); n = C.c_int(-1)
+            assert lib.afv_orb_extract(ctx.handle, a0, w, h, stride, afv._lib.ptr(kps), afv._lib.ptr(desc), small, C.byref(n)) == ECAP, what
+            assert n.value == small, what
+            assert kps.tobytes() == want[0][0][:small].tobytes() and np.array_equal(desc, want[0][1][:small]), what + ("extract, clamped",)
+            # ---- afv_orb_detect, afv_orb_compute at its keypoints ----
+            kd = np.zeros(cap, afv.KP_DTYPE); n = C.c_int(-1)
+            assert lib.afv_orb_detect(ctx.handle, a0, w, h, stride, afv._lib.ptr(kd), cap, C.byref(n)) == 0, what
+            same(kd, None, n.value, want[0], what + ("detect",))
+            kd = np.ascontiguousarray(kd[:n.value]); dc = np.zeros((n.value, 32), np.uint8)
+            assert lib.afv_orb_compute(ctx.handle, a0, w, h, stride, afv._lib.ptr(kd), n.value, afv._lib.ptr(dc)) == 0, what
+            assert np.array_equal(dc, want[0][1]), what + ("compute",)
+            # ---- afv_frame_extract ----
+            kps = np.zeros(cap, afv.KP_DTYPE); desc = np.zeros((cap, 32), np.uint8); n = C.c_int(-1)
+            assert lib.afv_frame_extract(frame.handle, vp(addrs[1]), w, h, stride, afv._lib.ptr(kps), afv._lib.ptr(desc), cap, C.byref(n)) == 0, what
+            same(kps, desc, n.value, want[1], what + ("frame_extract",))
+            assert frame.N == len(want[1][0]), what
+            # ---- afv_orb_extract_batch: one chunk of two frames; with too little room; three chunks of one frame over the copy lane ----
+            ctx.set_pipeline_chunk(64, 8)
+            rc, kps, desc, n = batch(addrs[:2], stride, w, h, cap)
+            assert rc == 0, what
+            for i in range(2):
+                same(kps[i], desc[i], int(n[i]), want[i], what + ("batch of 2", i))
+            small = min(len(wk) for wk, _ in want[:2]) // 2
+            rc, kps, desc, n = batch(addrs[:2], stride, w, h, small)
+            assert rc == ECAP and n.tolist() == [small, small], what
+            for i in range(2):
+                assert kps[i].tobytes() == want[i][0][:small].tobytes() and np.array_equal(desc[i], want[i][1][:small]), what + ("batch of 2, clamped", i)
+            ctx.set_pipeline_chunk(1, 1)
+            rc, kps, desc, n = batch(addrs, stride, w, h, cap)
+            assert rc == 0, what
+            for i in range(3):
+                same(kps[i], desc[i], int(n[i]), want[i], what + ("3 chunks", i))
+        # only the first frame page-locked: every frame goes through the arena (tight rows and rows with a stride; one chunk and three)
+        for a, b in (("pinned-tight", "pageable-tight"), ("pinned-strided", "pageable-strided")):
+            addrs = [forms[a][1][0]] + forms[b][1][1:]
+            for chunk, nf in ((1, 3), (64, 2)):
+                ctx.set_pipeline_chunk(chunk, 1)
+                rc, kps, desc, n = batch(addrs[:nf], forms[a][2], w, h, cap)
+                assert rc == 0, (w, h, a, b, chunk)
+                for i in range(nf):
+                    same(kps[i], desc[i], int(n[i]), want[i], (w, h, "mixed", a, chunk, i))
+        frame.close()
+        del forms
+    ctx.close()
+
+
 def test_device_resident_batch_matches_host_path(gpu_ctx, afv):
     import torch
     frames = np.stack([afv.synth.corners_frame(40 + i) for i in range(6)])
