@@ -4,6 +4,10 @@
 // (Feature_orb32.cpp:34; OpenCV fast.cpp FAST_t<16> + cornerScore<16>).  The Harris responses cv::ORB computes next are
 // k_harris.hip's job: they are only needed for the candidates that survive retainBest on the FAST score, which is known once
 // every tile of a level is done.  One 256-thread workgroup owns a 64x32 tile:
+//   0. FAST reports 3 <= x < w - 3, 3 <= y < h - 3 only and the tile grid starts at (0, 0): a tile of the last tile column / row that holds no such
+//      pixel (level size 1 .. 3 past a multiple of the tile) leaves at once, and in a bottom tile that the level ends inside, the wavefronts
+//      whose rows all lie past the last reportable row skip steps 2a and 3 (fast_tile_rect .. fast_nms_wave_idle below; the staged window
+//      and the cleared score plane stay whole, so nothing a later step reads depends on the skips);
 //   1. the tile plus a 4 px halo (ring radius 3 + the NMS neighbour) is staged in LDS with coalesced dword loads;
 //   2a. OpenCV's necessary pre-test (each of the 4 even antipodal ring pairs must hold a brighter / a darker pixel) on
 //      the 66x34 ring-extended tile, TWO horizontally adjacent pixels per lane as packed u16 pairs: per polarity
@@ -81,7 +85,40 @@ static_assert(FT_PITCH >= FT_LW && FT_PITCH % 4 == 0, "tile pitch");
 #define ST_GROUPS 14                                       // staging: 18 dword columns x 14 row groups = 252 threads
 #define ST_ITERS ((FT_LH + ST_GROUPS - 1) / ST_GROUPS)     // rows rs, rs + 14, ... (3 at FT_H = 32)
 static_assert(PRE_ITERS <= 16, "pre-test flags live in 16-bit halves");
+static_assert((FT_H + 1) / PRE_ITERS == PRE_GROUPS - 1, "the row group of score row FT_H is the last one");
 static_assert(ST_ITERS >= 2 && ST_GROUPS * (ST_ITERS - 1) <= FT_LH - 1, "staging rows");
+
+// ---- the part of a tile FAST can report ----
+// FAST_t visits 3 <= x < w - 3, 3 <= y < h - 3 only (cv::ORB runs it with edge threshold 0: this is the only border), the tile grid starts at
+// (0, 0) and covers the level with whole 64 x 32 tiles: the last tile column / row of a level may hold few reportable pixels or none.
+// In TILE coordinates (pixel 0 .. FT_W - 1 x 0 .. FT_H - 1 of tile (txi, tyi)) the reportable pixels are columns [x0, x1) x rows [y0, y1);
+// there are none when x1 <= x0 or y1 <= y0.  ONE set of expressions for the kernel and for afv_debug_fast_tiles below, which
+// tests/test_fast_ragged_cpu.py holds to the rectangles it computes itself.
+struct FastTileRect {
+    int x0, y0, x1, y1;
+};
+static inline __host__ __device__ FastTileRect fast_tile_rect(int lw, int lh, int txi, int tyi) {
+    const int ax = 3 - txi * FT_W, ay = 3 - tyi * FT_H, bx = lw - 3 - txi * FT_W, by = lh - 3 - tyi * FT_H;
+    FastTileRect r;
+    r.x0 = ax > 0 ? ax : 0;
+    r.y0 = ay > 0 ? ay : 0;
+    r.x1 = bx < FT_W ? bx : FT_W;
+    r.y1 = by < FT_H ? by : FT_H;
+    return r;
+}
+static inline __host__ __device__ bool fast_tile_empty(const FastTileRect &r) { return r.x1 <= r.x0 || r.y1 <= r.y0; }
+// The last row of the tile's score plane (tile rows -1 .. FT_H: the tile and the NMS neighbour rows it borrows from the tiles above / below)
+// whose score can be non-zero: FT_H unless the level ends inside the tile - then the last reportable row, h - 4.
+static inline __host__ __device__ int fast_row_hi(int lh, int tyi) {
+    const int r = lh - 4 - tyi * FT_H;
+    return r < FT_H ? r : FT_H;
+}
+// step 2a: row group g computes the tile rows PRE_ITERS g - 1 .. PRE_ITERS g + PRE_ITERS - 2; the last group that holds a row <= row_hi (row_hi >= 0)
+static inline __host__ __device__ int fast_last_row_group(int row_hi) { return (row_hi + 1) / PRE_ITERS; }
+// the first row group a wavefront of step 2a holds threads of (thread tid = row group tid / PRE_PAIRS): wavefront w is idle when it is past the last one
+static inline __host__ __device__ int fast_pre_wave_first_group(int w) { return w * AFV_WAVE / PRE_PAIRS; }
+// step 3: wavefront w owns the tile rows 2 NR w .. 2 NR w + 2 NR - 1 (NR = FT_H / 8): idle when its first row is past row_hi
+static inline __host__ __device__ bool fast_nms_wave_idle(int w, int row_hi) { return w * (FT_H / 4) > row_hi; }
 
 // two horizontally adjacent tile bytes as a packed u16 pair: one 16-bit LDS read (any alignment) + one byte permute
 __device__ __forceinline__ short2v ld_pair(const uint8_t *c, int off) {
@@ -198,7 +235,21 @@ __global__ __launch_bounds__(256) void k_fast_nms(const Geo *__restrict__ geo_p,
     const int tyi = (int)afv_udiv((uint32_t)t, L.dv_tiles_x), txi = t - tyi * L.tiles_x;
     const int gx0 = txi * FT_W - FT_HALO, gy0 = tyi * FT_H - FT_HALO;
     const int lw = L.w, lh = L.h;
+#ifndef FT_NO_EMPTY_SKIP  // (-DFT_NO_EMPTY_SKIP, -DFT_NO_ROW_TRIM: the kernel without either cut, kept for A / B runs)
+    // a tile without a reportable pixel (the last tile column / row of a level whose size is 1 .. 3 past a multiple of the tile) reports nothing
+    // whatever it holds: the workgroup leaves before it touches LDS, memory or a counter (tile-uniform: lw, lh, txi, tyi are scalars)
+    if (fast_tile_empty(fast_tile_rect(lw, lh, txi, tyi))) return;
+#endif
     const int tid = threadIdx.x, lane = tid & 63;
+    // bottom tiles of a level: the last row group of step 2a and the last row of step 3 that can matter; wavefronts past them skip the step
+    // (wave is a scalar: the skips are branches of the scalar unit, no lane is masked)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifndef FT_NO_ROW_TRIM
+    const int row_hi = fast_row_hi(lh, tyi);
+#else
+    const int row_hi = FT_H;
+#endif
+    const int g_last = fast_last_row_group(row_hi);
 
     const uint8_t *img;
     int pitch;
@@ -286,15 +337,18 @@ __global__ __launch_bounds__(256) void k_fast_nms(const Geo *__restrict__ geo_p,
     //     outside the FAST border in y exist in the top / bottom tiles of a level only and their scores are cleared by step 3 before
     //     anything looks at them, and the one row the last row group computes past the ring-extended tile (LDS row 38) lies where
     //     step 3 never reads.
+    //     In a bottom tile whose level ends at tile row row_hi < FT_H the row groups past g_last hold no row that can score (rows past h - 4 are
+    //     cleared by step 3 whatever they hold): their threads get 0x3fff in both halves of T0 - no entry, 0 in the wave scan - and a wavefront
+    //     that holds no other thread skips the step altogether.
     const int thr = geo.fast_threshold;
-    {
+    if (fast_pre_wave_first_group(wave) <= g_last) {
         const int rg0 = (int)(__umul24((unsigned)tid, 1928u) >> 16);  // tid / 34 (exact for tid < 256)
         const int rg = min(rg0, PRE_GROUPS - 1);
         const int pr = tid - rg0 * PRE_PAIRS;  // threads >= 238: 0 .. 17 (in range, unused)
         const int col = 2 + 2 * pr, gx = gx0 + col;
         short2v T0;
-        T0.x = (short)((rg0 < PRE_GROUPS && pr > 0 && gx >= 3 && gx < lw - 3) ? thr : 0x3fff);
-        T0.y = (short)((rg0 < PRE_GROUPS && pr < PRE_PAIRS - 1 && gx + 1 >= 3 && gx + 1 < lw - 3) ? thr : 0x3fff);
+        T0.x = (short)((rg0 <= g_last && pr > 0 && gx >= 3 && gx < lw - 3) ? thr : 0x3fff);  // (g_last <= PRE_GROUPS - 1)
+        T0.y = (short)((rg0 <= g_last && pr < PRE_PAIRS - 1 && gx + 1 >= 3 && gx + 1 < lw - 3) ? thr : 0x3fff);
         const int p00 = (rg * PRE_ITERS + 3) * FT_PITCH + col;
         const uint8_t *c = &tile[p00];
         const int sh = (col - 4) & 3;  // 0 or 2
@@ -436,7 +490,9 @@ __global__ __launch_bounds__(256) void k_fast_nms(const Geo *__restrict__ geo_p,
     //    rows is read (two aligned dwords, one LDS instruction) and reduced ONCE - 3 permutes + 2 packed max - and an output costs two
     //    more packed max (round 5; rows 8 apart, every row of every 3x3 window fetched by itself: 114 -> 86 vector, 40 -> 10 LDS
     //    instructions per thread).  keep <=> own score > every neighbour (a zero score never is).  Keep flags -> one compaction per wavefront.
-    {
+    //    A wavefront holds two values of rr = 2 NR consecutive tile rows: in a bottom tile the wavefronts whose rows all lie past row_hi have
+    //    nothing to keep and skip the step.
+    if (!fast_nms_wave_idle(wave, row_hi)) {
         const int c = 4 + 2 * (tid & 31), rr = tid >> 5;
         uint32_t kb = 0;
         constexpr int NR = FT_H / 8;
@@ -515,4 +571,41 @@ extern "C" void afv_launch_fast_nms(const Geo *geo, int total_tiles, const Frame
     const int total = total_tiles * nframes;
     dim3 grid((total + 7) / 8 * 8);
     hipLaunchKernelGGL(k_fast_nms, grid, dim3(256), 0, stream, geo, *src0, pyr, cand_packed, cand_count, total, frame_base);
+}
+
+// host-only (no device, no context): what k_fast_nms decides for every tile of a frame of the given geometry, from the expressions the kernel
+// itself uses (fast_tile_rect, fast_tile_empty, fast_row_hi, ...) and the kernel's own decoding of the flat tile index.  Per tile 12 ints:
+// level, tile column, tile row, the reportable rectangle x0, y0, x1, y1 in tile coordinates, 1 if the workgroup leaves at once, row_hi,
+// g_last, bit w set if wavefront w skips step 2a, bit w set if wavefront w skips step 3.  level_wh: w, h per level.
+extern "C" int afv_debug_fast_tiles(const afv_orb_params *params, int width, int height, int32_t *tiles, int tiles_cap, int32_t *level_wh,
+                                    int *n_out) {
+    if (!params || !tiles || !level_wh || !n_out) return AFV_EINVAL;
+    Geo geo;
+    const int rc = afv_build_geometry(*params, width, height, 1, geo);
+    if (rc) return rc;
+    if (geo.total_tiles * 12 > tiles_cap) return AFV_ECAPACITY;
+    for (int l = 0; l < AFV_MAX_LEVELS; ++l) {
+        level_wh[2 * l] = l < geo.nlevels ? geo.lv[l].w : 0;
+        level_wh[2 * l + 1] = l < geo.nlevels ? geo.lv[l].h : 0;
+    }
+    for (int tile_id = 0; tile_id < geo.total_tiles; ++tile_id) {
+        int l = 0;
+        for (int i = 1; i < AFV_MAX_LEVELS; ++i)
+            if (i < geo.nlevels && tile_id >= geo.lv[i].tile_base) l = i;
+        const LevelGeo &L = geo.lv[l];
+        const int t = tile_id - L.tile_base;
+        const int tyi = (int)afv_udiv((uint32_t)t, L.dv_tiles_x), txi = t - tyi * L.tiles_x;
+        const FastTileRect r = fast_tile_rect(L.w, L.h, txi, tyi);
+        const int row_hi = fast_row_hi(L.h, tyi), g_last = fast_last_row_group(row_hi);
+        int pre_idle = 0, nms_idle = 0;
+        for (int w = 0; w < 256 / AFV_WAVE; ++w) {
+            if (!(fast_pre_wave_first_group(w) <= g_last)) pre_idle |= 1 << w;
+            if (fast_nms_wave_idle(w, row_hi)) nms_idle |= 1 << w;
+        }
+        int32_t *o = tiles + 12 * tile_id;
+        o[0] = l, o[1] = txi, o[2] = tyi, o[3] = r.x0, o[4] = r.y0, o[5] = r.x1, o[6] = r.y1;
+        o[7] = fast_tile_empty(r) ? 1 : 0, o[8] = row_hi, o[9] = g_last, o[10] = pre_idle, o[11] = nms_idle;
+    }
+    *n_out = geo.total_tiles;
+    return AFV_OK;
 }

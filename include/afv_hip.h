@@ -727,6 +727,13 @@ int afv_debug_blur_level(afv_ctx *ctx, int frame, int level, uint8_t *out);
 int afv_debug_pyramid_plan(const afv_orb_params *params, int width, int height, int tile_w, int tile_h, int16_t *regions,
                            int regions_cap, int32_t *info, int16_t *tables, int tables_cap);
 
+/* host-only (no device, no context): what the FAST kernel decides per tile of a frame of the given geometry - per 64 x 32 tile, in the order
+ * of the flat tile index, 12 ints: level, tile column, tile row, the rectangle of pixels FAST can report (3 <= x < w - 3, 3 <= y < h - 3) in tile
+ * coordinates x0, y0, x1, y1 (exclusive ends), 1 if the tile holds none and its workgroup leaves at once, the last score row that matters, the
+ * last pre-test row group, the wavefronts (bit mask) that skip the pre-test, the wavefronts that skip the NMS.  level_wh[2 * AFV_MAX_LEVELS]:
+ * w, h per level.  tests/test_fast_ragged_cpu.py holds these decisions to rectangles it computes itself. */
+int afv_debug_fast_tiles(const afv_orb_params *params, int width, int height, int32_t *tiles, int tiles_cap, int32_t *level_wh, int *n_out);
+
 #ifdef __cplusplus
 }
 #endif
