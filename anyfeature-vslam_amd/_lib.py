@@ -89,7 +89,12 @@ class ProjJob(C.Structure):
 class FrameParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_x", C.c_float), ("min_y", C.c_float), ("max_x", C.c_float), ("max_y", C.c_float),
                 ("grid_cols", C.c_int32), ("grid_rows", C.c_int32), ("distorted", C.c_int32), ("cap", C.c_int32), ("desc_bytes", C.c_int32),
-                ("float_dim", C.c_int32)]
+                ("float_dim", C.c_int32), ("keep_pyramid", C.c_int32)]
+
+
+class StereoParams(C.Structure):
+    """afv_stereo_params: the scalars of Frame::ComputeStereoMatches"""
+    _fields_ = [("struct_size", C.c_uint32), ("mbf", C.c_float), ("fx", C.c_float), ("th_high", C.c_float), ("th_low", C.c_float)]
 
 
 class ProjQueries(C.Structure):
@@ -198,6 +203,12 @@ SYMBOLS = {
     "afv_frame_match_projection": (_i, [_vp, C.POINTER(ProjQueries), _vp, _vp]),
     "afv_frame_match_fuse": (_i, [_vp, C.POINTER(ProjQueries), _i, _vp, _vp]),
     "afv_frame_match_initialization": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _i, _vp, _vp]),
+    "afv_pyramid_level_sizes": (_i, [_vp, _i, _i, C.POINTER(C.c_int32), _vp, _vp]),
+    "afv_frame_set_pyramid": (_i, [_vp, _i, _i, C.POINTER(_vp), _i]),
+    "afv_frame_get_pyramid_level": (_i, [_vp, _i, _vp]),
+    "afv_frame_stereo_match": (_i, [_vp, _vp, C.POINTER(StereoParams), C.POINTER(C.c_int32)]),
+    "afv_frame_set_depth": (_i, [_vp, _vp, _i, _i, _i, _f]),
+    "afv_frame_get_stereo": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "afv_table_set_from_frame": (_i, [_vp, _i, _vp]),
     "afv_table_match_bow_frame_h": (_i, [_vp, _vp, _i, _vp, _f, _f, _i, _vp, _vp]),
     "afv_set_projection_resolve": (_i, [_vp, _i]),

@@ -16,8 +16,10 @@
 //                                   include/FeatureMatcher.h:47-82, src/FeatureMatcher.cc:73-154, 287-397, 399-557, 794-1064,
 //                                   1066-1287, 1291-1506 — the projection geometry stays with the caller, as in the reference
 // The reference binary is vslamlab_anyfeature_mono; the stereo branches of the matchers (FeatureMatcher.cc:114-119, 705-747, 880-894,
-// 1367-1372) are served through the optional mvuRight members below, mvImagePyramid through ImagePyramid().  What stays with the
-// reference is Frame::ComputeStereoMatches itself (Frame.cc:465-645), which is Frame code, not plugin code.
+// 1367-1372) are served through the optional mvuRight members below, mvImagePyramid through ImagePyramid().  Frame::ComputeStereoMatches
+// (Frame.cc:465-645) and Frame::ComputeStereoFromRGBD (:648-669) run on the device between resident frames that kept their pyramids:
+// DeviceFrame::ComputeStereoMatches / ComputeStereoFromRGBD below (semantics and the three deviations from the reference's routine:
+// include/afv_hip.h, "stereo and RGB-D frames"; parity with a build of the reference is unpinned).
 // Error behaviour follows the reference: no exceptions cross the boundary; an empty image leaves the outputs
 // untouched (ORBextractor.cc:570-571); an unrecoverable device error terminates (cf. Feature_sift128.cpp:61).
 #pragma once
@@ -253,13 +255,16 @@ class FeatureExtractor_orb32_hip {
 class DeviceFrame {
   public:
     // mnMinX .. mnMaxY: Frame::ComputeImageBounds (Frame.cc:435-466); distorted: mDistCoef.at<float>(0) != 0 (Frame.cc:405)
-    DeviceFrame(afv_ctx *ctx_, float mnMinX, float mnMinY, float mnMaxX, float mnMaxY, bool distorted = false, int grid_cols = 64, int grid_rows = 48)
+    // keep_pyramid: the stereo constructor's frames (Frame.cc:76-80) - Extract() leaves the pyramid levels with the frame for ComputeStereoMatches
+    DeviceFrame(afv_ctx *ctx_, float mnMinX, float mnMinY, float mnMaxX, float mnMaxY, bool distorted = false, int grid_cols = 64, int grid_rows = 48,
+                bool keep_pyramid = false)
         : ctx(ctx_) {
         afv_frame_params p{};
         p.struct_size = sizeof(p);
         p.min_x = mnMinX; p.min_y = mnMinY; p.max_x = mnMaxX; p.max_y = mnMaxY;
         p.grid_cols = grid_cols; p.grid_rows = grid_rows;
         p.distorted = distorted ? 1 : 0;
+        p.keep_pyramid = keep_pyramid ? 1 : 0;
         const int rc = afv_frame_create(ctx, &p, &f);
         if (rc != AFV_OK) fatal("afv_frame_create", rc, ctx);
     }
@@ -302,6 +307,32 @@ class DeviceFrame {
         }
         const int rc = afv_frame_set_undistorted(f, x.data(), y.data());
         if (rc != AFV_OK) fatal("afv_frame_set_undistorted", rc, ctx);
+    }
+    // Frame::ComputeStereoMatches (Frame.cc:465-645): this frame is the left eye, `right` the right one (both keep_pyramid, one context).
+    // mvuRight / mvDepth are filled as the reference's members and stay on the device for the projection searches and the keyframe table.
+    // Returns the number of features with mvuRight >= 0.
+    int ComputeStereoMatches(DeviceFrame &right, float mbf, float fx, float th_high, float th_low, std::vector<float> &mvuRight, std::vector<float> &mvDepth) {
+        afv_stereo_params p{};
+        p.struct_size = sizeof(p);
+        p.mbf = mbf; p.fx = fx; p.th_high = th_high; p.th_low = th_low;
+        int32_t n_stereo = 0;
+        int rc = afv_frame_stereo_match(f, right.f, &p, &n_stereo);
+        if (rc != AFV_OK) fatal("afv_frame_stereo_match", rc, ctx);
+        GetStereo(mvuRight, mvDepth);
+        return n_stereo;
+    }
+    // Frame::ComputeStereoFromRGBD (Frame.cc:648-669): imDepth as rows of floats (cv::Mat CV_32F: ptr<float>(0), cols, rows, step)
+    void ComputeStereoFromRGBD(const float *imDepth, int cols, int rows, size_t step_bytes, float mbf, std::vector<float> &mvuRight, std::vector<float> &mvDepth) {
+        const int rc = afv_frame_set_depth(f, imDepth, cols, rows, (int)step_bytes, mbf);
+        if (rc != AFV_OK) fatal("afv_frame_set_depth", rc, ctx);
+        GetStereo(mvuRight, mvDepth);
+    }
+    void GetStereo(std::vector<float> &mvuRight, std::vector<float> &mvDepth) {
+        const size_t n = (size_t)std::max(N(), 0);
+        mvuRight.assign(n, -1.0f);
+        mvDepth.assign(n, -1.0f);
+        const int rc = afv_frame_get_stereo(f, mvuRight.data(), mvDepth.data(), nullptr, nullptr);
+        if (rc != AFV_OK) fatal("afv_frame_get_stereo", rc, ctx);
     }
     int N() const { return afv_frame_count(f); }
     afv_frame *handle() { return f; }

@@ -828,6 +828,10 @@ static int extract_one(afv_ctx *c, const uint8_t *gray, int width, int height, i
     if (frame) {
         const int rc_grid = afv_frame_after_extract(frame, s);  // (a failed launch must not leave has_grid set over the zeroed memset: ADVICE r5)
         if (rc_grid) return rc_grid;
+        if (frame->p.keep_pyramid) {  // the levels stay with the frame: device copies behind the kernels, read by later work on this stream
+            const int rc_pyr = afv_frame_keep_pyramid(frame, src, s);
+            if (rc_pyr) return rc_pyr;
+        }
     }
     HIPCHK(c, hipGetLastError());
     trace.mark();  // kernel launches

@@ -23,6 +23,7 @@ static void frame_free(afv_frame *f) {
     }
     if (f->c) (void)hipSetDevice(f->c->device);
     if (f->d_block) (void)hipFree(f->d_block);
+    if (f->d_pyr) (void)hipFree(f->d_pyr);
     delete f;
 }
 
@@ -78,6 +79,7 @@ extern "C" int afv_frame_create(afv_ctx *c, const afv_frame_params *params, afv_
         const size_t o_leaf = take((size_t)cap * 4), o_nid = take((size_t)cap * 4), o_seg = take((size_t)cap * 4), o_oct = take((size_t)cap);
         const size_t o_dense = take((size_t)cap * 4);
         const size_t o_bword = take((size_t)cap * 4), o_bval = take((size_t)cap * 8);
+        const size_t o_depth = take((size_t)cap * 4), o_sad = take((size_t)cap * 4), o_bestr = take((size_t)cap * 4);  // afv_stereo.hip
         hipError_t e = hipMalloc(reinterpret_cast<void **>(&f->d_block), off);
         if (e == hipSuccess) e = hipMemsetAsync(f->d_block, 0, off, c->stream);
         if (e != hipSuccess) {
@@ -102,6 +104,10 @@ extern "C" int afv_frame_create(afv_ctx *c, const afv_frame_params *params, afv_
         f->d_bow_word = reinterpret_cast<int32_t *>(B + o_bword);
         f->d_bow_value = reinterpret_cast<double *>(B + o_bval);
         f->d_bow_n = f->d_n + 2;
+        f->d_nstereo = f->d_n + 3;
+        f->d_depth = reinterpret_cast<float *>(B + o_depth);
+        f->d_sad = reinterpret_cast<int *>(B + o_sad);
+        f->d_best_r = reinterpret_cast<int *>(B + o_bestr);
         try {
             c->frames.push_back(f);
             std::lock_guard<std::mutex> lk(g_frames_mutex);
@@ -165,6 +171,9 @@ int afv_frame_after_extract(afv_frame *f, hipStream_t s) {
     f->has_fv = false;
     f->has_bow = false;
     f->has_grid = false;
+    f->has_depth = false;
+    f->has_stereo = false;
+    f->has_pyramid = false;  // (afv_frame_keep_pyramid follows for a keep_pyramid frame)
     const int rc = frame_launch_grid(f, true, !f->p.distorted, true, true, !f->p.distorted, true, s);
     if (rc) return rc;
     f->has_grid = !f->p.distorted;
@@ -210,6 +219,8 @@ extern "C" int afv_frame_set_features(afv_frame *f, const afv_keypoint *kps, con
         f->has_fv = false;
         f->has_bow = false;
         f->has_grid = false;
+        f->has_depth = false;
+        f->has_stereo = false;
         const int rc = frame_launch_grid(f, true, !f->p.distorted, size == nullptr, u_right == nullptr, !f->p.distorted, false, s);
         if (rc) return rc;
         f->has_grid = !f->p.distorted;

@@ -95,6 +95,24 @@ extern "C" int afv_launch_match_l2_pairs(const float *desc, const int *nset, int
 extern "C" void afv_launch_match_init(const DevProjJob *jobs, int njobs, int max_nq, size_t wg_lds, const DevProjJob *one, int *ticket,
                                       hipStream_t stream);
 
+// ---- k_stereo.hip: Frame::ComputeStereoMatches / ComputeStereoFromRGBD ----
+struct DevStereoJob {
+    const afv_keypoint *kps_l, *kps_r;   // mvKeys / mvKeysRight (distorted)
+    const float *size_l, *size_r;        // keyPtsSize
+    const uint32_t *desc_l, *desc_r;     // rows of `words` dwords (binary, zero padded) or `fdim` floats
+    int n_l, n_r, words, fdim;
+    float th_high, th_orb, mbf, max_d;
+    int n_rows, nlevels;
+    int lw[AFV_MAX_LEVELS], lh[AFV_MAX_LEVELS];
+    const uint8_t *pyr_l[AFV_MAX_LEVELS], *pyr_r[AFV_MAX_LEVELS];  // level l: lw[l] x lh[l] bytes, tightly packed
+    float *u_right, *depth;              // [n_l] outputs
+    int *sad, *best_r, *n_stereo;
+};
+extern "C" void afv_launch_stereo_match(const DevStereoJob *job, hipStream_t stream);
+extern "C" void afv_launch_stereo_median(float *u_right, float *depth, const int *sad, int n, int *n_stereo, hipStream_t stream);
+extern "C" void afv_launch_stereo_rgbd(const afv_keypoint *kps, const float *x_un, int n, const float *img, int w, int h, float mbf, float *u_right,
+                                       float *depth, hipStream_t stream);
+
 extern "C" void afv_launch_bow_transform(const DevVocab *v, const uint32_t *desc, int n, int levelsup, int *leaf_node,
                                          int *node_at_level, int *rank_at_level, hipStream_t stream);
 extern "C" int afv_launch_bow_transform_f32(const DevVocab *v, const float *desc, int n, int dim, int levelsup, int *leaf_node, int *node_at_level,
@@ -151,6 +169,15 @@ struct afv_frame {
     int *d_bow_n = nullptr;
     bool has_bow = false;
     int bow_n = 0;
+    // stereo / RGB-D (afv_stereo.hip): mvDepth next to d_ur, the test outputs of the stereo search, the kept pyramid
+    float *d_depth = nullptr;        // [cap]
+    int *d_sad = nullptr, *d_best_r = nullptr, *d_nstereo = nullptr;  // [cap], [cap], one int
+    bool has_depth = false;          // d_depth holds values (else mvDepth reads -1)
+    bool has_stereo = false;         // d_sad / d_best_r hold the last afv_frame_stereo_match
+    uint8_t *d_pyr = nullptr;        // the frame's own pyramid: level l tightly packed at pyr_off[l] (an allocation of its own, made on first use)
+    size_t pyr_bytes = 0, pyr_off[AFV_MAX_LEVELS]{};
+    int pyr_levels = 0, pyr_w[AFV_MAX_LEVELS]{}, pyr_h[AFV_MAX_LEVELS]{};
+    bool has_pyramid = false;
 };
 
 #define AFV_MAX_SIDE 8192
@@ -544,6 +571,8 @@ int afv_check_resolve_guard(afv_ctx *c, const int32_t *nmatches, int n);
 void afv_table_release_all(afv_ctx *c);  // afv_destroy: tables / communicators still alive die with their context
 void afv_frame_release_all(afv_ctx *c);  // ... and so do its frames
 int afv_frame_after_extract(afv_frame *f, hipStream_t s);  // afv_frame.hip: k_frame_grid behind the describe kernel of afv_frame_extract
+// afv_stereo.hip: a keep_pyramid frame takes device copies of the levels of frame slot 0 of the extraction that just ran on stream s
+int afv_frame_keep_pyramid(afv_frame *f, const FrameSrc &src, hipStream_t s);
 int afv_extract_into_frame(afv_ctx *c, afv_frame *f, const uint8_t *gray, int width, int height, int stride_bytes, afv_keypoint *kps,
                            uint8_t *desc32, int cap, int *n_out);  // afv_extract.hip: afv_orb_extract with the frame as second destination
 // what afv_create (afv_api.hip) needs from the extractor's geometry (afv_extract.hip): level sizes, quotas and buffer layout of `max_batch`

@@ -6,6 +6,8 @@ In the reference a Frame is built once - ExtractFeatures (Frame.cc:242-259), Und
 vectors the reference's members hold (mvKeys, mDescriptors, keyPtsSigma2 / Inf / Size) AND leaves keypoints, descriptors, the
 per-feature scale data and the 64 x 48 grid in HBM; SearchByProjection / Fuse / SearchForInitialization / ComputeBoW /
 SearchByBoW(KF, F) / the promotion to a keyframe then run against them without uploading the frame again.
+Stereo and RGB-D frames: ComputeStereoMatches (Frame.cc:465-645) between two resident frames that kept their pyramids, and
+ComputeStereoFromRGBD (:648-669), fill mvuRight / mvDepth on the device, where the projection searches and the keyframe table read them.
 Plumbing only: every method is one C-ABI call.
 """
 import ctypes as C
@@ -20,10 +22,11 @@ FRAME_GRID_COLS, FRAME_GRID_ROWS = 64, 48  # Frame.h:40-41
 
 class Frame:
     def __init__(self, ctx, min_x=0.0, min_y=0.0, max_x=640.0, max_y=480.0, grid_cols=FRAME_GRID_COLS, grid_rows=FRAME_GRID_ROWS,
-                 distorted=False, cap=0, desc_bytes=32, float_dim=0):
+                 distorted=False, cap=0, desc_bytes=32, float_dim=0, keep_pyramid=False):
         """desc_bytes: size of one binary descriptor (32 ORB, 61 AKAZE, 48 BRISK ...; <= 64); float_dim > 0: float descriptors of that many
         floats instead (SIFT128, SURF64, KAZE64 ...: L2^2 distances) - the reference's matchers dispatch on the descriptor type
-        (FeatureMatcher.cc:1508-1531); frames that are not 32-byte binary are filled with set_features"""
+        (FeatureMatcher.cc:1508-1531); frames that are not 32-byte binary are filled with set_features.
+        keep_pyramid: extract leaves the detector's unblurred pyramid levels with the frame (ComputeStereoMatches reads mvImagePyramid)"""
         self.ctx, self.lib = ctx, ctx.lib
         self.float_dim = int(float_dim)
         self.desc_bytes = 4 * self.float_dim if self.float_dim else int(desc_bytes)
@@ -32,6 +35,7 @@ class Frame:
         p.grid_cols, p.grid_rows, p.distorted, p.cap = int(grid_cols), int(grid_rows), int(bool(distorted)), int(cap)
         p.desc_bytes = int(desc_bytes)
         p.float_dim = self.float_dim
+        p.keep_pyramid = int(bool(keep_pyramid))
         self.params = p
         h = C.c_void_p()
         ctx.check(self.lib.afv_frame_create(ctx.handle, C.byref(p), C.byref(h)), "afv_frame_create")
@@ -62,6 +66,7 @@ class Frame:
         Context.extract, or N when host_outputs is False (the device copy only)."""
         gray = np.ascontiguousarray(gray, np.uint8)
         h, w = gray.shape
+        self._pyr_sizes = self._level_sizes(w, h) if self.params.keep_pyramid else None
         if not host_outputs:
             self.ctx.check(self.lib.afv_frame_extract(self.handle, ptr(gray), w, h, gray.strides[0], None, None, 0, None), "afv_frame_extract")
             return self.N
@@ -88,6 +93,77 @@ class Frame:
         """mvKeysUn of a `distorted` frame (cv::undistortPoints is the caller's, Frame.cc:403-433); builds the grid"""
         x, y = np.ascontiguousarray(x, np.float32), np.ascontiguousarray(y, np.float32)
         self.ctx.check(self.lib.afv_frame_set_undistorted(self.handle, ptr(x), ptr(y)), "afv_frame_set_undistorted")
+
+    # ---- stereo / RGB-D ----
+    def _level_sizes(self, w, h):
+        """[(lw, lh)] of the context's pyramid for a w x h image"""
+        n = C.c_int32(0)
+        lw = (C.c_int32 * _lib.MAX_LEVELS)(); lh = (C.c_int32 * _lib.MAX_LEVELS)()
+        self.ctx.check(self.lib.afv_pyramid_level_sizes(self.ctx.handle, int(w), int(h), C.byref(n), lw, lh), "afv_pyramid_level_sizes")
+        return [(lw[l], lh[l]) for l in range(n.value)]
+
+    def set_pyramid(self, levels):
+        """the pyramid of a frame filled with set_features: uint8 [h, w] levels, level 0 the image; the sizes must be the context's
+        geometry for that image size (the C side reads exactly those sizes, so they are checked here first)"""
+        lv = [np.ascontiguousarray(a, np.uint8) for a in levels]
+        if not lv or any(a.ndim != 2 for a in lv):
+            raise ValueError("levels: a list of 2-D uint8 images")
+        h, w = lv[0].shape
+        sizes = self._level_sizes(w, h)
+        if len(sizes) != len(lv) or any(a.shape != (lh, lw) for a, (lw, lh) in zip(lv, sizes)):
+            raise _lib.AfvError(_lib.EINVAL, "set_pyramid: the levels are not the context's geometry for %d x %d: %r" % (w, h, sizes))
+        arr = (C.c_void_p * len(lv))(*[a.ctypes.data for a in lv])
+        self.ctx.check(self.lib.afv_frame_set_pyramid(self.handle, w, h, arr, len(lv)), "afv_frame_set_pyramid")
+        self._pyr_sizes = sizes
+
+    def pyramid(self):
+        """the levels the frame holds (keep_pyramid / set_pyramid), back on the host"""
+        sizes = getattr(self, "_pyr_sizes", None)
+        if sizes is None:
+            raise _lib.AfvError(_lib.EINVAL, "the frame holds no pyramid")
+        out = []
+        for l, (lw, lh) in enumerate(sizes):
+            a = np.zeros((lh, lw), np.uint8)
+            self.ctx.check(self.lib.afv_frame_get_pyramid_level(self.handle, l, ptr(a)), "afv_frame_get_pyramid_level")
+            out.append(a)
+        return out
+
+    def ComputeStereoMatches(self, right, mbf, fx, th_high=None, th_low=None):
+        """Frame::ComputeStereoMatches (Frame.cc:465-645) of this (left) frame against `right`: fills mvuRight / mvDepth on the device and
+        returns the number of features with mvuRight >= 0.  None thresholds = FeatureMatcher.TH_HIGH / TH_LOW.  Semantics:
+        tests/_stereo_ref.py (deviations A, B, C of include/afv_hip.h; parity with a build of the reference is unpinned)"""
+        from .matcher import FeatureMatcher
+        p = _lib.sized(_lib.StereoParams)
+        p.mbf, p.fx = float(mbf), float(fx)
+        p.th_high = float(FeatureMatcher.TH_HIGH if th_high is None else th_high)
+        p.th_low = float(FeatureMatcher.TH_LOW if th_low is None else th_low)
+        n = C.c_int32(0)
+        self.ctx.check(self.lib.afv_frame_stereo_match(self.handle, right.handle, C.byref(p), C.byref(n)), "afv_frame_stereo_match")
+        return int(n.value)
+
+    def ComputeStereoFromRGBD(self, depth, mbf):
+        """Frame::ComputeStereoFromRGBD (Frame.cc:648-669): depth = float32 [h, w] image"""
+        d = np.asarray(depth, np.float32)
+        if d.ndim != 2 or d.strides[1] != 4 or d.strides[0] < 4 * d.shape[1]:   # rows of floats at any row stride are taken as they lie
+            d = np.ascontiguousarray(d)
+        h, w = d.shape
+        self.ctx.check(self.lib.afv_frame_set_depth(self.handle, ptr(d), w, h, d.strides[0], float(mbf)), "afv_frame_set_depth")
+
+    def stereo(self):
+        """(mvuRight, mvDepth, sad, best_r): the last two are test outputs of ComputeStereoMatches (-1 where none)"""
+        n = self.N
+        ur = np.zeros(max(n, 1), np.float32); dp = np.zeros(max(n, 1), np.float32)
+        sad = np.zeros(max(n, 1), np.int32); br = np.zeros(max(n, 1), np.int32)
+        self.ctx.check(self.lib.afv_frame_get_stereo(self.handle, ptr(ur), ptr(dp), ptr(sad), ptr(br)), "afv_frame_get_stereo")
+        return ur[:n], dp[:n], sad[:n], br[:n]
+
+    @property
+    def mvuRight(self):
+        return self.stereo()[0]
+
+    @property
+    def mvDepth(self):
+        return self.stereo()[1]
 
     def grid(self):
         """(cell_ptr[cols * rows + 1], cell_idx[...]) of the device-built grid, cell = ix * rows + iy"""

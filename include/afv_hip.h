@@ -490,6 +490,10 @@ typedef struct {
                                          desc_bytes = 4 * float_dim).  It meets a keyframe table of float rows of the same float_dim
                                          (afv_table_create_f32) in afv_table_set_from_frame / afv_table_match_bow_frame_h / qref_table;
                                          a binary table or another float_dim answers AFV_EUNSUPPORTED */
+    int32_t keep_pyramid;             /* (appended; callers of the earlier layouts read 0) 1: afv_frame_extract leaves the detector's unblurred
+                                         pyramid levels of its image with the frame (device copies out of the context's pyramid buffer,
+                                         behind the extraction on the context's stream) for afv_frame_stereo_match; 0: the frame of
+                                         before, nothing is copied */
 } afv_frame_params;
 int afv_frame_create(afv_ctx *ctx, const afv_frame_params *params, afv_frame **out);
 void afv_frame_destroy(afv_frame *f);
@@ -560,6 +564,43 @@ int afv_table_set_from_frame(afv_table *t, int slot, afv_frame *f);
  * of TrackReferenceKeyFrame (Tracking.cc:626-629, one slot) and of Relocalization (:1162-1182, the candidates). */
 int afv_table_match_bow_frame_h(afv_table *t, const int32_t *slots, int nslots, afv_frame *f, float th_low, float nnratio,
                                 int check_orientation, int32_t *match_f, int32_t *nmatches);
+/* ---- stereo and RGB-D frames: mvuRight / mvDepth made on the device ----
+ * Frame::ComputeStereoMatches (src/Frame.cc:465-645) and Frame::ComputeStereoFromRGBD (:648-669).  The semantics are those of the plain
+ * restatement tests/_stereo_ref.py, which the device is held to bit for bit; it follows the reference's routine (ORB-SLAM2's, which the
+ * reference marks "has not been modified yet to work with AnyFeature-VSLAM") with three deviations: (A) the row band of a right keypoint is
+ * 2 x ITS OWN keyPtsSize (the reference reads the left frame's size at the right index, :491); (B) rows outside [0, nRows) are dropped
+ * (:496-497 index unchecked); (C) a keypoint whose 11 x 11 window or 11 x 21 search strip leaves its pyramid level, or whose octave is no
+ * level, is skipped (the reference would assert inside OpenCV).  Caller data cannot take the search outside its arrays: a scaled
+ * coordinate round(u / size), round(v / size), round(uR0 / size) that is not finite or beyond +-2^20 (a zero, denormal or NaN keyPtsSize,
+ * a huge coordinate) skips the keypoint like (C); a left keypoint whose y is NaN or outside (-1, nRows) has no row; the ends of a right
+ * keypoint's row band are clamped to +-2^30 and a NaN end makes the band empty.  Parity with a real build is unpinned: none exists.
+ * New symbols and appended fields only: AFV_ABI_VERSION stays 6. */
+/* host-only: the level sizes of the context's pyramid for a width x height image (width / height within the context's maxima, levels of
+ * at least 32 px; else AFV_EINVAL): *nlevels, lw[AFV_MAX_LEVELS], lh[AFV_MAX_LEVELS] */
+int afv_pyramid_level_sizes(afv_ctx *ctx, int width, int height, int32_t *nlevels, int32_t *lw, int32_t *lh);
+/* the pyramid of a frame filled with afv_frame_set_features (any extractor's frames; tests): nlevels host images, level l tightly packed
+ * lw[l] x lh[l] bytes, where nlevels / lw / lh are the context's geometry for a width x height image (afv_pyramid_level_sizes; another
+ * level count or a NULL level: AFV_EINVAL).  Synchronous. */
+int afv_frame_set_pyramid(afv_frame *f, int width, int height, const uint8_t *const *levels, int nlevels);
+/* a kept pyramid level back on the host (tightly packed lw x lh; AFV_EINVAL without a pyramid) */
+int afv_frame_get_pyramid_level(afv_frame *f, int level, uint8_t *out);
+typedef struct {
+    uint32_t struct_size;   /* sizeof(afv_stereo_params) */
+    float mbf, fx;          /* Frame::mbf, fx: mb = mbf / fx, maxD = mbf / mb, minD = 0 (:501-503) */
+    float th_high, th_low;  /* FeatureMatcher::TH_HIGH / TH_LOW: the search starts at th_high, thOrbDist = (th_high + th_low) / 2 */
+} afv_stereo_params;
+/* ComputeStereoMatches of `left` against `right`: both on one context (else AFV_EINVAL), with features and a pyramid each (else
+ * AFV_EINVAL), of the same descriptor kind and size and pyramids of the same geometry (else AFV_EUNSUPPORTED).  The keypoints are the
+ * frames' mvKeys (the distorted points), sizes their keyPtsSize.  Fills left's mvuRight / mvDepth planes (-1 where no match), which
+ * afv_frame_match_projection / _fuse / afv_table_set_from_frame then read with no further call; *n_stereo (may be NULL) = features with
+ * mvuRight >= 0.  Two launches (k_stereo_match, k_stereo_median) and a 4-byte copy of the count on the context's stream, one wait. */
+int afv_frame_stereo_match(afv_frame *left, afv_frame *right, const afv_stereo_params *params, int32_t *n_stereo);
+/* ComputeStereoFromRGBD: depth = a width x height image of floats (host, stride_bytes per row), read at the truncated distorted keypoint;
+ * d > 0: mvDepth = d, mvuRight = mvKeysUn.x - mbf / d; else (and for a keypoint outside the image) both -1. */
+int afv_frame_set_depth(afv_frame *f, const float *depth, int width, int height, int stride_bytes, float mbf);
+/* mvuRight[n], mvDepth[n] and, after afv_frame_stereo_match, for tests: sad[n] = the SAD of an accepted pair before the median filter,
+ * best_r[n] = the right index the descriptor search chose; -1 where none.  Any pointer may be NULL. */
+int afv_frame_get_stereo(afv_frame *f, float *u_right, float *depth, int32_t *sad, int32_t *best_r);
 /* engine of the ordered phase of the projection searches / SearchForInitialization (identical results):
  *   1: one fixed point over all live queries of a job on a 1024-thread workgroup (round 5)   0: the ordered walk of rounds 1-4 on one
  *   wavefront   2 (default): 1 whenever the job's tables fit the workgroup's LDS, else 0   3: as 1, but ranking and ordered phase as two
