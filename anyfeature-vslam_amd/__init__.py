@@ -9,6 +9,7 @@ Layout:
   extractor.py   FeatureExtractorSettings / FeatureExtractor_orb32 mirror (reference: Feature_orb32.{h,cpp})
   matcher.py     FeatureMatcher mirror (reference: FeatureMatcher.{h,cc})
   frame.py       the device-resident Frame (reference: Frame.{h,cc} as far as the front end reads it)
+  points.py      the device-resident map-point store (reference: MapPoint.{h,cc} as far as the projection searches read it)
   database.py    KeyFrameDatabase mirror over the keyframe table (reference: KeyFrameDatabase.{h,cc}, LoopClosing.cc:137-157)
   synth.py       bit-reproducible synthetic inputs
 """
@@ -17,6 +18,7 @@ from .extractor import (CovarianceMethod, FeatureExtractorSettings, FeatureExtra
                         KP_DTYPE)
 from .vocabulary import Vocabulary  # noqa: F401
 from .frame import Frame  # noqa: F401
+from .points import MapPoints  # noqa: F401
 from . import akaze, table  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
 from .akaze import AkazeContext  # noqa: F401

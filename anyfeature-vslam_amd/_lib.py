@@ -105,6 +105,26 @@ class ProjQueries(C.Structure):
                 ("qref_table", C.c_void_p), ("qref_slot", C.c_void_p), ("qref_idx", C.c_void_p)]
 
 
+class PointSearch(C.Structure):
+    """afv_point_search: a projection search through the ids of resident map points"""
+    _fields_ = [("struct_size", C.c_uint32), ("flavour", C.c_int32), ("points", C.c_void_p), ("ids", C.c_void_p), ("nq", C.c_int32),
+                ("radius_th", C.c_float), ("radius_scale", C.c_float), ("viewing_cos_limit", C.c_float), ("qframe", C.c_void_p),
+                ("qangle", C.c_void_p), ("occupied", C.c_void_p), ("th_high", C.c_float), ("nnratio", C.c_float),
+                ("check_orientation", C.c_int32)]
+
+
+class PointProjection(C.Structure):
+    """afv_point_projection: host outputs of afv_frame_project_points"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_in_view", C.c_int32), ("in_view", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p),
+                ("ur", C.c_void_p), ("size", C.c_void_p), ("sigma", C.c_void_p), ("view_cos", C.c_void_p), ("r", C.c_void_p),
+                ("qmin", C.c_void_p), ("qmax", C.c_void_p), ("er", C.c_void_p)]
+
+
+PT_FRUSTUM, PT_LASTFRAME, PT_RELOC, PT_FUSE = 0, 1, 2, 3
+POINTS_MAX_CAPACITY = 1 << 22
+PTF_SET, PTF_BAD, PTF_OBSERVED = 1, 2, 4   # afv_points_get's flag bits
+
+
 class BowQuery(C.Structure):
     """afv_bow_query: the query BowVector of afv_table_score_bow - a table slot, a resident frame or host arrays"""
     _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("slot", C.c_int32), ("n", C.c_int32), ("frame", C.c_void_p),
@@ -212,6 +232,17 @@ SYMBOLS = {
     "afv_table_set_from_frame": (_i, [_vp, _i, _vp]),
     "afv_table_match_bow_frame_h": (_i, [_vp, _vp, _i, _vp, _f, _f, _i, _vp, _vp]),
     "afv_set_projection_resolve": (_i, [_vp, _i]),
+    "afv_points_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "afv_points_destroy": (None, [_vp]),
+    "afv_points_set": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "afv_points_set_flags": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "afv_points_set_descriptors": (_i, [_vp, _vp, _i, _vp]),
+    "afv_points_set_descriptors_from_table": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "afv_points_get": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "afv_frame_set_pose": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _f, _f]),
+    "afv_frame_search_points": (_i, [_vp, C.POINTER(PointSearch), _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "afv_frame_fuse_points": (_i, [_vp, C.POINTER(PointSearch), _i, _vp, _vp]),
+    "afv_frame_project_points": (_i, [_vp, C.POINTER(PointSearch), C.POINTER(PointProjection)]),
     "afv_vocab_set_weights": (_i, [_vp, _vp, _vp, _vp]),
     "afv_bow_vector": (_i, [_vp, _vp, _vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_frame_get_bowvec": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),

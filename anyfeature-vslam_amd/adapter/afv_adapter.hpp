@@ -248,6 +248,54 @@ class FeatureExtractor_orb32_hip {
     std::vector<float> mvScaleFactor;
 };
 
+// ---- the device-resident map points (include/afv_hip.h afv_points_*; reference object: MapPoint, src/MapPoint.cc) ----
+// One per Map.  LocalMapping writes a point where it calls SetWorldPos / UpdateNormalAndDepth / ComputeDistinctiveDescriptors / SetBadFlag
+// ("Resident map points"); a DeviceFrame with a pose then searches the points by id.  Arrays are indexed like `ids`.
+class DeviceMapPoints {
+  public:
+    DeviceMapPoints(afv_ctx *ctx_, int capacity, int desc_bytes = AFV_DESC_BYTES, int float_dim = 0) : ctx(ctx_) {
+        const int rc = afv_points_create(ctx, capacity, desc_bytes, float_dim, &p);
+        if (rc != AFV_OK) fatal("afv_points_create", rc, ctx);
+    }
+    ~DeviceMapPoints() { afv_points_destroy(p); }
+    DeviceMapPoints(const DeviceMapPoints &) = delete;
+    DeviceMapPoints &operator=(const DeviceMapPoints &) = delete;
+
+    // MapPoint::SetWorldPos: xyz = ids.size() x 3 floats
+    void SetWorldPos(const std::vector<int32_t> &ids, const float *xyz) { Set(ids, xyz, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr); }
+    // MapPoint::UpdateNormalAndDepth: normalVector (n x 3), minDistance / maxDistance (the raw members), refSize / refDistance / refSigma
+    void UpdateNormalAndDepth(const std::vector<int32_t> &ids, const float *normal, const float *minDistance, const float *maxDistance,
+                              const float *refSize, const float *refDistance, const float *refSigma) {
+        Set(ids, nullptr, normal, minDistance, maxDistance, refSize, refDistance, refSigma);
+    }
+    // any subset of the fields at once (nullptr leaves a field as it is)
+    void Set(const std::vector<int32_t> &ids, const float *xyz, const float *normal, const float *minDistance, const float *maxDistance,
+             const float *refSize, const float *refDistance, const float *refSigma) {
+        const int rc = afv_points_set(p, ids.data(), (int)ids.size(), xyz, normal, minDistance, maxDistance, refSize, refDistance, refSigma);
+        if (rc != AFV_OK) fatal("afv_points_set", rc, ctx);
+    }
+    // isBad() / NumberOfObservations() > 0 (SetBadFlag, AddObservation, EraseObservation)
+    void SetFlags(const std::vector<int32_t> &ids, const uint8_t *bad, const uint8_t *observed) {
+        const int rc = afv_points_set_flags(p, ids.data(), (int)ids.size(), bad, observed);
+        if (rc != AFV_OK) fatal("afv_points_set_flags", rc, ctx);
+    }
+    // MapPoint::ComputeDistinctiveDescriptors: the chosen rows by value ...
+    void SetDescriptors(const std::vector<int32_t> &ids, const uint8_t *rows) {
+        const int rc = afv_points_set_descriptors(p, ids.data(), (int)ids.size(), rows);
+        if (rc != AFV_OK) fatal("afv_points_set_descriptors", rc, ctx);
+    }
+    // ... or as rows (keyframe slot, feature index) of the keyframe table, copied on the device
+    void SetDescriptorsFromTable(const std::vector<int32_t> &ids, afv_table *table, const int32_t *slot, const int32_t *idx) {
+        const int rc = afv_points_set_descriptors_from_table(p, ids.data(), (int)ids.size(), table, slot, idx);
+        if (rc != AFV_OK) fatal("afv_points_set_descriptors_from_table", rc, ctx);
+    }
+    afv_points *handle() { return p; }
+
+  private:
+    afv_ctx *ctx;
+    afv_points *p = nullptr;
+};
+
 // ---- the device-resident Frame (include/afv_hip.h afv_frame_*; reference object: Frame, src/Frame.cc:171-240) ----
 // One per Frame the tracker keeps alive (currentFrame, lastFrame, the initial frame): Frame::Frame calls Extract() instead of the plain
 // operator(), and from then on SearchByProjection / Fuse / SearchForInitialization / ComputeBoW / SearchByBoW(KF, F) and the promotion to
@@ -334,11 +382,80 @@ class DeviceFrame {
         const int rc = afv_frame_get_stereo(f, mvuRight.data(), mvDepth.data(), nullptr, nullptr);
         if (rc != AFV_OK) fatal("afv_frame_get_stereo", rc, ctx);
     }
+    // ---- resident map points: the geometry in front of the projection searches runs on the device (afv_frame_search_points) ----
+    // Frame::SetPose + the intrinsics: Rcw row-major, tcw, Ow = twc as UpdatePoseMatrices computes it (Frame.cc:270-273)
+    void SetPose(const float Rcw[9], const float tcw[3], const float Ow[3], float fx, float fy, float cx, float cy, float mbf) {
+        const int rc = afv_frame_set_pose(f, Rcw, tcw, Ow, fx, fy, cx, cy, mbf);
+        if (rc != AFV_OK) fatal("afv_frame_set_pose", rc, ctx);
+    }
+    // Tracking::SearchLocalPoints (Tracking.cc:988-1028): isInFrustum of every point of `ids` and SearchByProjection(F, vpMapPoints, th)
+    // in one call.  assign[N] = index INTO ids of the point now in F.pts[i] | -1; inView[ids.size()] = mbTrackInView (IncreaseVisible)
+    int SearchLocalPoints(DeviceMapPoints &points, const std::vector<int32_t> &ids, float radiusTh, float viewingCosLimit, float thHigh, float nnratio,
+                          std::vector<int32_t> &assign, std::vector<uint8_t> &inView, const uint8_t *occupied = nullptr) {
+        afv_point_search s = PointSearch(points, ids, AFV_PT_FRUSTUM, radiusTh, thHigh, nnratio, false, occupied);
+        s.viewing_cos_limit = viewingCosLimit;
+        inView.assign(ids.size() + 1, 0);
+        const int n = Search(s, assign, inView.data());
+        inView.resize(ids.size());
+        return n;
+    }
+    // SearchByProjection(CurrentFrame = this, LastFrame, th) (FeatureMatcher.cc:1291-1402): ids[i] = the map point of LastFrame's feature i,
+    // -1 for none / an outlier
+    int SearchByProjectionLast(DeviceMapPoints &points, DeviceFrame &last, const std::vector<int32_t> &ids, float radiusTh, float thHigh, float nnratio,
+                               bool checkOrientation, std::vector<int32_t> &assign, const uint8_t *occupied = nullptr) {
+        afv_point_search s = PointSearch(points, ids, AFV_PT_LASTFRAME, radiusTh, thHigh, nnratio, checkOrientation, occupied);
+        s.qframe = last.f;
+        return Search(s, assign, nullptr);
+    }
+    // SearchByProjection(CurrentFrame = this, pKF, sAlreadyFound, th, useHigh) (:1404-1506): ids[i] = the map point of the keyframe's feature
+    // i (-1: none / already found), kfAngles[i] = pKF->mvKeysUn[i].angle
+    int SearchByProjectionReloc(DeviceMapPoints &points, const std::vector<int32_t> &ids, const float *kfAngles, float radiusTh, float descDistTh,
+                                float nnratio, bool checkOrientation, std::vector<int32_t> &assign, const uint8_t *occupied = nullptr) {
+        afv_point_search s = PointSearch(points, ids, AFV_PT_RELOC, radiusTh, descDistTh, nnratio, checkOrientation, occupied);
+        s.qangle = kfAngles;
+        return Search(s, assign, nullptr);
+    }
+    // matching core of Fuse(pKF = this, vpMapPoints, th) (:794-940; useInfGate false: Fuse(pKF, Scw, ...)): best[ids.size()] = feature | -1
+    int FusePoints(DeviceMapPoints &points, const std::vector<int32_t> &ids, float radiusTh, float thLow, bool useInfGate, std::vector<int32_t> &best) {
+        afv_point_search s = PointSearch(points, ids, AFV_PT_FUSE, radiusTh, thLow, 0.0f, false, nullptr);
+        best.assign(ids.size() + 1, -1);
+        int32_t n = 0;
+        const int rc = afv_frame_fuse_points(f, &s, useInfGate ? 1 : 0, best.data(), &n);
+        if (rc != AFV_OK) fatal("afv_frame_fuse_points", rc, ctx);
+        best.resize(ids.size());
+        return n;
+    }
+    float radiusScale = 1.15f;  // FeatureMatcher's static radiusScale
+
     int N() const { return afv_frame_count(f); }
     afv_frame *handle() { return f; }
     afv_ctx *context() { return ctx; }
 
   private:
+    afv_point_search PointSearch(DeviceMapPoints &points, const std::vector<int32_t> &ids, int flavour, float radiusTh, float th, float nnratio,
+                                 bool checkOrientation, const uint8_t *occupied) const {
+        afv_point_search s{};
+        s.struct_size = sizeof(s);
+        s.flavour = flavour;
+        s.points = points.handle();
+        s.ids = ids.data();
+        s.nq = (int32_t)ids.size();
+        s.radius_th = radiusTh;
+        s.radius_scale = radiusScale;
+        s.occupied = occupied;
+        s.th_high = th;
+        s.nnratio = nnratio;
+        s.check_orientation = checkOrientation ? 1 : 0;
+        return s;
+    }
+    int Search(const afv_point_search &s, std::vector<int32_t> &assign, uint8_t *inView) {
+        assign.assign((size_t)std::max(N(), 0) + 1, -1);
+        int32_t n = 0;
+        const int rc = afv_frame_search_points(f, &s, assign.data(), &n, inView, nullptr);
+        if (rc != AFV_OK) fatal("afv_frame_search_points", rc, ctx);
+        assign.resize((size_t)std::max(N(), 0));
+        return n;
+    }
     afv_ctx *ctx;
     afv_frame *f = nullptr;
 };

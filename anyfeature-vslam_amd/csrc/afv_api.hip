@@ -37,9 +37,10 @@ extern "C" void afv_destroy(afv_ctx *c) {
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
     afv_table_release_all(c);
     afv_frame_release_all(c);
+    afv_points_release_all(c);
     void *ptrs[] = {c->d_geo, c->d_tab, c->d_pyr, c->d_cand_packed, c->d_kept_xy, c->d_l1, c->d_l1_resp, c->d_l1_count, c->d_hq, c->d_hq_n, c->d_kept_resp,
                     c->d_kept_node, c->d_cand_count, c->d_sel_count, c->d_sel, c->d_frames, c->d_out_block,
-                    c->d_status, c->d_match, c->d_topk, c->d_slice, c->d_tickets, c->d_pf_blob, c->d_l2_scratch, c->d_proj_ticket};
+                    c->d_status, c->d_match, c->d_topk, c->d_slice, c->d_tickets, c->d_pf_blob, c->d_l2_scratch, c->d_proj_ticket, c->d_points_count};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->h_stage) {
@@ -511,6 +512,7 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
     const bool fuse = kind == AFV_KIND_FUSE, per_query = kind != AFV_KIND_PROJ;
     if (!c || !jobs || njobs < 1 || !assign || !nmatches) return AFV_EINVAL;
     if (dev && njobs != 1) return AFV_EINVAL;
+    PointQueries *const pq = dev ? dev->pq : nullptr;  // the query side comes from resident map points (afv_points.hip)
     for (int i = 0; i < njobs; ++i) {
         const afv_proj_job &j = jobs[i];
         if (j.n < 0 || j.n > AFV_MAX_SIDE || j.nq < 0 || j.nq > 65535) return AFV_EINVAL;
@@ -521,7 +523,8 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
         }
         if (j.grid_cols < 1 || j.grid_rows < 1 || (long)j.grid_cols * j.grid_rows > 8192) return AFV_EINVAL;
         if (!dev && j.n > 0 && (!j.desc || !j.x || !j.y || !j.size)) return AFV_EINVAL;
-        if (j.nq > 0 && ((!j.qdesc && !(dev && (dev->qdesc_dev || dev->qref_table))) || !j.qu || !j.qv || !j.qr || !j.qmin_size || !j.qmax_size)) return AFV_EINVAL;
+        if (j.nq > 0 && !pq && ((!j.qdesc && !(dev && (dev->qdesc_dev || dev->qref_table))) || !j.qu || !j.qv || !j.qr || !j.qmin_size || !j.qmax_size)) return AFV_EINVAL;
+        if (pq && !pq->ids && j.nq > 0) return AFV_EINVAL;
         const bool has_angle = dev ? dev->angle != nullptr : j.angle != nullptr;
         const bool has_qangle = j.qangle != nullptr || (dev && dev->qangle_dev);
         if (kind == AFV_KIND_INIT && j.check_orientation && ((j.n > 0 && !has_angle) || (j.nq > 0 && !has_qangle))) return AFV_EINVAL;
@@ -534,7 +537,7 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
     }
     HIPCHK(c, hipSetDevice(c->device));
     Blob b(c);
-    struct Off { size_t fd, x, y, size, angle, occ, inf, cptr, cent, qd, qrs, qri, qvalid, qu, qv, qr, qmin, qmax, qang, qocc, keys, ncand, ori, ur, qur, qer; int words; bool stereo; };
+    struct Off { size_t fd, x, y, size, angle, occ, inf, cptr, cent, qd, qrs, qri, qvalid, qu, qv, qr, qmin, qmax, qang, qocc, keys, ncand, ori, ur, qur, qer, pids, pcount; int words; bool stereo; };
     std::vector<Off> offs(njobs);
     size_t total_out = 0;
     int max_nq = 0, max_n = 0;
@@ -549,9 +552,9 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
         if (dev && dev->words != o.words) return AFV_EINVAL;
         // mvuRight branches: FeatureMatcher.cc:114-119, :1367-1372, :880-894.  A resident frame always carries the plane (-1 = monocular);
         // it takes part when the caller sends the queries' side of the gate
-        const bool ur_here = dev ? (dev->u_right != nullptr && j.q_ur != nullptr) : j.u_right != nullptr;
+        const bool ur_here = dev ? (dev->u_right != nullptr && (j.q_ur != nullptr || (pq && pq->stereo))) : j.u_right != nullptr;
         o.stereo = ur_here && (kind == AFV_KIND_PROJ || kind == AFV_KIND_FUSE);
-        if (o.stereo && kind == AFV_KIND_PROJ && j.nq > 0 && !j.q_er_max) return AFV_EINVAL;
+        if (o.stereo && kind == AFV_KIND_PROJ && j.nq > 0 && !j.q_er_max && !pq) return AFV_EINVAL;
         if (!dev) {
             o.fd = j.float_dim ? b.put(j.desc, (size_t)j.n * j.float_dim * 4) : put_desc(b, j.desc, j.n, j.desc_bytes, o.words);
             o.x = b.put(j.x, (size_t)j.n * 4); o.y = b.put(j.y, (size_t)j.n * 4); o.size = b.put(j.size, (size_t)j.n * 4);
@@ -561,8 +564,9 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
             grid_lds = std::max(grid_lds, afv_frame_grid_lds(j.grid_cols, j.grid_rows, std::max(j.n, 1)));
         }
         o.occ = (j.occupied && kind != AFV_KIND_INIT) ? b.put(j.occupied, (size_t)j.n) : 0;
-        o.qur = o.stereo ? b.put(j.q_ur, (size_t)j.nq * 4) : 0;
-        o.qer = (o.stereo && kind == AFV_KIND_PROJ) ? b.put(j.q_er_max, (size_t)j.nq * 4) : 0;
+        o.qur = (o.stereo && !pq) ? b.put(j.q_ur, (size_t)j.nq * 4) : 0;
+        o.qer = (o.stereo && kind == AFV_KIND_PROJ && !pq) ? b.put(j.q_er_max, (size_t)j.nq * 4) : 0;
+        if (pq) o.pids = b.put(pq->ids, (size_t)j.nq * 4);
         const bool by_ref = dev && dev->qref_table && !dev->qdesc_dev;
         if (by_ref) {
             // MapPoint descriptors by reference (rows of a keyframe table): checked here, gathered on the device behind the upload
@@ -574,12 +578,14 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
             }
             o.qrs = b.put(dev->qref_slot, (size_t)j.nq * 4);
             o.qri = b.put(dev->qref_idx, (size_t)j.nq * 4);
-        } else if (!(dev && dev->qdesc_dev)) {
+        } else if (!(dev && dev->qdesc_dev) && !pq) {
             o.qd = j.float_dim ? b.put(j.qdesc, (size_t)j.nq * j.float_dim * 4) : put_desc(b, j.qdesc, j.nq, j.desc_bytes, o.words);
         }
         o.qvalid = (j.qvalid && !(dev && dev->qvalid_dev)) ? b.put(j.qvalid, (size_t)j.nq) : 0;
-        o.qu = b.put(j.qu, (size_t)j.nq * 4); o.qv = b.put(j.qv, (size_t)j.nq * 4); o.qr = b.put(j.qr, (size_t)j.nq * 4);
-        o.qmin = b.put(j.qmin_size, (size_t)j.nq * 4); o.qmax = b.put(j.qmax_size, (size_t)j.nq * 4);
+        if (!pq) {
+            o.qu = b.put(j.qu, (size_t)j.nq * 4); o.qv = b.put(j.qv, (size_t)j.nq * 4); o.qr = b.put(j.qr, (size_t)j.nq * 4);
+            o.qmin = b.put(j.qmin_size, (size_t)j.nq * 4); o.qmax = b.put(j.qmax_size, (size_t)j.nq * 4);
+        }
         o.qang = (j.qangle && !(dev && dev->qangle_dev)) ? b.put(j.qangle, (size_t)j.nq * 4) : 0;
         o.qocc = j.qoccupies ? b.put(j.qoccupies, (size_t)j.nq) : 0;
         total_out += (size_t)(per_query ? j.nq : j.n);
@@ -597,6 +603,15 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
         offs[i].ncand = b.reserve_scratch((size_t)std::max(j.nq, 1) * 4);
         offs[i].ori = b.reserve_scratch((size_t)std::max(j.nq, 1) * 8);
         if (dev && dev->qref_table && !dev->qdesc_dev) offs[i].qd = b.reserve_scratch((size_t)std::max(j.nq, 1) * dev->qref_table->words * 4);
+        if (pq) {  // what k_points_project writes: the whole query side
+            Off &o = offs[i];
+            const size_t nq4 = (size_t)std::max(j.nq, 1) * 4;
+            o.qu = b.reserve_scratch(nq4); o.qv = b.reserve_scratch(nq4); o.qr = b.reserve_scratch(nq4);
+            o.qmin = b.reserve_scratch(nq4); o.qmax = b.reserve_scratch(nq4); o.qur = b.reserve_scratch(nq4); o.qer = b.reserve_scratch(nq4);
+            o.qvalid = b.reserve_scratch(nq4 / 4); o.qocc = b.reserve_scratch(nq4 / 4);
+            o.qd = b.reserve_scratch(nq4 * o.words);
+            o.pcount = b.reserve_scratch(16);
+        }
         if (!dev) {
             offs[i].cptr = b.reserve_scratch(((size_t)j.grid_cols * j.grid_rows + 1) * 4);
             offs[i].cent = b.reserve_scratch((size_t)std::max(j.n, 1) * 16);
@@ -622,6 +637,7 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
     const bool zero_copy_in = zero_copy && dev && njobs == 1 && !any_float && !(jobs[0].occupied && kind != AFV_KIND_INIT);
     uint8_t *B = c->d_match, *H = b.h.data();
     uint8_t *IN = zero_copy_in ? H : B;  // where the kernels find the staged inputs
+    uint8_t *QIN = pq ? B : IN;          // ... and the query arrays: k_points_project writes them into device memory
     size_t acc = 0;
     for (int i = 0; i < njobs; ++i) {
         const afv_proj_job &j = jobs[i];
@@ -653,20 +669,20 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
         d.min_x = j.min_x; d.min_y = j.min_y; d.inv_w = j.grid_inv_w; d.inv_h = j.grid_inv_h; d.cols = j.grid_cols; d.rows = j.grid_rows;
         d.nq = j.nq;
         d.qdesc = (dev && dev->qdesc_dev) ? dev->qdesc_dev
-                                          : reinterpret_cast<const uint32_t *>(((dev && dev->qref_table) ? B : IN) + o.qd);
-        d.qvalid = (dev && dev->qvalid_dev) ? dev->qvalid_dev : (j.qvalid ? IN + o.qvalid : nullptr);
-        d.qu = reinterpret_cast<const float *>(IN + o.qu); d.qv = reinterpret_cast<const float *>(IN + o.qv);
-        d.qr = reinterpret_cast<const float *>(IN + o.qr); d.qmin = reinterpret_cast<const float *>(IN + o.qmin);
-        d.qmax = reinterpret_cast<const float *>(IN + o.qmax);
+                                          : reinterpret_cast<const uint32_t *>(((dev && dev->qref_table) ? B : QIN) + o.qd);
+        d.qvalid = (dev && dev->qvalid_dev) ? dev->qvalid_dev : ((j.qvalid || pq) ? QIN + o.qvalid : nullptr);
+        d.qu = reinterpret_cast<const float *>(QIN + o.qu); d.qv = reinterpret_cast<const float *>(QIN + o.qv);
+        d.qr = reinterpret_cast<const float *>(QIN + o.qr); d.qmin = reinterpret_cast<const float *>(QIN + o.qmin);
+        d.qmax = reinterpret_cast<const float *>(QIN + o.qmax);
         d.qangle = (dev && dev->qangle_dev) ? dev->qangle_dev : (j.qangle ? reinterpret_cast<const float *>(IN + o.qang) : nullptr);
-        d.qocc = j.qoccupies ? IN + o.qocc : nullptr;
+        d.qocc = (j.qoccupies || pq) ? QIN + o.qocc : nullptr;
         d.th = j.th_high; d.ratio = j.nnratio; d.tol = j.size_tol; d.inv_tol = j.inv_size_tol;
         d.check_ori = j.check_orientation != 0; d.mode = j.mode;
         d.pass_cap = afv_debug_pass_cap;
         d.keys = reinterpret_cast<unsigned long long *>(B + o.keys); d.ncand = reinterpret_cast<int *>(B + o.ncand);
         d.orilist = reinterpret_cast<int *>(B + o.ori);
-        d.q_ur = o.stereo ? reinterpret_cast<const float *>(IN + o.qur) : nullptr;
-        d.q_er = (o.stereo && kind == AFV_KIND_PROJ) ? reinterpret_cast<const float *>(IN + o.qer) : nullptr;
+        d.q_ur = o.stereo ? reinterpret_cast<const float *>(QIN + o.qur) : nullptr;
+        d.q_er = (o.stereo && kind == AFV_KIND_PROJ) ? reinterpret_cast<const float *>(QIN + o.qer) : nullptr;
         d.stereo_gate = (o.stereo && kind == AFV_KIND_PROJ) ? 1 : 0;
         uint8_t *R = zero_copy ? H : B;
         d.assign = reinterpret_cast<int *>(R + out_off + acc * 4); d.nmatches = reinterpret_cast<int *>(R + nm_off + (size_t)i * 4);
@@ -684,6 +700,23 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
         const afv_table *qt = dev->qref_table;
         afv_launch_frame_gather(qt->d_desc, qt->d_n, qt->nsets, qt->cap, reinterpret_cast<const int *>(IN + offs[0].qrs),
                                 reinterpret_cast<const int *>(IN + offs[0].qri), jobs[0].nq, B + offs[0].qd, nullptr, qt->words, c->stream);
+    }
+    if (pq && jobs[0].nq > 0) {  // geometry and descriptor gather: the one launch a search through ids adds
+        const Off &o = offs[0];
+        DevPointsJob &pj = pq->job;
+        pj.ids = reinterpret_cast<const int *>(IN + o.pids);
+        pj.nq = jobs[0].nq;
+        pj.qu = reinterpret_cast<float *>(B + o.qu); pj.qv = reinterpret_cast<float *>(B + o.qv); pj.qr = reinterpret_cast<float *>(B + o.qr);
+        pj.qmin = reinterpret_cast<float *>(B + o.qmin); pj.qmax = reinterpret_cast<float *>(B + o.qmax);
+        pj.q_ur = reinterpret_cast<float *>(B + o.qur); pj.q_er = reinterpret_cast<float *>(B + o.qer);
+        pj.qvalid = B + o.qvalid; pj.qocc = B + o.qocc;
+        pj.qd = reinterpret_cast<uint4 *>(B + o.qd);
+        pj.count = c->d_points_count;
+        pj.ticket = c->d_points_count + 1;
+        pj.count_out = reinterpret_cast<int *>(B + o.pcount);
+        pj.o_size = pj.o_sigma = pj.o_cos = nullptr;
+        afv_launch_points_project(&pj, c->stream);
+        HIPCHK(c, hipGetLastError());
     }
     const DevProjJob *dj = reinterpret_cast<const DevProjJob *>(B + jobs_off);
     const DevProjJob *one = zero_copy_in ? reinterpret_cast<const DevProjJob *>(H + jobs_off) : nullptr;
@@ -706,13 +739,19 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
         HIPCHK(c, b.fetch(assign, out_off, total_out * 4, c->stream));
         if (!fuse) HIPCHK(c, b.fetch(nmatches, nm_off, (size_t)njobs * 4, c->stream));
     }
+    if (pq) {
+        pq->n_in_view = 0;
+        if (jobs[0].nq > 0) {
+            if (pq->in_view) HIPCHK(c, b.fetch(pq->in_view, offs[0].qvalid, (size_t)jobs[0].nq, c->stream));
+            HIPCHK(c, b.fetch(&pq->n_in_view, offs[0].pcount, 4, c->stream));
+        }
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (zero_copy) {
         std::memcpy(assign, H + out_off, total_out * 4);
         if (!fuse) std::memcpy(nmatches, H + nm_off, (size_t)njobs * 4);
-    } else {
-        b.finish();
     }
+    b.finish();
     if (fuse) {  // independent queries: the count is just the number of hits
         size_t at = 0;
         for (int i = 0; i < njobs; ++i) {

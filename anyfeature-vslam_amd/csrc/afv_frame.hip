@@ -27,6 +27,11 @@ static void frame_free(afv_frame *f) {
     delete f;
 }
 
+bool afv_frame_is_live(const afv_frame *f) {
+    std::lock_guard<std::mutex> lk(g_frames_mutex);
+    return g_live_frames.count(f) != 0;
+}
+
 void afv_frame_release_all(afv_ctx *c) {
     std::vector<afv_frame *> mine;
     mine.swap(c->frames);

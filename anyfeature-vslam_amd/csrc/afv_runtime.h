@@ -113,6 +113,47 @@ extern "C" void afv_launch_stereo_median(float *u_right, float *depth, const int
 extern "C" void afv_launch_stereo_rgbd(const afv_keypoint *kps, const float *x_un, int n, const float *img, int w, int h, float mbf, float *u_right,
                                        float *depth, hipStream_t stream);
 
+// ---- k_points.hip: the resident map-point store and the projections in front of the projection searches ----
+#define AFV_PTF_SET 1u       // flag bits of a point
+#define AFV_PTF_BAD 2u
+#define AFV_PTF_OBSERVED 4u
+struct DevPointPlanes {      // the store (SoA over `cap` ids)
+    float *pos[3], *normal[3], *min_d, *max_d, *ref_size, *ref_dist, *ref_sigma;
+    uint8_t *flags;
+    uint8_t *desc;           // [cap] rows of 4 * words bytes
+    int cap, words;
+};
+struct DevPointsJob {        // k_points_project: a kernel argument
+    DevPointPlanes P;
+    const int *ids;
+    int nq, flavour;
+    float R[9], t[3], Ow[3], fx, fy, cx, cy, mbf;
+    float min_x, max_x, min_y, max_y;
+    float rs_th;             // radius_scale * radius_th, one float product made on the host
+    float cos_limit, tol;
+    const float *last_size;  // LASTFRAME: keyPtsSize of the last frame, indexed by q
+    float *qu, *qv, *qr, *qmin, *qmax, *q_ur, *q_er;
+    uint8_t *qvalid, *qocc;
+    uint4 *qd;               // [nq] gathered rows; null: no gather
+    int *count, *ticket;     // the context's accumulator of queries in view and its ticket, both zero at rest
+    int *count_out;          // where the last workgroup leaves the sum
+    float *o_size, *o_sigma, *o_cos;  // afv_frame_project_points only (may be null)
+};
+struct DevPointsMove {       // k_points_move: n ids between packed arrays (host order) and the planes; null = field not moved
+    DevPointPlanes P;
+    const int *ids;
+    int n, gather;           // gather 0: packed -> planes (a setter); 1: planes -> packed (afv_points_get)
+    float *pos, *normal, *min_d, *max_d, *ref_size, *ref_dist, *ref_sigma;
+    uint8_t *bad, *observed, *flags;
+    int mark_set;
+};
+extern "C" void afv_launch_points_project(const DevPointsJob *job, hipStream_t stream);
+extern "C" void afv_launch_points_move(const DevPointsMove *job, hipStream_t stream);
+// descriptor rows of n ids: from packed rows of the store's pitch (table == null), from rows (slot, idx) of a keyframe table, or (gather)
+// out of the store into packed rows
+extern "C" void afv_launch_points_rows(const DevPointPlanes *P, const int *ids, int n, uint8_t *packed, const uint8_t *table, int table_cap,
+                                       const int *slot, const int *idx, int gather, hipStream_t stream);
+
 extern "C" void afv_launch_bow_transform(const DevVocab *v, const uint32_t *desc, int n, int levelsup, int *leaf_node,
                                          int *node_at_level, int *rank_at_level, hipStream_t stream);
 extern "C" int afv_launch_bow_transform_f32(const DevVocab *v, const float *desc, int n, int dim, int levelsup, int *leaf_node, int *node_at_level,
@@ -178,6 +219,24 @@ struct afv_frame {
     size_t pyr_bytes = 0, pyr_off[AFV_MAX_LEVELS]{};
     int pyr_levels = 0, pyr_w[AFV_MAX_LEVELS]{}, pyr_h[AFV_MAX_LEVELS]{};
     bool has_pyramid = false;
+    // afv_frame_set_pose (afv_points.hip): what k_points_project takes as kernel arguments
+    bool has_pose = false;
+    float Rcw[9]{}, tcw[3]{}, Ow[3]{}, fx = 0, fy = 0, cx = 0, cy = 0, mbf = 0;
+};
+
+// the device-resident map-point store (afv_points.hip)
+struct afv_points {
+    afv_ctx *c = nullptr;
+    int cap = 0;
+    int desc_bytes = 32, words = 8, float_dim = 0;  // as afv_frame
+    uint8_t *d_block = nullptr;  // the planes, one allocation
+    DevPointPlanes P{};
+    uint8_t *d_stage = nullptr;  // device staging of the setters / afv_points_get (grow-only)
+    size_t stage_bytes = 0;
+    uint8_t *h_pin = nullptr;    // its pinned host image: a setter fills it, uploads it and returns
+    size_t pin_bytes = 0;
+    hipEvent_t ev = nullptr;     // the last upload out of h_pin (the next setter waits for it before it refills the image)
+    bool ev_armed = false;
 };
 
 #define AFV_MAX_SIDE 8192
@@ -199,8 +258,10 @@ struct afv_ctx {
     int proj_wg_lds_max = 0;       // dynamic LDS bytes the workgroup engines may use (0: unavailable); afv_project_prepare at afv_create
     int frame_lds_max = 0;         // dynamic LDS bytes k_frame_grid / k_featvec_build may use; afv_frame_prepare at afv_create
     int *d_proj_ticket = nullptr;  // hand-off ticket of the one-launch search (k_proj_search1), zero at rest
+    int *d_points_count = nullptr; // k_points_project: {in-view accumulator, workgroup ticket}, zero at rest (made with the first map-point store)
     int proj_fuse = 1;             // 1: single-job searches rank and resolve in one launch (afv_set_projection_fuse)
     std::vector<afv_frame *> frames;  // frames alive on this context (destroyed with it)
+    std::vector<afv_points *> points; // ... and its map-point stores (afv_points.hip)
     int split_chunks = 0;          // ... into this many chunks (alternating streams); 0 = about 85 frames each; afv_set_split_chunks
     // small-batch ("latency") path: kernels shaped for one or a few frames; afv_set_small_batch_path
     int small_mode = 1;            // 0 = never, 1 = batches of at most small_max_frames, 2 = always
@@ -570,6 +631,8 @@ int afv_match_bow_plain32(afv_ctx *c, const afv_match_job *jobs, int njobs, int3
 int afv_check_resolve_guard(afv_ctx *c, const int32_t *nmatches, int n);
 void afv_table_release_all(afv_ctx *c);  // afv_destroy: tables / communicators still alive die with their context
 void afv_frame_release_all(afv_ctx *c);  // ... and so do its frames
+bool afv_frame_is_live(const afv_frame *f);  // afv_frame.hip: the pointer names a frame that was not destroyed
+void afv_points_release_all(afv_ctx *c); // ... and its map-point stores
 int afv_frame_after_extract(afv_frame *f, hipStream_t s);  // afv_frame.hip: k_frame_grid behind the describe kernel of afv_frame_extract
 // afv_stereo.hip: a keep_pyramid frame takes device copies of the levels of frame slot 0 of the extraction that just ran on stream s
 int afv_frame_keep_pyramid(afv_frame *f, const FrameSrc &src, hipStream_t s);
@@ -597,6 +660,16 @@ struct ProjFeatureSide {      // device pointers of the feature side; null fdesc
     const int32_t *qref_slot = nullptr, *qref_idx = nullptr;
     const float *qangle_dev = nullptr;
     const uint8_t *qvalid_dev = nullptr;
+    // ... or the whole query side made on the device from the ids of resident map points (afv_points.hip): k_points_project runs ahead of
+    // the search kernels and writes qu .. q_er_max, qvalid, qoccupies and the gathered rows into the call's staging area
+    struct PointQueries *pq = nullptr;
+};
+struct PointQueries {
+    DevPointsJob job{};            // planes, pose, flavour, rules; the core fills in ids and the outputs
+    const int32_t *ids = nullptr;  // host [nq]
+    bool stereo = false;           // the flavour has a stereo gate (every one but RELOC)
+    uint8_t *in_view = nullptr;    // host [nq] out, may be null
+    int32_t n_in_view = 0;         // out
 };
 enum { AFV_KIND_PROJ = 0, AFV_KIND_FUSE = 1, AFV_KIND_INIT = 2 };
 int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, int32_t *assign, int32_t *nmatches, int kind,

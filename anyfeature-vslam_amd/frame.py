@@ -266,3 +266,89 @@ class Frame:
                                                                float(matcher.mfNNratio), int(matcher.mbCheckOrientation), ptr(out), ptr(nm)),
                        "afv_frame_match_initialization")
         return out[:n1].copy(), int(nm[0])
+
+    # ---- resident map points: the geometry in front of the projection searches on the device ----
+    RADIUS_SCALE = 1.15  # FeatureMatcher's static radiusScale
+
+    def set_pose(self, Rcw, tcw, Ow, fx, fy, cx, cy, mbf=0.0):
+        """Frame::SetPose + the intrinsics: Rcw [3, 3], tcw [3], Ow = twc as the host computes it (Frame.cc:270-273)"""
+        R = np.ascontiguousarray(Rcw, np.float32).reshape(9)
+        t = np.ascontiguousarray(tcw, np.float32).reshape(3)
+        o = np.ascontiguousarray(Ow, np.float32).reshape(3)
+        self.ctx.check(self.lib.afv_frame_set_pose(self.handle, ptr(R), ptr(t), ptr(o), float(fx), float(fy), float(cx), float(cy), float(mbf)),
+                       "afv_frame_set_pose")
+
+    def _point_search(self, points, ids, flavour, radiusTh, viewingCosLimit=0.5, th=0.0, nnratio=0.0, check_orientation=False, qframe=None,
+                      qangle=None, occupied=None, radius_scale=None):
+        s = _lib.sized(_lib.PointSearch)
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        ang = None if qangle is None else np.ascontiguousarray(qangle, np.float32)
+        occ = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+        s.flavour, s.points, s.ids, s.nq = int(flavour), points.handle, ptr(ids), len(ids)
+        s.radius_th, s.radius_scale = float(radiusTh), float(self.RADIUS_SCALE if radius_scale is None else radius_scale)
+        s.viewing_cos_limit = float(viewingCosLimit)
+        s.qframe = None if qframe is None else qframe.handle
+        s.qangle, s.occupied = ptr(ang), ptr(occ)
+        s.th_high, s.nnratio, s.check_orientation = float(th), float(nnratio), int(bool(check_orientation))
+        return s, (ids, ang, occ)
+
+    def project_points(self, points, ids, flavour=_lib.PT_FRUSTUM, radiusTh=1.0, viewingCosLimit=0.5, last=None, radius_scale=None):
+        """afv_frame_project_points: the projection alone.  Returns a dict: in_view (bool), n_in_view, u, v, ur (mTrackProjX / Y / XR), size
+        (trackSize), sigma (trackSigma), view_cos (trackViewCos), r (the window radius), qmin, qmax (the size band), er (the stereo gate); 0 where not in view"""
+        s, keep = self._point_search(points, ids, flavour, radiusTh, viewingCosLimit, qframe=last, radius_scale=radius_scale)
+        n = s.nq
+        out = {k: np.zeros(max(n, 1), np.float32) for k in ("u", "v", "ur", "size", "sigma", "view_cos", "r", "qmin", "qmax", "er")}
+        iv = np.zeros(max(n, 1), np.uint8)
+        o = _lib.sized(_lib.PointProjection)
+        o.in_view = ptr(iv)
+        for k, a in out.items():
+            setattr(o, k, ptr(a))
+        self.ctx.check(self.lib.afv_frame_project_points(self.handle, C.byref(s), C.byref(o)), "afv_frame_project_points")
+        res = {k: a[:n] for k, a in out.items()}
+        res["in_view"] = iv[:n] != 0
+        res["n_in_view"] = int(o.n_in_view)
+        return res
+
+    def isInFrustum(self, points, ids, viewingCosLimit):
+        """Frame::isInFrustum (Frame.cc:276-331) of the points `ids`: mbTrackInView per id"""
+        return self.project_points(points, ids, _lib.PT_FRUSTUM, 1.0, viewingCosLimit)["in_view"]
+
+    def _search_points(self, s, keep):
+        n = self.N
+        out = np.full(max(n, 1), -1, np.int32)
+        nm = np.zeros(1, np.int32)
+        iv = np.zeros(max(s.nq, 1), np.uint8)
+        niv = C.c_int32(0)
+        self.ctx.check(self.lib.afv_frame_search_points(self.handle, C.byref(s), ptr(out), ptr(nm), ptr(iv), C.byref(niv)), "afv_frame_search_points")
+        return out[:n].copy(), int(nm[0]), iv[:s.nq] != 0
+
+    def SearchLocalPoints(self, matcher, points, ids, radiusTh, viewingCosLimit=0.5, occupied=None):
+        """Tracking::SearchLocalPoints (Tracking.cc:988-1028): isInFrustum of every point and SearchByProjection(F, vpMapPoints, th)
+        (FeatureMatcher.cc:73-154) in one call.  Returns (assign[N] = index into ids | -1, nmatches, in_view[len(ids)])"""
+        s, keep = self._point_search(points, ids, _lib.PT_FRUSTUM, radiusTh, viewingCosLimit, matcher.TH_HIGH, matcher.mfNNratio, False,
+                                     occupied=occupied)
+        return self._search_points(s, keep)
+
+    def SearchByProjectionLast(self, matcher, points, last, ids, radiusTh, occupied=None):
+        """SearchByProjection(CurrentFrame = self, LastFrame = last, th) (FeatureMatcher.cc:1291-1402): ids[i] = the map point of the last
+        frame's feature i, -1 for none / an outlier.  Returns (assign, nmatches)"""
+        s, keep = self._point_search(points, ids, _lib.PT_LASTFRAME, radiusTh, 0.0, matcher.TH_HIGH, matcher.mfNNratio, matcher.mbCheckOrientation,
+                                     qframe=last, occupied=occupied)
+        return self._search_points(s, keep)[:2]
+
+    def SearchByProjectionReloc(self, matcher, points, ids, radiusTh, keyframe=None, angles=None, occupied=None, useHighMatchingThreshold=False):
+        """SearchByProjection(CurrentFrame = self, pKF, sAlreadyFound, th, useHigh) (FeatureMatcher.cc:1404-1506): ids[i] = the map point of
+        the keyframe's feature i (-1: none / already found); the keyframe's angles from a resident frame in its role or a host array"""
+        th = matcher.descDistTh_high_reloc if useHighMatchingThreshold else matcher.descDistTh_low_reloc
+        s, keep = self._point_search(points, ids, _lib.PT_RELOC, radiusTh, 0.0, th, matcher.mfNNratio, matcher.mbCheckOrientation, qframe=keyframe,
+                                     qangle=angles, occupied=occupied)
+        return self._search_points(s, keep)[:2]
+
+    def FusePoints(self, matcher, points, ids, radiusTh, use_inf_gate=True):
+        """matching core of Fuse(pKF = self, vpMapPoints, th) (FeatureMatcher.cc:794-940; use_inf_gate False: the Sim3 flavour): returns
+        (bestIdx[len(ids)] | -1, nFound)"""
+        s, keep = self._point_search(points, ids, _lib.PT_FUSE, radiusTh, 0.0, matcher.TH_LOW, matcher.mfNNratio, False)
+        out = np.full(max(s.nq, 1), -1, np.int32)
+        nm = np.zeros(1, np.int32)
+        self.ctx.check(self.lib.afv_frame_fuse_points(self.handle, C.byref(s), int(bool(use_inf_gate)), ptr(out), ptr(nm)), "afv_frame_fuse_points")
+        return out[:s.nq].copy(), int(nm[0])

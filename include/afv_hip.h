@@ -21,6 +21,10 @@
  *   afv_match_l2                DescriptorDistance_sift128 (src/Feature_sift128.cpp:132-134) inside the
  *                               SearchByBoW(KF,KF) control flow (config #3)
  *   afv_hamming256              DescriptorDistance_orb32 (src/Feature_orb32.cpp:67-84)
+ *   afv_points_*, afv_frame_search_points / _fuse_points / _project_points
+ *                               Frame::isInFrustum (src/Frame.cc:276-331) and the projection loops of SearchByProjection(cur, last)
+ *                               (src/FeatureMatcher.cc:1312-1351), the relocalisation search (:1425-1465) and Fuse (:811-858) over
+ *                               device-resident map points: four rule sets and one deviation (D1), listed at "resident map points"
  */
 #ifndef AFV_HIP_H
 #define AFV_HIP_H
@@ -601,6 +605,97 @@ int afv_frame_set_depth(afv_frame *f, const float *depth, int width, int height,
 /* mvuRight[n], mvDepth[n] and, after afv_frame_stereo_match, for tests: sad[n] = the SAD of an accepted pair before the median filter,
  * best_r[n] = the right index the descriptor search chose; -1 where none.  Any pointer may be NULL. */
 int afv_frame_get_stereo(afv_frame *f, float *u_right, float *depth, int32_t *sad, int32_t *best_r);
+/* ---- resident map points: Frame::isInFrustum and the projections in front of the projection searches, on the device ----
+ * The geometry every projection search starts with - transform the map point into the camera, project it, test the image bounds, the
+ * scale-invariance band and the viewing angle, predict size and window radius - runs in ONE kernel (k_points_project) over a
+ * device-resident store of map points and the pose of the resident frame; a search then sends the ids of its points, 4 bytes per query.
+ * The semantics are those of the plain restatement tests/_points_ref.py, which the device is held to bit for bit: float arithmetic, one
+ * rounding per operator, three-term sums as a0 + (a1 + a2).  Parity with a build of the reference is unpinned (its last bit depends on its
+ * toolchain).  Four rule sets, each as the reference writes it:
+ *   AFV_PT_FRUSTUM    Frame::isInFrustum (Frame.cc:276-331) + the radius of SearchByProjection(F, vpMapPoints) (FeatureMatcher.cc:90-95,
+ *                     :116-117): PcZ < 0.0f rejects; u < min || u > max rejects (inclusive bounds); dist < 0.8f * min_distance ||
+ *                     dist > 1.2f * max_distance rejects; viewCos = dot / dist, viewCos < limit rejects; size = (ref_size * ref_distance) /
+ *                     dist; r = ((radius_scale * radius_th) * RadiusByViewingCos(viewCos)) * size with (double)viewCos > 0.998 ? 2.5f : 4.0f;
+ *                     the stereo gate is r * ((ref_sigma * ref_distance) / dist)
+ *   AFV_PT_LASTFRAME  SearchByProjection(CurrentFrame, LastFrame) (FeatureMatcher.cc:1312-1351, :1369-1371): invzc < 0 rejects (z = -0.0f
+ *                     rejects, z = +0.0f does not); inclusive bounds; no distance band, no viewing angle; size = keyPtsSize of feature q of
+ *                     the LAST resident frame (qframe), whose angle plane gives the query angles; r = (radius_scale * radius_th) * size,
+ *                     which is the stereo gate too
+ *   AFV_PT_RELOC      SearchByProjection(CurrentFrame, pKF, sAlreadyFound) (:1425-1465): NO depth test; inclusive bounds; the distance
+ *                     band; no viewing angle; predicted size; r = (radius_scale * radius_th) * size; no stereo gate
+ *   AFV_PT_FUSE       Fuse (:811-858, :309-357, :968-1015): z < 0.0f rejects; KeyFrame::IsInImage: x >= min && x < max (half-open,
+ *                     KeyFrame.cc:654-657); the distance band; dot < 0.5 * dist rejects; predicted size; r = (radius_scale * radius_th) * size
+ * FRUSTUM, LASTFRAME and RELOC project u = ((fx * PcX) * invz) + cx, FUSE x = PcX * invz; u = (fx * x) + cx (they differ in the last bit).
+ * q_ur = u - mbf * invz.  The size band of a query is size / sizeTolerance .. size * sizeTolerance (the frame's).
+ * D1, the one deliberate deviation: a query whose u, v, r or size band is not finite (z = +0, dist = 0, NaN coordinates) is not in view;
+ * the reference would hand such values to GetFeaturesInArea, whose float-to-int conversion is undefined.
+ * Queries: ids[q] == -1, an id that was never set and a bad point are invalid queries (not in view; the slot stays in the list, so q stays
+ * the last frame's feature index for LASTFRAME and the keyframe's for RELOC); the order of ids is the query order of the ordered phase;
+ * a query occupies its feature (afv_proj_queries.qoccupies) when its point's `observed` flag is set.  What a plane holds for a query that is
+ * not in view is 0.
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+typedef struct afv_points afv_points;
+#define AFV_POINTS_MAX_CAPACITY (1 << 22)
+/* a store of `capacity` map points (1 .. AFV_POINTS_MAX_CAPACITY, else AFV_EINVAL) whose descriptor rows are binary of desc_bytes 1 .. 64
+ * (0 = 32), or, with float_dim > 0, float rows (a multiple of 4 up to 1024): the kinds and the row padding of frames.  It belongs to the
+ * context and dies with it.  Per point id: pos[3] (MapPoint::XYZ), normal[3] (normalVector), min_distance / max_distance (the raw members:
+ * the device applies 0.8f * and 1.2f * as the getters do, MapPoint.cc:420-430), ref_size, ref_distance, ref_sigma, the flags `bad` and
+ * `observed` (NumberOfObservations() > 0), one descriptor row, and whether afv_points_set ever named it. */
+int afv_points_create(afv_ctx *ctx, int capacity, int desc_bytes, int float_dim, afv_points **out);
+void afv_points_destroy(afv_points *p);
+/* The setters take HOST arrays over n ids (pos / normal: n x 3 floats; the others n floats / bytes / rows), copy them before they return and
+ * work asynchronously on the context's stream.  An array that is NULL leaves that field as it is.  An id outside [0, capacity) refuses the
+ * whole call with AFV_EINVAL before anything is written; the ids of one call are distinct (a repeated id keeps one of its values).
+ * afv_points_set marks its ids as set. */
+int afv_points_set(afv_points *p, const int32_t *ids, int n, const float *pos, const float *normal, const float *min_d, const float *max_d,
+                   const float *ref_size, const float *ref_dist, const float *ref_sigma);
+int afv_points_set_flags(afv_points *p, const int32_t *ids, int n, const uint8_t *bad, const uint8_t *observed);
+/* rows: n x desc_bytes bytes (n x float_dim floats for a float store), packed */
+int afv_points_set_descriptors(afv_points *p, const int32_t *ids, int n, const uint8_t *rows);
+/* the row of feature idx[i] of keyframe slot[i] of a table, COPIED device to device now (MapPoint::ComputeDistinctiveDescriptors clones the
+ * keyframe's row).  A table of another kind or width: AFV_EUNSUPPORTED; a slot or an index out of range: AFV_EINVAL, before anything moves. */
+int afv_points_set_descriptors_from_table(afv_points *p, const int32_t *ids, int n, afv_table *table, const int32_t *slot, const int32_t *idx);
+/* for tests: what the store holds for n ids, any pointer may be NULL; flags[i] = 1 (set) | 2 (bad) | 4 (observed).  Synchronous. */
+int afv_points_get(afv_points *p, const int32_t *ids, int n, float *pos, float *normal, float *min_d, float *max_d, float *ref_size,
+                   float *ref_dist, float *ref_sigma, uint8_t *flags, uint8_t *rows);
+/* the pose of a resident frame and its intrinsics: Rcw row-major, tcw, Ow = twc as the host computes it with the reference's own
+ * expression (Frame.cc:270-273, FeatureMatcher.cc:1416).  The image bounds are the frame's (afv_frame_params).  The searches below answer
+ * AFV_EINVAL on a frame without a pose. */
+int afv_frame_set_pose(afv_frame *f, const float *Rcw, const float *tcw, const float *Ow, float fx, float fy, float cx, float cy, float mbf);
+enum { AFV_PT_FRUSTUM = 0, AFV_PT_LASTFRAME = 1, AFV_PT_RELOC = 2, AFV_PT_FUSE = 3 };
+typedef struct {
+    uint32_t struct_size;         /* sizeof(afv_point_search) */
+    int32_t flavour;              /* AFV_PT_* */
+    afv_points *points;
+    const int32_t *ids;           /* [nq] host: point id | -1 */
+    int32_t nq;                   /* <= 65535 */
+    float radius_th, radius_scale, viewing_cos_limit; /* radiusTh; radiusScale (1.15f in the reference); FRUSTUM's viewingCosLimit */
+    afv_frame *qframe;            /* LASTFRAME: the last frame (nq <= its count); RELOC without qangle: optional source of the query
+                                     angles; ignored (never read) by the other flavours */
+    const float *qangle;          /* RELOC: host alternative, [nq] degrees */
+    const uint8_t *occupied;      /* per FRAME feature, as in afv_proj_queries; NULL = none */
+    float th_high, nnratio;
+    int32_t check_orientation;
+} afv_point_search;
+typedef struct {
+    uint32_t struct_size;         /* sizeof(afv_point_projection) */
+    int32_t n_in_view;            /* out */
+    uint8_t *in_view;             /* host outputs over nq queries, any may be NULL */
+    float *u, *v, *ur, *size, *sigma, *view_cos, *r, *qmin, *qmax; /* sigma: every flavour but LASTFRAME; view_cos: FRUSTUM */
+    float *er;                    /* the stereo gate the search applies to |ur - mvuRight|: r * sigma (FRUSTUM), r (the others) */
+} afv_point_projection;
+/* FRUSTUM (searched in AFV_PROJ_LOCALMAP mode: Tracking::SearchLocalPoints, Tracking.cc:988-1028), LASTFRAME and RELOC (AFV_PROJ_LASTFRAME
+ * mode): assign[n] (the QUERY INDEX now in F.pts[i] | -1), *nmatches; in_view[nq] (may be NULL) is what IncreaseVisible needs
+ * (Tracking.cc:1010-1013), *n_in_view (may be NULL) their number.  One launch (k_points_project: geometry and descriptor gather) ahead of
+ * the search kernels of afv_frame_match_projection.  AFV_EINVAL / AFV_EUNSUPPORTED before any launch: store and frame on different
+ * contexts (EINVAL), a store of another descriptor kind or width than the frame (EUNSUPPORTED), no pose, qframe missing for LASTFRAME, an
+ * id at or beyond the capacity, nq > 65535, an unknown struct_size, the wrong flavour for the entry point.  nq == 0 is legal. */
+int afv_frame_search_points(afv_frame *f, const afv_point_search *s, int32_t *assign, int32_t *nmatches, uint8_t *in_view, int32_t *n_in_view);
+/* AFV_PT_FUSE: best[nq] (feature index | -1), *nfound, as afv_frame_match_fuse */
+int afv_frame_fuse_points(afv_frame *f, const afv_point_search *s, int use_inf_gate, int32_t *best, int32_t *nfound);
+/* the projection alone, any flavour (tests; hosts that want mTrackProjX and the like) */
+int afv_frame_project_points(afv_frame *f, const afv_point_search *s, afv_point_projection *host_out);
+
 /* engine of the ordered phase of the projection searches / SearchForInitialization (identical results):
  *   1: one fixed point over all live queries of a job on a 1024-thread workgroup (round 5)   0: the ordered walk of rounds 1-4 on one
  *   wavefront   2 (default): 1 whenever the job's tables fit the workgroup's LDS, else 0   3: as 1, but ranking and ordered phase as two
