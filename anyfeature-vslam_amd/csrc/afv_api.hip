@@ -762,7 +762,7 @@ int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, i
         }
     } else {
         for (int i = 0; i < njobs; ++i)
-            if (nmatches[i] == -0x7fffffff) {  // PW_GUARD: the fixed point did not settle within its pass guard (never observed)
+            if (nmatches[i] == -0x7fffffff) {  // AFV_FP_GUARD (afv_wave.h): the fixed point did not settle within its pass guard (never observed)
                 c->last_error = "projection search: the fixed point hit its pass guard; afv_set_projection_resolve(ctx, 0) selects the ordered walk";
                 return AFV_EHIP;
             }

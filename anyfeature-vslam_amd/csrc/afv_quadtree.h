@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "afv_wave.h"
+
 #define QT_T 1024
 #define QT_NW (QT_T / 64)
 #define QT_PPT 8  // points a thread keeps in registers (coordinates + node label): sets of up to 8192 points never re-read memory

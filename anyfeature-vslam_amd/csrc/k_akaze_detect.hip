@@ -18,6 +18,7 @@
 //  3. k_akz_refine_a / _b: the 2x2 sub-pixel solve and the ordered compaction over the slot space.
 #include <cstdlib>
 #include "afv_device.h"
+#include "afv_wave.h"
 #include "akz_jobs.h"
 #include "../../include/afv_hip.h"
 

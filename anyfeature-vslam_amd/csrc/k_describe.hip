@@ -14,6 +14,7 @@
 // pass + round-half-even(S/65536) only at the sampled locations.  A test that falls outside the level ROI reads the unblurred apron pixel, as in OpenCV
 // where only the ROI is blurred in place.  No blurred image ever touches HBM.
 #include "afv_device.h"
+#include "afv_wave.h"
 #include "afv_runtime.h"  // the launchers below are declared there: a signature that drifts is a compile error, not a silent ABI mismatch
 
 // the 256 test pairs (x0, y0, x1, y1) as floats (FeatureExtractor.h:219-477): one 16-byte load per test, no conversions
@@ -112,17 +113,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// sum over the 64 lanes (every lane receives it): DPP row reductions, then the last lane's total through a scalar register
-__device__ __forceinline__ int wave_sum(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111 /*row_shr:1*/, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112 /*row_shr:2*/, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114 /*row_shr:4*/, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118 /*row_shr:8*/, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142 /*row_bcast:15*/, 0xa, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143 /*row_bcast:31*/, 0xc, 0xf, false);
-    return __builtin_amdgcn_readlane(v, 63);
 }
 
 // round-half-even(S / 65536) saturated to 255.  S < 2^24 whenever the result is not saturated, so u32 -> f32 is exact, the scaling by
@@ -348,8 +338,8 @@ __device__ __forceinline__ void describe_body(const Geo *__restrict__ geo_p, con
     if constexpr (MODE != 1) blur_rows(P, H, lane);  // overwrites the patch (see the slice layout above): everything that reads P comes before this line
     float angle = given_angle;
     if constexpr (MODE != 2) {
-        m10 = wave_sum(m10);
-        m01 = wave_sum(m01);
+        m10 = afv_wave_sum(m10);
+        m01 = afv_wave_sum(m01);
         angle = fast_atan2_deg((float)m01, (float)m10);
     }
     const float ptx = (float)cx * L.scale, pty = (float)cy * L.scale;

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "afv_device.h"
+#include "afv_wave.h"
 #include "afv_runtime.h"  // the launchers below are declared there: a signature that drifts is a compile error, not a silent ABI mismatch
 
 typedef short short2v __attribute__((ext_vector_type(2)));
@@ -40,24 +41,7 @@ __device__ __forceinline__ uint32_t pk_shr1(uint32_t v) {  // v_pk_lshrrev_b16: 
 }
 __device__ __forceinline__ short2v pk_sar15(short2v v) { return v >> (short)15; }  // v_pk_ashrrev_i16: 0xffff where negative
 
-// ---- cross-lane helpers on DPP (no LDS round trips) ----
-#define DPP_QUAD_XOR1 0xB1       // quad_perm:[1,0,3,2]
-#define DPP_QUAD_XOR2 0x4E       // quad_perm:[2,3,0,1]
-#define DPP_ROW_HALF_MIRROR 0x141
-#define DPP_ROW_SHR(n) (0x110 + (n))
-#define DPP_ROW_BCAST15 0x142
-#define DPP_ROW_BCAST31 0x143
-// inclusive prefix sum over the 64 lanes of a wavefront: 4 Hillis-Steele steps inside each row of 16 lanes, then the row
-// totals are carried over with row_bcast15 (rows 1, 3) and row_bcast31 (rows 2, 3)
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR(1), 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR(2), 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR(4), 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR(8), 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_BCAST15, 0xa, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_BCAST31, 0xc, 0xf, false);
-    return v;
-}
+// ---- cross-lane helpers on DPP (no LDS round trips): the control words and the wavefront scan are afv_wave.h's ----
 // one lane's LDS fetch-add as ONE instruction (the compiler's wave aggregation of atomics - mbcnt, compare, popcount, multiply - is dead
 // weight when a single lane is active by construction)
 __device__ __forceinline__ int lds_add_rtn_one_lane(int *p, int v) {
@@ -416,7 +400,7 @@ __global__ __launch_bounds__(256) void k_fast_nms(const Geo *__restrict__ geo_p,
             bd |= as_u32(pk_sar15(lo - (V - T0))) & bit;
         }
         const int cnt = __popc(bb) | (__popc(bd) << 16);
-        const int incl = wave_incl_scan(cnt);
+        const int incl = afv_wave_incl_scan(cnt);
         int base_b = 0, base_d = 0;
         if (lane == 63) {
             base_b = lds_add_rtn_one_lane(&pre_nb, incl & 0xffff);
@@ -533,7 +517,7 @@ __global__ __launch_bounds__(256) void k_fast_nms(const Geo *__restrict__ geo_p,
         }
         kb &= ((0xffffu << (16 - FT_H / 8)) & 0xffffu) * 0x00010001u;
         const int cnt = __popc(kb);
-        const int incl = wave_incl_scan(cnt);
+        const int incl = afv_wave_incl_scan(cnt);
         int base = 0;
         if (lane == 63) base = lds_add_rtn_one_lane(&list_n, incl);
         // `list` aliases `pre`: every wavefront must be done with the score lists before anyone writes (barrier above)

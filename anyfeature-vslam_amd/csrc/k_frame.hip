@@ -12,6 +12,7 @@
 //                     (node id, feature index), stopped words left out - the CSR body the BoW-guided matchers index (FeatureMatcher.cc:205-276)
 //   k_table_promote   KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-60): the frame's arrays into a slot of the keyframe table
 #include "afv_device.h"
+#include "afv_wave.h"
 #include "afv_runtime.h"
 #include "afv_jobs.h"
 

@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "afv_device.h"
+#include "afv_wave.h"
 #include "afv_runtime.h"  // the launchers below are declared there: a signature that drifts is a compile error, not a silent ABI mismatch
 
 typedef short short2v __attribute__((ext_vector_type(2)));

@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "afv_device.h"
+#include "afv_wave.h"
 #include "afv_runtime.h"  // the launchers below are declared there: a signature that drifts is a compile error, not a silent ABI mismatch
 #include "afv_jobs.h"
 
@@ -25,37 +26,6 @@
 #define MT 256
 #define NO_KEY 0x7fffffff
 #define MAX_SIDE 8192  // features per side a job may hold (LDS bitset + bin table)
-
-// LDS hand-off between lanes of ONE wavefront: DS operations of a wave execute in order, only the compiler has to be
-// kept from moving reads above writes
-#define WAVE_LDS_SYNC()                                        \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); \
-    } while (0)
-
-// The same hand-off when nothing but LDS traffic of THIS wavefront has to be ordered: a workgroup-scope release also drains the
-// vector-memory counter, i.e. it waits for every global store / load the wavefront still has in flight (about 2 us per round of the
-// ordered resolve walk, measured) — wavefront scope keeps the compiler from reordering and costs nothing at run time.
-#define WAVE_LDS_ONLY_SYNC()                                   \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-    } while (0)
-
-
-
-__device__ __forceinline__ int rotation_bin(float a1, float a2) {
-    // FeatureMatcher.cc:1587-1599, rotFactor = 1/30 (:1579-1585)
-    const float rot_factor = 1.0f / 30.0f;
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * rot_factor);
-    if (bin == 30) bin = 0;
-    return bin;
-}
 
 // merge two (best key, second distance) summaries.  key = dist << 16 | position
 __device__ __forceinline__ void merge_best(int &k, int &s, int k2, int s2) {
@@ -77,12 +47,7 @@ __device__ __forceinline__ void wave_merge_best(int &k, int &s) {
         const int s2 = __builtin_amdgcn_update_dpp(IDS, s, ctrl, rmask, 0xf, false);           \
         merge_best(k, s, k2, s2);                                                              \
     }
-    AFV_MB_STEP(0x111, 0xf)  // row_shr:1
-    AFV_MB_STEP(0x112, 0xf)  // row_shr:2
-    AFV_MB_STEP(0x114, 0xf)  // row_shr:4
-    AFV_MB_STEP(0x118, 0xf)  // row_shr:8
-    AFV_MB_STEP(0x142, 0xa)  // row_bcast:15 into rows 1, 3
-    AFV_MB_STEP(0x143, 0xc)  // row_bcast:31 into rows 2, 3
+    AFV_DPP_REDUCE64(AFV_MB_STEP)
 #undef AFV_MB_STEP
     k = __builtin_amdgcn_readlane(k, 63);
     s = __builtin_amdgcn_readlane(s, 63);
@@ -92,14 +57,6 @@ __device__ __forceinline__ int med3_i32(int a, int b, int c) {  // v_med3_i32 (n
     int r;
     asm("v_med3_i32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
-}
-
-template <int W>
-__device__ __forceinline__ int hamming_words(const uint32_t *a_regs, const uint32_t *b) {
-    int d = 0;
-#pragma unroll
-    for (int i = 0; i < W; ++i) d += __popc(a_regs[i] ^ b[i]);
-    return d;
 }
 
 // ---------------- float descriptors inside the BoW-guided matchers (round 6; W == 0 in the templates below) ----------------
@@ -185,7 +142,7 @@ __device__ void match_bow_job(const DevMatchJob &J, uint32_t *s_matched, uint8_t
                     (void)q;
                     merge_best(k, s, BK::make(l2sqr(frow(J.d1, idx1, J.fdim), frow(J.d2, idx2, J.fdim), J.fdim), b), BK::none2);
                 } else {
-                    const int d = hamming_words<W>(q, J.d2 + (size_t)idx2 * W);
+                    const int d = afv_hamming<W>(q, J.d2 + (size_t)idx2 * W);
                     merge_best(k, s, (d << 16) | b, NO_KEY >> 16);
                 }
             }
@@ -231,7 +188,7 @@ __device__ void match_bow_job(const DevMatchJob &J, uint32_t *s_matched, uint8_t
                         s_matched[idx2 >> 5] |= 1u << (idx2 & 31);
                         s_red[16]++;
                         if (J.check_ori) {
-                            const int bin = rotation_bin(J.ang1[(size_t)idx1 * J.ang_stride], J.ang2[(size_t)idx2 * J.ang_stride]);
+                            const int bin = afv_rotation_bin(J.ang1[(size_t)idx1 * J.ang_stride], J.ang2[(size_t)idx2 * J.ang_stride]);
                             s_bin[key] = (uint8_t)bin;
                             s_hist[bin]++;
                         }
@@ -244,16 +201,8 @@ __device__ void match_bow_job(const DevMatchJob &J, uint32_t *s_matched, uint8_t
     // M6: keep only the three dominant rotation bins (computeThreeMaxima :1631-1668)
     if (J.check_ori) {
         if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < 30; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-                else if (sz > max3) { max3 = sz; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            s_red[8] = i1; s_red[9] = i2; s_red[10] = i3;
+            const AfvMaxima3 mx = afv_three_maxima(s_hist);
+            s_red[8] = mx.i1; s_red[9] = mx.i2; s_red[10] = mx.i3;
         }
         __syncthreads();
         const int i1 = s_red[8], i2 = s_red[9], i3 = s_red[10];
@@ -343,7 +292,7 @@ __device__ __forceinline__ void bow_segment_small(const DevMatchJob &J, const Se
         const int key = kf_frame ? m_idx2 : idx1;
         J.out[key] = kf_frame ? idx1 : m_idx2;
         if (J.check_ori) {
-            const int bin = rotation_bin(a1, m_a2);
+            const int bin = afv_rotation_bin(a1, m_a2);
             bins[key] = (uint8_t)bin;
             atomicAdd(&hist[bin], 1);
         }
@@ -383,7 +332,7 @@ __device__ void bow_segment(const DevMatchJob &J, const Seg S, uint32_t *s_taken
                 (void)q;
                 merge_best(k, s, BK::make(l2sqr(frow(J.d1, idx1, J.fdim), frow(J.d2, idx2, J.fdim), J.fdim), b), BK::none2);
             } else {
-                const int d = hamming_words<W>(q, J.d2 + (size_t)idx2 * W);
+                const int d = afv_hamming<W>(q, J.d2 + (size_t)idx2 * W);
                 merge_best(k, s, (d << 16) | b, NO_KEY >> 16);
             }
         }
@@ -405,7 +354,7 @@ __device__ void bow_segment(const DevMatchJob &J, const Seg S, uint32_t *s_taken
                 J.out[key] = kf_frame ? idx1 : idx2;
                 s_taken[b >> 5] |= 1u << (b & 31);
                 if (J.check_ori) {
-                    const int bin = rotation_bin(J.ang1[(size_t)idx1 * J.ang_stride], J.ang2[(size_t)idx2 * J.ang_stride]);
+                    const int bin = afv_rotation_bin(J.ang1[(size_t)idx1 * J.ang_stride], J.ang2[(size_t)idx2 * J.ang_stride]);
                     bins[key] = (uint8_t)bin;
                     atomicAdd(&hist[bin], 1);
                 }
@@ -442,16 +391,8 @@ __global__ __launch_bounds__(MT) void k_match_bow_finish(const DevMatchJob *__re
     const int tid = threadIdx.x;
     if (tid == 0) {
         const int *h = hist + blockIdx.x * 32;
-        int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-        for (int i = 0; i < 30; ++i) {
-            const int sz = h[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-            else if (sz > max3) { max3 = sz; i3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-        s_i[0] = i1; s_i[1] = i2; s_i[2] = i3;
+        const AfvMaxima3 mx = afv_three_maxima(h);
+        s_i[0] = mx.i1; s_i[1] = mx.i2; s_i[2] = mx.i3;
         s_drop = 0;
     }
     __syncthreads();
@@ -858,23 +799,15 @@ __global__ __launch_bounds__(MT, 2) void k_match_resolve(const uint8_t *__restri
         for (int i = tid; i < n1; i += MT) {
             const int c = out[i];
             if (c >= 0) {
-                const int bin = rotation_bin(ang[((size_t)a * cap + i) * ang_stride], ang[((size_t)b * cap + c) * ang_stride]);
+                const int bin = afv_rotation_bin(ang[((size_t)a * cap + i) * ang_stride], ang[((size_t)b * cap + c) * ang_stride]);
                 s_bin[i] = (uint8_t)bin;
                 atomicAdd(&s_hist[bin], 1);
             }
         }
         __syncthreads();
         if (tid == 0) {  // computeThreeMaxima (FeatureMatcher.cc:1631-1668)
-            int i1 = -1, i2 = -1, i3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < 30; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-                else if (sz > max3) { max3 = sz; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            s_drop0 = i1; s_drop1 = i2; s_drop2 = i3;
+            const AfvMaxima3 mx = afv_three_maxima(s_hist);
+            s_drop0 = mx.i1; s_drop1 = mx.i2; s_drop2 = mx.i3;
         }
         __syncthreads();
         const int i1 = s_drop0, i2 = s_drop1, i3 = s_drop2;
@@ -911,12 +844,9 @@ __global__ __launch_bounds__(MT, 2) void k_match_resolve(const uint8_t *__restri
 //     is final: after convergence the waiting rows are rescanned, up to 32 at a time (two per wavefront), against the claims of the
 //     rows before them, the answers up to the first that takes a column are pinned, and the iteration continues;
 //   * there is no matched-set bitmap: "column c is taken for row i" is claim[c] < i.
-#define RW_INF 0x7fffffff
-#define AFV_RESOLVE_GUARD (-0x7fffffff)  // nmatches of a pair whose fixed point hit its pass guard
-#define RW_WLIST 128  // waiting rows looked at per convergence
+// (threads, waiting list, guard value, the adoption verdict and the tail's count are shared with the engines of k_project.hip: afv_wave.h,
+// AFV_FP_* / afv_wg_*)
 #define RW_RPW 2      // waiting rows a wavefront rescans together (they share the column loads): 32 per step
-#define RWT 1024      // threads: one per live row
-#define RW_NW (RWT / 64)
 static inline size_t resolve_wg_lds_bytes(int cap, bool stage_cols, int words) {
     const size_t c = ((size_t)cap + 63) & ~(size_t)63;
     return std::min<size_t>(c, PAIR_KEYS_LDS) * 32 /*key records*/ + 3 * c * 4 /*claims*/ + c * 4 /*matches*/ + 2 * c * 2 /*wants of the last two passes*/ +
@@ -969,7 +899,7 @@ __device__ __forceinline__ void resolve_eval(const int4 t4, const int4 t8, const
 }
 
 template <int W>
-__global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restrict__ desc, const float *__restrict__ ang, int ang_stride,
+__global__ __launch_bounds__(AFV_FP_T) void k_match_resolve_wg(const uint8_t *__restrict__ desc, const float *__restrict__ ang, int ang_stride,
                                                          const int *__restrict__ nset, int cap, const int *__restrict__ pair_a,
                                                          const int *__restrict__ pair_b, const int4 *__restrict__ topk, float th,
                                                          float ratio, int check_ori, int *__restrict__ match,
@@ -985,21 +915,21 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
     uint8_t *s_flag = s_bin + capr;  // per live row: 1 = asked for a rescan in the last pass, 2 = pinned by a rescan
     uint32_t *s_cols = reinterpret_cast<uint32_t *>((reinterpret_cast<uintptr_t>(s_flag + capr) + 15) & ~(uintptr_t)15);
     __shared__ int s_hist[32];
-    __shared__ int s_nm, s_drop0, s_drop1, s_drop2, s_first, s_part[RW_RPW * RW_NW], s_cntw[RW_NW];
-    __shared__ unsigned short s_wlist[RW_WLIST];  // live indices of the rows waiting for a rescan, in row order
+    __shared__ int s_nm, s_drop0, s_drop1, s_drop2, s_first, s_part[RW_RPW * AFV_FP_NW], s_cntw[AFV_FP_NW];
+    __shared__ unsigned short s_wlist[AFV_FP_WLIST];  // live indices of the rows waiting for a rescan, in row order
     const int p = pair_base + blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int a = pair_a[p], b = pair_b[p];
     const int n1 = min(nset[a], cap), n2 = min(nset[b], cap);
     const int4 *tk = topk + (size_t)p * cap * 2;
     int *out = match + (size_t)p * cap;
-    for (int i = tid; i < capr; i += RWT) s_out[i] = -1;
-    for (int i = tid; i < 3 * capr; i += RWT) s_claim[i] = RW_INF;
+    for (int i = tid; i < capr; i += AFV_FP_T) s_out[i] = -1;
+    for (int i = tid; i < 3 * capr; i += AFV_FP_T) s_claim[i] = AFV_FP_INF;
     if (tid < 32) s_hist[tid] = 0;
     // rows whose best distance fails TH_LOW can never match: compact the others IN ROW ORDER, keys staged in LDS.  A thread per row (sets of
     // up to 1024 rows - the usual case - in ONE step: one L2 round trip for the records, the 16 wavefronts' live counts meet in LDS behind
     // one barrier, every thread places its row from them)
     int nlive = 0;
-    for (int i0 = 0; i0 < n1; i0 += RWT) {
+    for (int i0 = 0; i0 < n1; i0 += AFV_FP_T) {
         const int i = i0 + tid;
         int4 t4 = make_int4(NO_KEY, NO_KEY, NO_KEY, NO_KEY), t8 = make_int4(NO_KEY, NO_KEY, NO_KEY, TOPK);
         if (i < n1) {
@@ -1012,7 +942,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         __syncthreads();
         int off = nlive, tot = 0;
 #pragma unroll
-        for (int w = 0; w < RW_NW; ++w) {
+        for (int w = 0; w < AFV_FP_NW; ++w) {
             const int cw = s_cntw[w];
             off += w < wv ? cw : 0;
             tot += cw;
@@ -1042,7 +972,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
     bool cols_ready = false;
     int pass = 0;
     // every pass finalises at least one more row or rescans one: a guard, never reached - if it ever is, the pair is REPORTED
-    // (nmatches = AFV_RESOLVE_GUARD, which the host entry points turn into AFV_EHIP), not returned half settled
+    // (nmatches = AFV_FP_GUARD, which the host entry points turn into AFV_EHIP), not returned half settled
     const int pass_limit = pass_cap > 0 ? pass_cap : 3 * nlive + 64;
     bool guard_hit = false;
     while (nlive > 0) {
@@ -1052,7 +982,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         }
         int *R = s_claim + (pass % 3) * capr, *Wc = s_claim + ((pass + 1) % 3) * capr, *Z = s_claim + ((pass + 2) % 3) * capr;
         bool changed = false;
-        for (int li = tid; li < nlive; li += RWT) {
+        for (int li = tid; li < nlive; li += AFV_FP_T) {
             const int w1 = s_w1[li], w2 = s_w2[li];
             const int flag = s_flag[li];
             int want = 0;
@@ -1073,7 +1003,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
                 s_flag[li] = rescan ? 1 : 0;
             }
             if (want >= 0) atomicMin(&Wc[want], li);
-            if (w2 >= 0) Z[w2] = RW_INF;  // what this row put into Z two passes ago (every row that did clears it: the array is empty before it is written again)
+            if (w2 >= 0) Z[w2] = AFV_FP_INF;  // what this row put into Z two passes ago (every row that did clears it: the array is empty before it is written again)
             s_w2[li] = (short)w1;
             s_w1[li] = (short)want;
             changed = changed || want != w1 || (rescan != ((flag & 1) != 0));
@@ -1081,7 +1011,9 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         ++pass;
         if (__syncthreads_or(changed ? 1 : 0)) continue;
         // converged: Wc holds the claims of the final wants (so far).  The rows that asked for a rescan, in row order (s_wlist): live row
-        // t is held by thread t, so a ballot + the wavefronts' counts place them
+        // t is held by thread t, so a ballot + the wavefronts' counts place them.  (This block and the compaction above are the text of
+        // afv_wg_collect_waiting / afv_wg_ordered_slot, afv_wave.h, written out: through the functions this kernel's register allocation
+        // moves - 113..115 instead of 116 vector registers at W = 16, 92 or 94 instead of 93 at W = 8 - whichever way they are called.)
         {
             const bool waits = tid < nlive && (s_flag[tid] & 3) == 1;  // the first 1024 live rows are looked at per cycle
             const unsigned long long bal = __ballot(waits);
@@ -1089,32 +1021,32 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
             __syncthreads();
             int off = 0, run = 0;
 #pragma unroll
-            for (int w = 0; w < RW_NW; ++w) {
+            for (int w = 0; w < AFV_FP_NW; ++w) {
                 const int cw = s_cntw[w];
                 off += w < wv ? cw : 0;
                 run += cw;
             }
             if (waits) {
                 const int slot = off + __popcll(bal & ((1ull << lane) - 1ull));
-                if (slot < RW_WLIST) s_wlist[slot] = (unsigned short)tid;
+                if (slot < AFV_FP_WLIST) s_wlist[slot] = (unsigned short)tid;
             }
             if (tid == 0) s_first = run;
             __syncthreads();
         }
-        int nw = min(s_first, RW_WLIST);
+        int nw = min(s_first, AFV_FP_WLIST);
 #if defined(AFV_RESOLVE_STATS) && AFV_RESOLVE_STATS == 4
         ++wg_conv;
         const long long wg_r0 = wall_clock64();
 #endif
-        if (nw == 0 && nlive > RWT) {  // sets above 1024 live rows: the rows behind the first 1024, one at a time (rare, slow, exact)
-            if (tid == 0) s_first = RW_INF;
+        if (nw == 0 && nlive > AFV_FP_T) {  // sets above 1024 live rows: the rows behind the first 1024, one at a time (rare, slow, exact)
+            if (tid == 0) s_first = AFV_FP_INF;
             __syncthreads();
-            int mine = RW_INF;
-            for (int li = RWT + tid; li < nlive; li += RWT)
+            int mine = AFV_FP_INF;
+            for (int li = AFV_FP_T + tid; li < nlive; li += AFV_FP_T)
                 if ((s_flag[li] & 3) == 1) mine = min(mine, li);
-            if (mine != RW_INF) atomicMin(&s_first, mine);
+            if (mine != AFV_FP_INF) atomicMin(&s_first, mine);
             __syncthreads();
-            if (s_first != RW_INF) {
+            if (s_first != AFV_FP_INF) {
                 if (tid == 0) s_wlist[0] = (unsigned short)s_first;
                 nw = 1;
             }
@@ -1124,7 +1056,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         if (stage_cols && !cols_ready) {  // first rescan of this pair: park the column descriptors in LDS
             const uint4 *gc = reinterpret_cast<const uint4 *>(d2);
             uint4 *sc = reinterpret_cast<uint4 *>(s_cols);
-            for (int i = tid; i < n2 * (W / 4); i += RWT) sc[i] = gc[i];
+            for (int i = tid; i < n2 * (W / 4); i += AFV_FP_T) sc[i] = gc[i];
             cols_ready = true;
             __syncthreads();
         }
@@ -1137,7 +1069,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         // iteration has settled with the new claim.  (Four rows per step, one per wavefront, left the slowest of 128 concurrent pairs
         // at 8 steps of two barriers each: that tail, not the median, is what a batch waits for.)
         bool took = false;
-        for (int g0 = 0; g0 < nw && !took; g0 += RW_RPW * RW_NW) {
+        for (int g0 = 0; g0 < nw && !took; g0 += RW_RPW * AFV_FP_NW) {
             int rr[RW_RPW], kk[RW_RPW], s2[RW_RPW], wr[RW_RPW];
             uint4 q[RW_RPW][W / 4];
             const int gb = g0 + wv * RW_RPW;
@@ -1201,15 +1133,9 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
                 s_part[wv * RW_RPW + lane] = v;
             }
             __syncthreads();
-            // adopt in row order (every thread computes the same verdict)
-            int nadopt = 0;
-#pragma unroll
-            for (int w = 0; w < RW_RPW * RW_NW; ++w) {
-                if (g0 + w < nw && !took) {
-                    ++nadopt;
-                    took = s_part[w] >= 0;
-                }
-            }
+            const AfvAdopt Ad = afv_wg_adopt_verdict<RW_RPW * AFV_FP_NW>(s_part, g0, nw);
+            const int nadopt = Ad.nadopt;
+            took = Ad.took;
 #if defined(AFV_RESOLVE_STATS) && AFV_RESOLVE_STATS == 4
             ++wg_steps; wg_resc += nadopt; wg_took += took ? 1 : 0;
 #endif
@@ -1225,7 +1151,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
 #if defined(AFV_RESOLVE_STATS) && AFV_RESOLVE_STATS == 4
         wg_tresc += wall_clock64() - wg_r0;
 #endif
-        if (!took && s_first <= RW_WLIST && nlive <= RWT) break;
+        if (!took && s_first <= AFV_FP_WLIST && nlive <= AFV_FP_T) break;
     }
 #if defined(AFV_RESOLVE_STATS) && AFV_RESOLVE_STATS == 4
     if (tid == 0) printf("wgpair %d nlive %d passes %d convergences %d rescan_steps %d rescans %d took %d fixedpoint_x10ns %lld rescan_x10ns %lld\n", p, nlive, pass, wg_conv, wg_steps, wg_resc, wg_took, wall_clock64() - wg_t0, wg_tresc);
@@ -1233,7 +1159,7 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
     // ---- matches, count ----
     {
         int cnt = 0;
-        for (int li = tid; li < nlive; li += RWT) {
+        for (int li = tid; li < nlive; li += AFV_FP_T) {
             const int w = s_w1[li];
             if (w >= 0) {
                 s_out[s_live[li]] = w;
@@ -1242,37 +1168,28 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         }
         if (tid == 0) s_nm = 0;
         __syncthreads();
-        cnt = afv_wave_incl_scan(cnt);
-        if (lane == 63 && cnt) atomicAdd(&s_nm, cnt);
+        afv_wg_add_count(cnt, &s_nm);
         __syncthreads();
     }
     if (check_ori) {
         // rotation histogram of the accepted matches (FeatureMatcher.cc:1587-1599): it never influences the walk
-        for (int i = tid; i < n1; i += RWT) {
+        for (int i = tid; i < n1; i += AFV_FP_T) {
             const int c = s_out[i];
             if (c >= 0) {
-                const int bin = rotation_bin(ang[((size_t)a * cap + i) * ang_stride], ang[((size_t)b * cap + c) * ang_stride]);
+                const int bin = afv_rotation_bin(ang[((size_t)a * cap + i) * ang_stride], ang[((size_t)b * cap + c) * ang_stride]);
                 s_bin[i] = (uint8_t)bin;
                 atomicAdd(&s_hist[bin], 1);
             }
         }
         __syncthreads();
         if (tid == 0) {  // computeThreeMaxima (FeatureMatcher.cc:1631-1668)
-            int i1 = -1, i2 = -1, i3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < 30; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-                else if (sz > max3) { max3 = sz; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            s_drop0 = i1; s_drop1 = i2; s_drop2 = i3;
+            const AfvMaxima3 mx = afv_three_maxima(s_hist);
+            s_drop0 = mx.i1; s_drop1 = mx.i2; s_drop2 = mx.i3;
         }
         __syncthreads();
         const int i1 = s_drop0, i2 = s_drop1, i3 = s_drop2;
         int dropped = 0;
-        for (int i = tid; i < n1; i += RWT) {
+        for (int i = tid; i < n1; i += AFV_FP_T) {
             if (s_out[i] >= 0) {
                 const int bb = s_bin[i];
                 if (bb != i1 && bb != i2 && bb != i3) { s_out[i] = -1; ++dropped; }
@@ -1281,8 +1198,8 @@ __global__ __launch_bounds__(RWT) void k_match_resolve_wg(const uint8_t *__restr
         if (dropped) atomicSub(&s_nm, dropped);
         __syncthreads();
     }
-    for (int i = tid; i < cap; i += RWT) out[i] = s_out[i];
-    if (tid == 0) nmatches[p] = guard_hit ? AFV_RESOLVE_GUARD : s_nm;
+    for (int i = tid; i < cap; i += AFV_FP_T) out[i] = s_out[i];
+    if (tid == 0) nmatches[p] = guard_hit ? AFV_FP_GUARD : s_nm;
 }
 
 // ---------------- M4: SearchForTriangulation ----------------
@@ -1325,7 +1242,7 @@ __device__ int tri_row(const DevTriJob &T, int idx1) {
             (void)q;
             d = l2sqr(frow(J.d1, idx1, J.fdim), frow(J.d2, idx2, J.fdim), J.fdim);
         } else {
-            d = hamming_words<W>(q, J.d2 + (size_t)idx2 * W);
+            d = afv_hamming<W>(q, J.d2 + (size_t)idx2 * W);
         }
         if ((float)d > J.th || d > best) continue;
         const float x2 = T.x2[idx2], y2 = T.y2[idx2], sg2 = T.sigma2_2[idx2];
@@ -1496,13 +1413,7 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint32_t *__restrict_
         if (i < n) best = min(best, ((unsigned)lo << 16) | (unsigned)i);
     }
     // wave minimum of (median, row): the least median, the first row on ties
-    best = min(best, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)best, 0x111, 0xf, 0xf, false));
-    best = min(best, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)best, 0x112, 0xf, 0xf, false));
-    best = min(best, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)best, 0x114, 0xf, 0xf, false));
-    best = min(best, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)best, 0x118, 0xf, 0xf, false));
-    best = min(best, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)best, 0x142, 0xa, 0xf, false));
-    best = min(best, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)best, 0x143, 0xc, 0xf, false));
-    const unsigned g = (unsigned)__builtin_amdgcn_readlane((int)best, 63);
+    const unsigned g = afv_wave_min_u32(best);
     if (lane == 0) {
         best_idx[s] = (int)(g & 0xffffu);
         best_median[s] = (int)(g >> 16);
@@ -1555,17 +1466,8 @@ __global__ __launch_bounds__(256) void k_distinctive_f32(const float *__restrict
         }
     }
     // the least median over the lanes, then the first row that has it
-    auto wave_min = [](unsigned v) {
-        v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x111, 0xf, 0xf, false));
-        v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x112, 0xf, 0xf, false));
-        v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x114, 0xf, 0xf, false));
-        v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x118, 0xf, 0xf, false));
-        v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x142, 0xa, 0xf, false));
-        v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, 0x143, 0xc, 0xf, false));
-        return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-    };
-    const unsigned gm = wave_min(best_med);
-    const unsigned gr = wave_min(best_med == gm ? best_row : 0xffffffffu);
+    const unsigned gm = afv_wave_min_u32(best_med);
+    const unsigned gr = afv_wave_min_u32(best_med == gm ? best_row : 0xffffffffu);
     if (lane == 0) {
         best_idx[s] = (int)gr;
         best_median[s] = __uint_as_float(gm);
@@ -1604,7 +1506,7 @@ static void launch_match_resolve(const uint8_t *desc, const float *ang, int ang_
     if (engine == 1) {  // workgroup-wide fixed point (round 4); columns are parked in LDS only for batches, and only once a pair needs a rescan
         const bool stage = cap <= pair_cols_lds(W) && npairs > 8;
         const size_t lds_wg = resolve_wg_lds_bytes(cap, stage, W);  // (the raised LDS limit: afv_match_prepare at afv_create)
-        hipLaunchKernelGGL(k_match_resolve_wg<W>, dim3(npairs), dim3(RWT), lds_wg, stream, desc, ang, ang_stride, nset, cap, pa, pb, topk, th, ratio,
+        hipLaunchKernelGGL(k_match_resolve_wg<W>, dim3(npairs), dim3(AFV_FP_T), lds_wg, stream, desc, ang, ang_stride, nset, cap, pa, pb, topk, th, ratio,
                            check_ori, match, nmatches, pair_base, stage ? 1 : 0, afv_debug_pass_cap);
         return;
     }

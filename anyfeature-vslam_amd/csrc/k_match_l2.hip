@@ -14,6 +14,7 @@
 //     64-row rounds (claim table, stop at the first conflict); a row whose 4 keys are used up is rescanned exactly
 //     (64 lanes over the columns).
 #include "afv_device.h"
+#include "afv_wave.h"
 #include "afv_runtime.h"  // the launchers below are declared there: a signature that drifts is a compile error, not a silent ABI mismatch
 
 #define L2T 256
@@ -21,13 +22,6 @@
 #define L2_CHUNK 32
 #define L2_NO_KEY 0xffffffffffffffffull
 #define L2_MAX_SIDE 8192
-
-#define L2_WAVE_SYNC()                                         \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); \
-    } while (0)
 
 __device__ __forceinline__ void l2_insert(unsigned long long (&k)[L2K], unsigned long long key) {
 #pragma unroll
@@ -219,16 +213,6 @@ __device__ __forceinline__ float l2_exact(const float *a, const float *b, int di
     return (float)s;
 }
 
-// FeatureMatcher.cc:1587-1599, rotFactor = 1/30 (:1579-1585): the bin rule of k_match.hip
-__device__ __forceinline__ int l2_rotation_bin(float a1, float a2) {
-    const float rot_factor = 1.0f / 30.0f;
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * rot_factor);
-    if (bin == 30) bin = 0;
-    return bin;
-}
-
 // ORI: the rotation histogram of SearchByBoW (FeatureMatcher.cc:578, 638, 657) over ang1[row] / ang2[column].  It never influences the greedy
 // walk (a removed match leaves its column taken), so the whole workgroup builds it after the walk, as k_match_resolve does.
 template <bool ORI>
@@ -305,7 +289,7 @@ __device__ __forceinline__ void l2_resolve_body(const float *__restrict__ d1, in
             }
         }
         if (type == 1) atomicMin(&s_claim[e0], lane);
-        L2_WAVE_SYNC();
+        WAVE_LDS_SYNC();
         bool stopper = type == 2;
         if (act && type != 2) {
             if (e0 >= 0 && s_claim[e0] < lane) stopper = true;
@@ -320,7 +304,7 @@ __device__ __forceinline__ void l2_resolve_body(const float *__restrict__ d1, in
         }
         nm += __popcll(__ballot(commit));
         if (type == 1) s_claim[e0] = 0x7fffffff;
-        L2_WAVE_SYNC();
+        WAVE_LDS_SYNC();
         if (stop == 0) {
             // exact rescan of row `pos` against the current matched set, 64 lanes over the columns
             const int q0 = pos;
@@ -357,7 +341,7 @@ __device__ __forceinline__ void l2_resolve_body(const float *__restrict__ d1, in
                 }
                 nm += 1;
             }
-            L2_WAVE_SYNC();
+            WAVE_LDS_SYNC();
             pos += 1;
         } else {
             pos += stop;
@@ -373,20 +357,12 @@ __device__ __forceinline__ void l2_resolve_body(const float *__restrict__ d1, in
         __syncthreads();
         for (int i = tid; i < n1; i += L2T) {
             const int c = out[i];
-            if (c >= 0) atomicAdd(&s_hist[l2_rotation_bin(ang1[i], ang2[c])], 1);
+            if (c >= 0) atomicAdd(&s_hist[afv_rotation_bin(ang1[i], ang2[c])], 1);
         }
         __syncthreads();
         if (tid == 0) {  // computeThreeMaxima (FeatureMatcher.cc:1631-1668)
-            int i1 = -1, i2 = -1, i3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < 30; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-                else if (sz > max3) { max3 = sz; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            s_keep[0] = i1; s_keep[1] = i2; s_keep[2] = i3;
+            const AfvMaxima3 mx = afv_three_maxima(s_hist);
+            s_keep[0] = mx.i1; s_keep[1] = mx.i2; s_keep[2] = mx.i3;
         }
         __syncthreads();
         const int i1 = s_keep[0], i2 = s_keep[1], i3 = s_keep[2];
@@ -394,7 +370,7 @@ __device__ __forceinline__ void l2_resolve_body(const float *__restrict__ d1, in
         for (int i = tid; i < n1; i += L2T) {  // the rows a thread visited above: its own out[] entries
             const int c = out[i];
             if (c >= 0) {
-                const int bin = l2_rotation_bin(ang1[i], ang2[c]);
+                const int bin = afv_rotation_bin(ang1[i], ang2[c]);
                 if (bin != i1 && bin != i2 && bin != i3) { out[i] = -1; ++dropped; }
             }
         }

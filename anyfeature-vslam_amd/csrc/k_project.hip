@@ -28,6 +28,7 @@
 // The grid arrives as cell_ptr + cell_ent (k_frame.hip builds it on the device): an entry carries the feature's index, position and
 // keyPtsSize, so a candidate costs ONE dependent load before its descriptor instead of two (index, then x / y / size).
 #include "afv_device.h"
+#include "afv_wave.h"
 #include "afv_runtime.h"  // the launchers below are declared there: a signature that drifts is a compile error, not a silent ABI mismatch
 #include "afv_jobs.h"
 
@@ -39,66 +40,8 @@
 #define P_NO_KEY 0xffffffffffffffffull
 #define P_MAX_FEATS 8192
 
-#define WAVE_LDS_SYNC()                                        \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); \
-    } while (0)
-
-
 __device__ __forceinline__ int key_dist(unsigned long long k) { return (int)(k >> 48); }
 __device__ __forceinline__ int key_idx(unsigned long long k) { return (int)(k & 0xffff); }
-
-__device__ __forceinline__ int proj_rotation_bin(float a1, float a2) {  // FeatureMatcher.cc:1587-1599
-    const float rot_factor = 1.0f / 30.0f;
-    float rot = a1 - a2;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * rot_factor);
-    if (bin == 30) bin = 0;
-    return bin;
-}
-
-template <int W>
-__device__ __forceinline__ int proj_hamming(const uint32_t *a, const uint32_t *b) {
-    int d = 0;
-#pragma unroll
-    for (int i = 0; i < W; ++i) d += __popc(a[i] ^ b[i]);
-    return d;
-}
-
-// wave-wide minimum on DPP (row shifts inside the rows of 16 lanes, then row_bcast15 / row_bcast31 carry the row results: no LDS
-// crossbar - the __shfl_xor butterfly of rounds 1-4 was six dependent ds_bpermute pairs per call); every lane receives the result
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#define AFV_MIN64_STEP(ctrl, rmask)                                                                                       \
-    {                                                                                                                     \
-        const unsigned lo_ = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)v, ctrl, rmask, 0xf, false);        \
-        const unsigned hi_ = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)(v >> 32), ctrl, rmask, 0xf, false); \
-        const unsigned long long t_ = ((unsigned long long)hi_ << 32) | lo_;                                              \
-        v = t_ < v ? t_ : v;                                                                                              \
-    }
-    AFV_MIN64_STEP(0x111, 0xf)  // row_shr:1
-    AFV_MIN64_STEP(0x112, 0xf)  // row_shr:2
-    AFV_MIN64_STEP(0x114, 0xf)  // row_shr:4
-    AFV_MIN64_STEP(0x118, 0xf)  // row_shr:8
-    AFV_MIN64_STEP(0x142, 0xa)  // row_bcast:15 into rows 1, 3
-    AFV_MIN64_STEP(0x143, 0xc)  // row_bcast:31 into rows 2, 3
-#undef AFV_MIN64_STEP
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-#define AFV_MIN32_STEP(ctrl, rmask) v = min(v, (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, ctrl, rmask, 0xf, false));
-    AFV_MIN32_STEP(0x111, 0xf)
-    AFV_MIN32_STEP(0x112, 0xf)
-    AFV_MIN32_STEP(0x114, 0xf)
-    AFV_MIN32_STEP(0x118, 0xf)
-    AFV_MIN32_STEP(0x142, 0xa)
-    AFV_MIN32_STEP(0x143, 0xc)
-#undef AFV_MIN32_STEP
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ int wave_sum_i32(int v) { return __builtin_amdgcn_readlane(afv_wave_incl_scan(v), 63); }
 
 struct Window {
     int cx0, cx1, cy0, cy1;
@@ -327,7 +270,7 @@ __device__ void topk_query(const DevProjJob &J, int q, int lane, int2 *s_list /*
         }
         PROJ_WAVE_WINDOW_DENSE(J, q, lane, s_list, {
             if (REC < 2 && J.occupied && J.occupied[idx]) continue;
-            unsigned long long key = make_key(proj_hamming<W>(qd, J.fdesc + (size_t)idx * W), c, kpos, idx);
+            unsigned long long key = make_key(afv_hamming<W>(qd, J.fdesc + (size_t)idx * W), c, kpos, idx);
             _Pragma("unroll") for (int s = 0; s < K; ++s) {
                 if (key < k[s]) {
                     const unsigned long long t = k[s];
@@ -338,12 +281,12 @@ __device__ void topk_query(const DevProjJob &J, int q, int lane, int2 *s_list /*
             ++visited;
         })
     }
-    visited = wave_sum_i32(visited);
+    visited = afv_wave_sum(visited);
     // K extraction rounds: the wave minimum of the lanes' heads (keys are unique: the feature is part of the key), the holder pops
     unsigned long long mine = P_NO_KEY;  // lane s ends up holding the query's s-th best key
 #pragma unroll
     for (int s = 0; s < K; ++s) {
-        const unsigned long long m = wave_min_u64(k[0]);
+        const unsigned long long m = afv_wave_min_u64(k[0]);
         if (lane == s) mine = m;
         if (k[0] == m && m != P_NO_KEY) {
 #pragma unroll
@@ -361,7 +304,7 @@ __device__ void topk_query(const DevProjJob &J, int q, int lane, int2 *s_list /*
             if (mine != P_NO_KEY) {
                 const int idx = key_idx(mine);
                 if (J.mode == 0) aux = __float_as_uint(J.size[idx]);
-                else if (J.check_ori) aux = (uint32_t)proj_rotation_bin(J.qangle[q], J.angle[idx]);
+                else if (J.check_ori) aux = (uint32_t)afv_rotation_bin(J.qangle[q], J.angle[idx]);
             }
             rec[8 + lane] = aux;
         }
@@ -404,7 +347,9 @@ __global__ __launch_bounds__(PT) void k_proj_topk(const DevProjJob *__restrict__
     else topk_query<16, K, REC>(J, q, lane, s_list[threadIdx.x >> 6]);
 }
 // one job, its record a kernel argument: a search against a resident frame uploads nothing ahead of the launch - the queries are read
-// straight from the caller's pinned staging arena (a few KB over the link, once)
+// straight from the caller's pinned staging arena (a few KB over the link, once).  (The other job-array kernels share their row-width
+// dispatch with their twin through a function of J - proj_resolve_wg_job, fuse_job, init_resolve_wg_job; this pair spells it out twice:
+// behind a function, in any form, the <PK, *> instantiations come out with 2 to 4 more scalar registers.)
 template <int K, int REC>
 __global__ __launch_bounds__(PT) void k_proj_topk1(const DevProjJob J) {
     __shared__ int2 s_list[PT / 64][PW_LIST];
@@ -578,7 +523,7 @@ __device__ void proj_resolve(const DevProjJob &J, int stage_cap) {
                 for (int i = 0; i < W; ++i) qd[i] = J.qdesc[(size_t)q0 * W + i];
                 PROJ_WAVE_WINDOW(J, q0, lane, {
                     if ((s_occ[idx >> 5] >> (idx & 31)) & 1u) continue;
-                    const unsigned long long key = make_key(proj_hamming<W>(qd, J.fdesc + (size_t)idx * W), c, kpos, idx);
+                    const unsigned long long key = make_key(afv_hamming<W>(qd, J.fdesc + (size_t)idx * W), c, kpos, idx);
                     if (key < k0) {
                         k1 = k0;
                         k0 = key;
@@ -587,8 +532,8 @@ __device__ void proj_resolve(const DevProjJob &J, int stage_cap) {
                     }
                 })
             }
-            const unsigned long long g0 = wave_min_u64(k0);
-            const unsigned long long g1 = wave_min_u64(k0 == g0 ? k1 : k0);
+            const unsigned long long g0 = afv_wave_min_u64(k0);
+            const unsigned long long g1 = afv_wave_min_u64(k0 == g0 ? k1 : k0);
             if (g0 != P_NO_KEY) {
                 const float best = (float)key_dist_of<W>(g0);
                 const int bidx = key_idx(g0);
@@ -602,7 +547,7 @@ __device__ void proj_resolve(const DevProjJob &J, int stage_cap) {
                         J.assign[bidx] = q0;
                         if (!J.qocc || J.qocc[q0]) s_occ[bidx >> 5] |= 1u << (bidx & 31);
                         if (J.mode == 1 && J.check_ori) {
-                            const int bin = proj_rotation_bin(J.qangle[q0], J.angle[bidx]);
+                            const int bin = afv_rotation_bin(J.qangle[q0], J.angle[bidx]);
                             J.orilist[2 * nori] = bidx;
                             J.orilist[2 * nori + 1] = bin;
                             s_hist[bin]++;
@@ -622,24 +567,16 @@ __device__ void proj_resolve(const DevProjJob &J, int stage_cap) {
         // filterMatchesWithOrientation (Pt flavour, FeatureMatcher.cc:1601-1613) over the accepted-match list
         __threadfence_block();
         WAVE_LDS_SYNC();
-        int i1 = -1, i2 = -1, i3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < 30; ++i) {
-            const int sz = s_hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-            else if (sz > max3) { max3 = sz; i3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+        const AfvMaxima3 mx = afv_three_maxima(s_hist);
         int dropped = 0;
         for (int i = lane; i < nori; i += 64) {
             const int b = J.orilist[2 * i + 1];
-            if (b != i1 && b != i2 && b != i3) {
+            if (b != mx.i1 && b != mx.i2 && b != mx.i3) {
                 J.assign[J.orilist[2 * i]] = -1;
                 ++dropped;
             }
         }
-        dropped = wave_sum_i32(dropped);
+        dropped = afv_wave_sum(dropped);
         nm -= dropped;
     }
 #ifdef AFV_PROJ_STATS
@@ -672,21 +609,7 @@ __global__ __launch_bounds__(PT) void k_proj_resolve(const DevProjJob *__restric
 //     the local-map mode a best key that passes the ratio test against the LAST key passes it against anything outside the list;
 //   * F.pts[c] ends up as the LAST query that took c (a query without observations does not block later ones, :108-110): atomic max over
 //     the final wants.
-#define PW_T 1024
-#define PW_NW (PW_T / 64)
-// "did any thread change something in this pass": ONE barrier.  Three rotating flags (the pass that writes flag p % 3 clears the one the
-// pass after next will use): __syncthreads_or goes through the device library's workgroup reduction (an LDS round plus two barriers).
-__device__ __forceinline__ bool wg_any_changed(bool changed, int pass, int *s_vote) {
-    if (__ballot(changed) && (threadIdx.x & 63) == 0) s_vote[pass % 3] = 1;
-    __syncthreads();
-    const bool any = s_vote[pass % 3] != 0;
-    if (threadIdx.x == 0) s_vote[(pass + 2) % 3] = 0;
-    return any;
-}
-#define PW_INF 0x7fffffff
-#define PW_WLIST 128
-#define PW_GUARD (-0x7fffffff)  // *nmatches when the pass guard trips (never observed; the host turns it into AFV_EHIP)
-
+// (threads, waiting list, guard value and the scaffolding shared with k_match_resolve_wg: afv_wave.h, AFV_FP_* / afv_wg_*)
 static inline size_t proj_wg_lds_bytes(int n, int nq, bool float_rows = false) {
     const size_t nr = ((size_t)n + 63) & ~(size_t)63, qr = ((size_t)nq + 63) & ~(size_t)63;
     return 3 * nr * 4 + qr * 16 /*keys*/ + qr * 4 /*meta*/ + qr * 4 /*query angle*/ + 3 * qr * 2 /*w1, w2, pin*/ + qr * 2 /*live*/ + qr /*flag*/ + 64 +
@@ -774,8 +697,8 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
     uint8_t *s_flag = reinterpret_cast<uint8_t *>(s_live + qr);               // 1 = asked for a rescan in the last pass, 2 = pinned by a rescan
     int2 *s_feat = reinterpret_cast<int2 *>(s_flag + qr + 64 - 8);            // float jobs only: the keys' features (qr and the 64 spare bytes keep it 8-byte aligned)
     __shared__ int s_hist[32];
-    __shared__ int s_nm, s_drop[3], s_first, s_part[PW_NW], s_cntw[PW_NW], s_guard, s_vote[3];
-    __shared__ unsigned short s_wlist[PW_WLIST];
+    __shared__ int s_nm, s_drop[3], s_first, s_part[AFV_FP_NW], s_cntw[AFV_FP_NW], s_guard, s_vote[3];
+    __shared__ unsigned short s_wlist[AFV_FP_WLIST];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid < 3) s_vote[tid] = 0;
 #ifdef AFV_PROJ_STATS
@@ -783,13 +706,13 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
     long long st_t1 = 0, st_t2 = 0, st_tr = 0;
     int st_conv = 0, st_steps = 0, st_adopt = 0, st_took = 0;
 #endif
-    for (int i = tid; i < 3 * nr; i += PW_T) s_claim[i] = PW_INF;
+    for (int i = tid; i < 3 * nr; i += AFV_FP_T) s_claim[i] = AFV_FP_INF;
     if (tid < 32) s_hist[tid] = 0;
     if (tid == 0) s_guard = 0;
     // live queries (valid, at least one candidate, best key within TH_HIGH) IN QUERY ORDER
     const int4 *grec = reinterpret_cast<const int4 *>(J.keys);
     int nlive = 0;
-    for (int q0 = 0; q0 < J.nq; q0 += PW_T) {
+    for (int q0 = 0; q0 < J.nq; q0 += AFV_FP_T) {
         const int q = q0 + tid;
         int4 ka = make_int4(-1, -1, -1, -1), kb = make_int4(0, 0, 0, 0);
         float qa = 0.0f;
@@ -801,18 +724,9 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
         bool live;
         if constexpr (W == 0) live = q < J.nq && (kb.z & 0xffff) != 0xffff && __int_as_float(ka.x) <= J.th;
         else live = (unsigned)ka.x != PROJ_NO_KEY32 && (float)((unsigned)ka.x >> 16) <= J.th;
-        const unsigned long long m = __ballot(live);
-        if (lane == 0) s_cntw[wv] = __popcll(m);
-        __syncthreads();
-        int off = nlive, tot = 0;
-#pragma unroll
-        for (int w = 0; w < PW_NW; ++w) {
-            const int cw = s_cntw[w];
-            off += w < wv ? cw : 0;
-            tot += cw;
-        }
+        const AfvSlot S = afv_wg_ordered_slot(live, nlive, s_cntw);
         if (live) {
-            const int slot = off + __popcll(m & ((1ull << lane) - 1ull));
+            const int slot = S.slot;
             s_live[slot] = (unsigned short)q;
             s_keys[slot] = ka;
             if constexpr (W == 0) s_feat[slot] = make_int2(kb.z, kb.w);
@@ -823,7 +737,7 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
             s_pin[slot] = -1;
             s_flag[slot] = 0;
         }
-        nlive += tot;
+        nlive += S.total;
         __syncthreads();
     }
 #ifdef AFV_PROJ_STATS
@@ -840,7 +754,7 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
         }
         int *R = s_claim + (pass % 3) * nr, *Wc = s_claim + ((pass + 1) % 3) * nr, *Z = s_claim + ((pass + 2) % 3) * nr;
         bool changed = false;
-        for (int li = tid; li < nlive; li += PW_T) {
+        for (int li = tid; li < nlive; li += AFV_FP_T) {
             const int w1 = s_w1[li], w2 = s_w2[li];
             const int flag = s_flag[li];
             const int meta = s_meta[li];
@@ -855,49 +769,15 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
                 s_flag[li] = rescan ? 1 : 0;
             }
             if (want >= 0 && meta < 0) atomicMin(&Wc[want], li);  // only a map point with observations blocks later queries
-            if (w2 >= 0) Z[w2] = PW_INF;  // what this query (maybe) put into Z two passes ago: Z is empty before it is written again
+            if (w2 >= 0) Z[w2] = AFV_FP_INF;  // what this query (maybe) put into Z two passes ago: Z is empty before it is written again
             s_w2[li] = (short)w1;
             s_w1[li] = (short)want;
             changed = changed || want != w1 || (rescan != ((flag & 1) != 0));
         }
-        if (wg_any_changed(changed, pass++, s_vote)) continue;
+        if (afv_wg_any_changed(changed, pass++, s_vote)) continue;
         // converged: Wc holds the claims of the final wants (so far).  The queries that asked for a rescan, in order
-        {
-            const bool waits = tid < nlive && (s_flag[tid] & 3) == 1;  // the first 1024 live queries are looked at per cycle
-            const unsigned long long bal = __ballot(waits);
-            if (lane == 0) s_cntw[wv] = __popcll(bal);
-            __syncthreads();
-            int off = 0, run = 0;
-#pragma unroll
-            for (int w = 0; w < PW_NW; ++w) {
-                const int cw = s_cntw[w];
-                off += w < wv ? cw : 0;
-                run += cw;
-            }
-            if (waits) {
-                const int slot = off + __popcll(bal & ((1ull << lane) - 1ull));
-                if (slot < PW_WLIST) s_wlist[slot] = (unsigned short)tid;
-            }
-            if (tid == 0) s_first = run;
-            __syncthreads();
-        }
-        const int nwait = s_first;
-        int nw = min(nwait, PW_WLIST);
-        if (nw == 0 && nlive > PW_T) {  // jobs above 1024 live queries: the waiting ones behind the first 1024, one at a time
-            __syncthreads();
-            if (tid == 0) s_first = PW_INF;
-            __syncthreads();
-            int mine = PW_INF;
-            for (int li = PW_T + tid; li < nlive; li += PW_T)
-                if ((s_flag[li] & 3) == 1) mine = min(mine, li);
-            if (mine != PW_INF) atomicMin(&s_first, mine);
-            __syncthreads();
-            if (s_first != PW_INF) {
-                if (tid == 0) s_wlist[0] = (unsigned short)s_first;
-                nw = 1;
-            }
-            __syncthreads();
-        }
+        const AfvWaiting Wt = afv_wg_collect_waiting(s_flag, nlive, s_cntw, &s_first, s_wlist);
+        const int nwait = Wt.nwait, nw = Wt.nw;
         if (nw == 0) break;
 #ifdef AFV_PROJ_STATS
         ++st_conv;
@@ -906,7 +786,7 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
         // exact rescans, one waiting query per wavefront (lanes over its window's cells), each against the claims of the queries BEFORE
         // it; adopted in order up to and including the first that takes a feature
         bool took = false;
-        for (int g0 = 0; g0 < nw && !took; g0 += PW_NW) {
+        for (int g0 = 0; g0 < nw && !took; g0 += AFV_FP_NW) {
             const int g = g0 + wv;
             int wr = -1;
             if (g < nw) {
@@ -938,7 +818,7 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
                     PROJ_WAVE_WINDOW(J, q0, lane, {
                         if (J.occupied && J.occupied[idx]) continue;
                         if (Wc[idx] < li) continue;
-                        const unsigned long long key = make_key(proj_hamming<W>(qd, J.fdesc + (size_t)idx * W), c, kpos, idx);
+                        const unsigned long long key = make_key(afv_hamming<W>(qd, J.fdesc + (size_t)idx * W), c, kpos, idx);
                         if (key < k0) {
                             k1 = k0;
                             k0 = key;
@@ -947,8 +827,8 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
                         }
                     })
                 }
-                const unsigned long long b0 = wave_min_u64(k0);
-                const unsigned long long b1 = wave_min_u64(k0 == b0 ? k1 : k0);
+                const unsigned long long b0 = afv_wave_min_u64(k0);
+                const unsigned long long b1 = afv_wave_min_u64(k0 == b0 ? k1 : k0);
                 if (b0 != P_NO_KEY) {
                     const float best = (float)key_dist_of<W>(b0);
                     const int bidx = key_idx(b0);
@@ -962,14 +842,9 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
             }
             if (lane == 0) s_part[wv] = wr;
             __syncthreads();
-            int nadopt = 0;
-#pragma unroll
-            for (int w = 0; w < PW_NW; ++w) {
-                if (g0 + w < nw && !took) {
-                    ++nadopt;
-                    took = s_part[w] >= 0;
-                }
-            }
+            const AfvAdopt Ad = afv_wg_adopt_verdict<AFV_FP_NW>(s_part, g0, nw);
+            const int nadopt = Ad.nadopt;
+            took = Ad.took;
             if (tid < nadopt) {
                 const int r = s_wlist[g0 + tid];
                 s_flag[r] = 2;
@@ -987,7 +862,7 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
 #endif
         // a taken feature enters the claims with the next pass (the pinned query's want changes from -1); if nothing was taken and every
         // waiting query was looked at, the converged state is the final one
-        if (!took && nwait <= PW_WLIST && nlive <= PW_T) break;
+        if (!took && nwait <= AFV_FP_WLIST && nlive <= AFV_FP_T) break;
     }
     __syncthreads();
 #ifdef AFV_PROJ_STATS
@@ -995,12 +870,12 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
 #endif
     // ---- F.pts, count ----
     int *A = s_claim;  // assign[feature] = last query that took it
-    for (int i = tid; i < nr; i += PW_T) A[i] = -1;
+    for (int i = tid; i < nr; i += AFV_FP_T) A[i] = -1;
     if (tid == 0) s_nm = 0;
     __syncthreads();
     int cnt = 0;
     const bool ori = J.mode == 1 && J.check_ori;
-    for (int li = tid; li < nlive; li += PW_T) {
+    for (int li = tid; li < nlive; li += AFV_FP_T) {
         const int w = (s_flag[li] & 2) ? (int)s_pin[li] : (int)s_w1[li];
         s_w1[li] = (short)w;
         if (w >= 0) {
@@ -1008,33 +883,24 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
             atomicMax(&A[w], q);
             ++cnt;
             if (ori) {  // updateRotationHistogram(rotHist, bestIdx2, LastFrame.mvKeysUn[i], CurrentFrame.mvKeysUn[bestIdx2]) (:1384-1385)
-                const int bin = proj_rotation_bin(s_qang[li], J.angle[w]);
+                const int bin = afv_rotation_bin(s_qang[li], J.angle[w]);
                 s_flag[li] = (uint8_t)bin;
                 atomicAdd(&s_hist[bin], 1);
             }
         }
     }
-    cnt = afv_wave_incl_scan(cnt);
-    if (lane == 63 && cnt) atomicAdd(&s_nm, cnt);
+    afv_wg_add_count(cnt, &s_nm);
     __syncthreads();
     if (ori) {
         // filterMatchesWithOrientation (Pt flavour, FeatureMatcher.cc:1601-1613): every accepted entry of a losing bin clears F.pts
         if (tid == 0) {
-            int i1 = -1, i2 = -1, i3 = -1, max1 = 0, max2 = 0, max3 = 0;
-            for (int i = 0; i < 30; ++i) {
-                const int sz = s_hist[i];
-                if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-                else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-                else if (sz > max3) { max3 = sz; i3 = i; }
-            }
-            if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-            else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-            s_drop[0] = i1; s_drop[1] = i2; s_drop[2] = i3;
+            const AfvMaxima3 mx = afv_three_maxima(s_hist);
+            s_drop[0] = mx.i1; s_drop[1] = mx.i2; s_drop[2] = mx.i3;
         }
         __syncthreads();
         const int i1 = s_drop[0], i2 = s_drop[1], i3 = s_drop[2];
         int dropped = 0;
-        for (int li = tid; li < nlive; li += PW_T) {
+        for (int li = tid; li < nlive; li += AFV_FP_T) {
             const int w = s_w1[li];
             if (w >= 0) {
                 const int b = s_flag[li];
@@ -1047,8 +913,8 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
         if (dropped) atomicSub(&s_nm, dropped);
         __syncthreads();
     }
-    for (int i = tid; i < J.n; i += PW_T) J.assign[i] = A[i];
-    if (tid == 0) *J.nmatches = s_guard ? PW_GUARD : s_nm;
+    for (int i = tid; i < J.n; i += AFV_FP_T) J.assign[i] = A[i];
+    if (tid == 0) *J.nmatches = s_guard ? AFV_FP_GUARD : s_nm;
 #ifdef AFV_PROJ_STATS
     if (tid == 0)
         printf("proj_resolve_wg: mode %d nq %d nlive %d passes %d convergences %d rescan_steps %d adopted %d took %d | x10ns: setup %lld fixedpoint %lld (rescans %lld) tail %lld\n",
@@ -1056,17 +922,16 @@ __device__ void proj_resolve_wg(const DevProjJob &J) {
 #endif
 }
 
-__global__ __launch_bounds__(PW_T) void k_proj_resolve_wg(const DevProjJob *__restrict__ jobs) {
+__device__ __forceinline__ void proj_resolve_wg_job(const DevProjJob &J) {
+    if (J.fdim) proj_resolve_wg<0>(J);
+    else if (J.words == 8) proj_resolve_wg<8>(J);
+    else proj_resolve_wg<16>(J);
+}
+__global__ __launch_bounds__(AFV_FP_T) void k_proj_resolve_wg(const DevProjJob *__restrict__ jobs) {
     const DevProjJob J = jobs[blockIdx.x];
-    if (J.fdim) proj_resolve_wg<0>(J);
-    else if (J.words == 8) proj_resolve_wg<8>(J);
-    else proj_resolve_wg<16>(J);
+    proj_resolve_wg_job(J);
 }
-__global__ __launch_bounds__(PW_T) void k_proj_resolve_wg1(const DevProjJob J) {
-    if (J.fdim) proj_resolve_wg<0>(J);
-    else if (J.words == 8) proj_resolve_wg<8>(J);
-    else proj_resolve_wg<16>(J);
-}
+__global__ __launch_bounds__(AFV_FP_T) void k_proj_resolve_wg1(const DevProjJob J) { proj_resolve_wg_job(J); }
 
 // ---------------- Fuse / SearchBySim3: independent queries, one wave each; first minimum in visiting order (:905) ----------------
 template <int W>
@@ -1101,30 +966,29 @@ __device__ void fuse_query(const DevProjJob &J, int q, int lane, int2 *s_list) {
             }
             unsigned long long key;
             if constexpr (W == 0) key = make_key_f32(proj_l2sqr(qrow, proj_frow(J, idx), J.fdim), epos, idx);
-            else key = make_key(proj_hamming<W>(qd, J.fdesc + (size_t)idx * W), c, kpos, idx);
+            else key = make_key(afv_hamming<W>(qd, J.fdesc + (size_t)idx * W), c, kpos, idx);
             k0 = key < k0 ? key : k0;
         })
     }
-    const unsigned long long g0 = wave_min_u64(k0);
+    const unsigned long long g0 = afv_wave_min_u64(k0);
     if (lane == 0) J.assign[q] = (g0 != P_NO_KEY && (float)key_dist_of<W>(g0) <= J.th) ? key_idx(g0) : -1;
 }
 
-__global__ __launch_bounds__(PT) void k_match_fuse(const DevProjJob *__restrict__ jobs) {
-    __shared__ int2 s_list[PT / 64][PW_LIST];
-    const DevProjJob J = jobs[blockIdx.y];
+__device__ __forceinline__ void fuse_job(const DevProjJob &J, int2 (*s_list)[PW_LIST]) {
     const int lane = threadIdx.x & 63, q = blockIdx.x * (PT / 64) + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     if (q >= J.nq) return;
     if (J.fdim) fuse_query<0>(J, q, lane, s_list[threadIdx.x >> 6]);
     else if (J.words == 8) fuse_query<8>(J, q, lane, s_list[threadIdx.x >> 6]);
     else fuse_query<16>(J, q, lane, s_list[threadIdx.x >> 6]);
 }
+__global__ __launch_bounds__(PT) void k_match_fuse(const DevProjJob *__restrict__ jobs) {
+    __shared__ int2 s_list[PT / 64][PW_LIST];
+    const DevProjJob J = jobs[blockIdx.y];
+    fuse_job(J, s_list);
+}
 __global__ __launch_bounds__(PT) void k_match_fuse1(const DevProjJob J) {
     __shared__ int2 s_list[PT / 64][PW_LIST];
-    const int lane = threadIdx.x & 63, q = blockIdx.x * (PT / 64) + __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    if (q >= J.nq) return;
-    if (J.fdim) fuse_query<0>(J, q, lane, s_list[threadIdx.x >> 6]);
-    else if (J.words == 8) fuse_query<8>(J, q, lane, s_list[threadIdx.x >> 6]);
-    else fuse_query<16>(J, q, lane, s_list[threadIdx.x >> 6]);
+    fuse_job(J, s_list);
 }
 
 // ---------------- SearchForInitialization (FeatureMatcher.cc:399-557, active part :480-556) ----------------
@@ -1208,7 +1072,7 @@ __device__ void init_resolve(const DevProjJob &J, unsigned char *s_tables /* 6 x
 #pragma unroll
                     for (int i = 0; i < W; ++i) qd[i] = J.qdesc[(size_t)q * W + i];
                     PROJ_WAVE_WINDOW(J, q, lane, {
-                        const int d = proj_hamming<W>(qd, J.fdesc + (size_t)idx * W);
+                        const int d = afv_hamming<W>(qd, J.fdesc + (size_t)idx * W);
                         if ((int)s_mdist[idx] <= d) continue;
                         const unsigned long long kk = make_key(d, c, kpos, idx);
                         if (kk < k0) {
@@ -1219,8 +1083,8 @@ __device__ void init_resolve(const DevProjJob &J, unsigned char *s_tables /* 6 x
                         }
                     })
                 }
-                g0 = wave_min_u64(k0);
-                g1 = wave_min_u64(k0 == g0 ? k1 : k0);
+                g0 = afv_wave_min_u64(k0);
+                g1 = afv_wave_min_u64(k0 == g0 ? k1 : k0);
             }
             if (g0 == P_NO_KEY) continue;
             const float best = (float)key_dist_of<W>(g0);
@@ -1234,7 +1098,7 @@ __device__ void init_resolve(const DevProjJob &J, unsigned char *s_tables /* 6 x
                     s_m21[bidx] = (m21_t)q;
                     s_mdist[bidx] = (md_t)key_dist_of<W>(g0);
                     if (J.check_ori) {
-                        const int bin = proj_rotation_bin(J.qangle[q], J.angle[bidx]);  // F1 keypoint first (:543)
+                        const int bin = afv_rotation_bin(J.qangle[q], J.angle[bidx]);  // F1 keypoint first (:543)
                         J.orilist[2 * nori] = q;
                         J.orilist[2 * nori + 1] = bin;
                         s_hist[bin]++;
@@ -1249,18 +1113,10 @@ __device__ void init_resolve(const DevProjJob &J, unsigned char *s_tables /* 6 x
     WAVE_LDS_SYNC();
     if (J.check_ori) {
         // filterMatchesWithOrientation (int flavour, :1615-1629): histogram over every accepted match, stolen ones included
-        int i1 = -1, i2 = -1, i3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < 30; ++i) {
-            const int sz = s_hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-            else if (sz > max3) { max3 = sz; i3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
+        const AfvMaxima3 mx = afv_three_maxima(s_hist);
         for (int i = lane; i < nori; i += 64) {
             const int b = J.orilist[2 * i + 1];
-            if (b != i1 && b != i2 && b != i3) J.assign[J.orilist[2 * i]] = -1;
+            if (b != mx.i1 && b != mx.i2 && b != mx.i3) J.assign[J.orilist[2 * i]] = -1;
         }
         __threadfence_block();
         WAVE_LDS_SYNC();
@@ -1268,7 +1124,7 @@ __device__ void init_resolve(const DevProjJob &J, unsigned char *s_tables /* 6 x
     // nMatches = entries still standing (accepts minus steals minus orientation drops)
     int cnt = 0;
     for (int q = lane; q < J.nq; q += 64) cnt += J.assign[q] >= 0;
-    cnt = wave_sum_i32(cnt);
+    cnt = afv_wave_sum(cnt);
     if (lane == 0) *J.nmatches = cnt;
 }
 
@@ -1292,10 +1148,6 @@ __global__ __launch_bounds__(64) void k_init_resolve(const DevProjJob *__restric
 // gate(i, f, d) = "some wanter j < i of f has d_j <= d" follows exactly from them in all but one constellation (an earlier wanter
 // farther than d, the closest wanter not earlier than i, three or more wanters), which falls back to a scan of the wants of the
 // queries before i (double-buffered by pass parity, so the scan reads the previous pass consistently).
-#define IW_T 1024
-#define IW_NW (IW_T / 64)
-#define IW_INF 0x7fffffff
-#define IW_WLIST 128
 static inline size_t init_wg_lds_bytes(int n, int nq) {
     const size_t nr = ((size_t)n + 63) & ~(size_t)63, qr = ((size_t)nq + 63) & ~(size_t)63;
     return 9 * nr * 4 + qr * 32 /*keys*/ + qr * 4 /*ncand*/ + 4 * qr * 2 /*want, dist x 2 buffers*/ + 2 * qr * 2 /*pin*/ + qr * 2 /*live*/ + qr /*flag*/ + 64;
@@ -1307,13 +1159,13 @@ struct InitState {
 };
 __device__ __forceinline__ bool init_gate(const InitState &S, int li, int f, int d) {
     const int e = S.E[f];
-    if (e == IW_INF) return false;
+    if (e == AFV_FP_INF) return false;
     if ((e >> 16) >= li) return false;                 // nobody before li wants f
     if ((e & 0xffff) <= d) return true;                // the earliest wanter already holds it at <= d
     const int m = S.M[f];
     if ((m & 0xffff) < li) return (m >> 16) <= d;      // the closest wanter of all is before li
     if (S.C[f] == 2) return false;                     // two wanters: only the earliest is before li, and it is farther than d
-    int mind = IW_INF;                                 // exact: the closest wanter among the queries before li
+    int mind = AFV_FP_INF;                                 // exact: the closest wanter among the queries before li
     for (int j = 0; j < li; ++j)
         if (S.want[j] == f) mind = min(mind, (int)S.dist[j]);
     return mind <= d;
@@ -1332,17 +1184,17 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
     unsigned short *s_live = reinterpret_cast<unsigned short *>(s_pind + qr);
     uint8_t *s_flag = reinterpret_cast<uint8_t *>(s_live + qr);
     __shared__ int s_hist[32];
-    __shared__ int s_nm, s_drop[3], s_first, s_part[IW_NW], s_partd[IW_NW], s_cntw[IW_NW], s_guard, s_vote[3];
-    __shared__ unsigned short s_wlist[IW_WLIST];
+    __shared__ int s_nm, s_drop[3], s_first, s_part[AFV_FP_NW], s_partd[AFV_FP_NW], s_cntw[AFV_FP_NW], s_guard, s_vote[3];
+    __shared__ unsigned short s_wlist[AFV_FP_WLIST];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (tid < 3) s_vote[tid] = 0;
-    for (int i = tid; i < 9 * nr; i += IW_T) s_E[i] = (i >= 6 * nr) ? 0 : IW_INF;
-    for (int q = tid; q < J.nq; q += IW_T) J.assign[q] = -1;
+    for (int i = tid; i < 9 * nr; i += AFV_FP_T) s_E[i] = (i >= 6 * nr) ? 0 : AFV_FP_INF;
+    for (int q = tid; q < J.nq; q += AFV_FP_T) J.assign[q] = -1;
     if (tid < 32) s_hist[tid] = 0;
     if (tid == 0) s_guard = 0;
     const int4 *grec = reinterpret_cast<const int4 *>(J.keys);
     int nlive = 0;
-    for (int q0 = 0; q0 < J.nq; q0 += IW_T) {
+    for (int q0 = 0; q0 < J.nq; q0 += AFV_FP_T) {
         const int q = q0 + tid;
         int4 ka = make_int4(-1, -1, -1, -1), kb = ka;
         int nc = 0;
@@ -1352,18 +1204,9 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
             nc = J.ncand[q];
         }
         const bool live = (unsigned)ka.x != PROJ_NO_KEY32 && (float)((unsigned)ka.x >> 16) <= J.th;
-        const unsigned long long m = __ballot(live);
-        if (lane == 0) s_cntw[wv] = __popcll(m);
-        __syncthreads();
-        int off = nlive, tot = 0;
-#pragma unroll
-        for (int w = 0; w < IW_NW; ++w) {
-            const int cw = s_cntw[w];
-            off += w < wv ? cw : 0;
-            tot += cw;
-        }
+        const AfvSlot S = afv_wg_ordered_slot(live, nlive, s_cntw);
         if (live) {
-            const int slot = off + __popcll(m & ((1ull << lane) - 1ull));
+            const int slot = S.slot;
             s_live[slot] = (unsigned short)q;
             s_keys[2 * slot] = ka;
             s_keys[2 * slot + 1] = kb;
@@ -1376,7 +1219,7 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
             s_pind[slot] = 0;
             s_flag[slot] = 0;
         }
-        nlive += tot;
+        nlive += S.total;
         __syncthreads();
     }
     int pass = 0;
@@ -1392,7 +1235,7 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
         InitState S{s_E + ir * nr, s_M + ir * nr, s_C + ir * nr, s_want + cur * qr, s_dist + cur * qr};
         int *WE = s_E + iw * nr, *WM = s_M + iw * nr, *WC = s_C + iw * nr;
         bool changed = false;
-        for (int li = tid; li < nlive; li += IW_T) {
+        for (int li = tid; li < nlive; li += AFV_FP_T) {
             const int w1 = S.want[li], w2 = s_want[nxt * qr + li];
             const int flag = s_flag[li];
             int want = -1, dw = 0;
@@ -1443,8 +1286,8 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
                 atomicAdd(&WC[want], 1);
             }
             if (w2 >= 0) {
-                s_E[iz * nr + w2] = IW_INF;
-                s_M[iz * nr + w2] = IW_INF;
+                s_E[iz * nr + w2] = AFV_FP_INF;
+                s_M[iz * nr + w2] = AFV_FP_INF;
                 s_C[iz * nr + w2] = 0;
             }
             const int dprev = S.dist[li];
@@ -1452,48 +1295,14 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
             s_dist[nxt * qr + li] = (short)dw;
             changed = changed || want != w1 || (want >= 0 && dw != dprev) || (rescan != ((flag & 1) != 0));
         }
-        if (wg_any_changed(changed, pass++, s_vote)) continue;
-        {
-            const bool waits = tid < nlive && (s_flag[tid] & 3) == 1;
-            const unsigned long long bal = __ballot(waits);
-            if (lane == 0) s_cntw[wv] = __popcll(bal);
-            __syncthreads();
-            int off = 0, run = 0;
-#pragma unroll
-            for (int w = 0; w < IW_NW; ++w) {
-                const int cw = s_cntw[w];
-                off += w < wv ? cw : 0;
-                run += cw;
-            }
-            if (waits) {
-                const int slot = off + __popcll(bal & ((1ull << lane) - 1ull));
-                if (slot < IW_WLIST) s_wlist[slot] = (unsigned short)tid;
-            }
-            if (tid == 0) s_first = run;
-            __syncthreads();
-        }
-        const int nwait = s_first;
-        int nw = min(nwait, IW_WLIST);
-        if (nw == 0 && nlive > IW_T) {
-            __syncthreads();
-            if (tid == 0) s_first = IW_INF;
-            __syncthreads();
-            int mine = IW_INF;
-            for (int li = IW_T + tid; li < nlive; li += IW_T)
-                if ((s_flag[li] & 3) == 1) mine = min(mine, li);
-            if (mine != IW_INF) atomicMin(&s_first, mine);
-            __syncthreads();
-            if (s_first != IW_INF) {
-                if (tid == 0) s_wlist[0] = (unsigned short)s_first;
-                nw = 1;
-            }
-            __syncthreads();
-        }
+        if (afv_wg_any_changed(changed, pass++, s_vote)) continue;
+        const AfvWaiting Wt = afv_wg_collect_waiting(s_flag, nlive, s_cntw, &s_first, s_wlist);
+        const int nwait = Wt.nwait, nw = Wt.nw;
         if (nw == 0) break;
         // the state the rescans read: the arrays written by the pass that just converged, the wants it produced
         InitState F{s_E + iw * nr, s_M + iw * nr, s_C + iw * nr, s_want + nxt * qr, s_dist + nxt * qr};
         bool took = false;
-        for (int g0 = 0; g0 < nw && !took; g0 += IW_NW) {
+        for (int g0 = 0; g0 < nw && !took; g0 += AFV_FP_NW) {
             const int g = g0 + wv;
             int wr = -1, wd = 0;
             if (g < nw) {
@@ -1509,7 +1318,7 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
                 }
                 unsigned long long k0 = P_NO_KEY, k1 = P_NO_KEY;
                 PROJ_WAVE_WINDOW(J, q0, lane, {
-                    const int d = proj_hamming<W>(qd, J.fdesc + (size_t)idx * W);
+                    const int d = afv_hamming<W>(qd, J.fdesc + (size_t)idx * W);
                     if (init_gate(F, li, idx, d)) continue;
                     const unsigned long long kk = make_key(d, c, kpos, idx);
                     if (kk < k0) {
@@ -1519,8 +1328,8 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
                         k1 = kk;
                     }
                 })
-                const unsigned long long b0 = wave_min_u64(k0);
-                const unsigned long long b1 = wave_min_u64(k0 == b0 ? k1 : k0);
+                const unsigned long long b0 = afv_wave_min_u64(k0);
+                const unsigned long long b1 = afv_wave_min_u64(k0 == b0 ? k1 : k0);
                 if (b0 != P_NO_KEY) {
                     const float best = (float)key_dist(b0);
                     const float best2 = b1 == P_NO_KEY ? 3.402823466e+38f : (float)key_dist(b1);
@@ -1535,14 +1344,9 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
                 s_partd[wv] = wd;
             }
             __syncthreads();
-            int nadopt = 0;
-#pragma unroll
-            for (int w = 0; w < IW_NW; ++w) {
-                if (g0 + w < nw && !took) {
-                    ++nadopt;
-                    took = s_part[w] >= 0;
-                }
-            }
+            const AfvAdopt Ad = afv_wg_adopt_verdict<AFV_FP_NW>(s_part, g0, nw);
+            const int nadopt = Ad.nadopt;
+            took = Ad.took;
             if (tid < nadopt) {
                 const int r = s_wlist[g0 + tid];
                 s_flag[r] = 2;
@@ -1551,7 +1355,7 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
             }
             __syncthreads();
         }
-        if (!took && nwait <= IW_WLIST && nlive <= IW_T) break;
+        if (!took && nwait <= AFV_FP_WLIST && nlive <= AFV_FP_T) break;
     }
     __syncthreads();
     // ---- matches: a query keeps its feature iff it is the closest (= last) of the feature's holders ----
@@ -1561,7 +1365,7 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
     if (tid == 0) s_nm = 0;
     __syncthreads();
     int cnt = 0;
-    for (int li = tid; li < nlive; li += IW_T) {
+    for (int li = tid; li < nlive; li += AFV_FP_T) {
         const int w = (s_flag[li] & 2) ? (int)s_pin[li] : (int)fw[li];
         int keep = -1, bin = 31;
         if (w >= 0) {
@@ -1569,7 +1373,7 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
             // a pinned answer of the last adoption round that took nothing is -1; one that took something was followed by a pass
             if ((FM[w] & 0xffff) == li) keep = w;
             if (J.check_ori) {
-                bin = proj_rotation_bin(J.qangle[q], J.angle[w]);  // F1 keypoint first (:543); stolen matches stay in the histogram
+                bin = afv_rotation_bin(J.qangle[q], J.angle[w]);  // F1 keypoint first (:543); stolen matches stay in the histogram
                 atomicAdd(&s_hist[bin], 1);
             }
         }
@@ -1578,19 +1382,11 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
     }
     __syncthreads();
     if (J.check_ori && tid == 0) {
-        int i1 = -1, i2 = -1, i3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < 30; ++i) {
-            const int sz = s_hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-            else if (sz > max3) { max3 = sz; i3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) { i3 = -1; }
-        s_drop[0] = i1; s_drop[1] = i2; s_drop[2] = i3;
+        const AfvMaxima3 mx = afv_three_maxima(s_hist);
+        s_drop[0] = mx.i1; s_drop[1] = mx.i2; s_drop[2] = mx.i3;
     }
     __syncthreads();
-    for (int li = tid; li < nlive; li += IW_T) {
+    for (int li = tid; li < nlive; li += AFV_FP_T) {
         int keep = s_pin[li];
         if (keep >= 0 && J.check_ori) {
             const int b = s_flag[li];
@@ -1601,21 +1397,20 @@ __device__ void init_resolve_wg(const DevProjJob &J) {
             ++cnt;
         }
     }
-    cnt = afv_wave_incl_scan(cnt);
-    if (lane == 63 && cnt) atomicAdd(&s_nm, cnt);
+    afv_wg_add_count(cnt, &s_nm);
     __syncthreads();
-    if (tid == 0) *J.nmatches = s_guard ? PW_GUARD : s_nm;
+    if (tid == 0) *J.nmatches = s_guard ? AFV_FP_GUARD : s_nm;
 }
 
-__global__ __launch_bounds__(IW_T) void k_init_resolve_wg(const DevProjJob *__restrict__ jobs) {
+__device__ __forceinline__ void init_resolve_wg_job(const DevProjJob &J) {
+    if (J.words == 8) init_resolve_wg<8>(J);
+    else init_resolve_wg<16>(J);
+}
+__global__ __launch_bounds__(AFV_FP_T) void k_init_resolve_wg(const DevProjJob *__restrict__ jobs) {
     const DevProjJob J = jobs[blockIdx.x];
-    if (J.words == 8) init_resolve_wg<8>(J);
-    else init_resolve_wg<16>(J);
+    init_resolve_wg_job(J);
 }
-__global__ __launch_bounds__(IW_T) void k_init_resolve_wg1(const DevProjJob J) {
-    if (J.words == 8) init_resolve_wg<8>(J);
-    else init_resolve_wg<16>(J);
-}
+__global__ __launch_bounds__(AFV_FP_T) void k_init_resolve_wg1(const DevProjJob J) { init_resolve_wg_job(J); }
 
 // ---------------- ranking + ordered phase in ONE launch (a single job whose record is the kernel argument) ----------------
 // A search against a resident frame is two dependent launches of a few microseconds each; the second one's dispatch and prologue are as long
@@ -1624,10 +1419,10 @@ __global__ __launch_bounds__(IW_T) void k_init_resolve_wg1(const DevProjJob J) {
 // wave's stores drained by the barrier -> ONE lane: agent-scope release, ticket; the last arriver: ONE agent-scope acquire -> barrier
 // -> plain loads) goes on as the fixed-point workgroup.  The ticket is zero at rest: the last arriver re-arms it.
 template <int KIND>  // 0 = projection (PK keys, REC 1), 1 = initialization (IK keys, REC 3)
-__global__ __launch_bounds__(PW_T) void k_proj_search1(const DevProjJob J, int *__restrict__ ticket) {
-    __shared__ int2 s_list[PW_NW][PW_LIST];
+__global__ __launch_bounds__(AFV_FP_T) void k_proj_search1(const DevProjJob J, int *__restrict__ ticket) {
+    __shared__ int2 s_list[AFV_FP_NW][PW_LIST];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int q = (int)blockIdx.x * PW_NW + wv;
+    const int q = (int)blockIdx.x * AFV_FP_NW + wv;
     if (q < J.nq) {  // wave-uniform
         if (KIND == 0) {  // (binary rows only: float jobs take the two-launch form - their instantiations would push this kernel into spilling)
             if (J.words == 8) topk_query<8, PK, 1>(J, q, lane, s_list[wv]);
@@ -1665,7 +1460,7 @@ __global__ __launch_bounds__(PW_T) void k_proj_search1(const DevProjJob J, int *
 extern "C" int afv_project_prepare(void) {
     // the one-launch search keeps 32 KB of static LDS for the ranking phase's candidate lists (16 wavefronts x PW_LIST x 8 bytes): its
     // dynamic share is what is left of the 160 KB of a CU, and that is the budget every engine is held to
-    const int want = 150 * 1024 - (int)sizeof(int2) * PW_NW * PW_LIST;
+    const int want = 150 * 1024 - (int)sizeof(int2) * AFV_FP_NW * PW_LIST;
     bool ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_proj_resolve_wg), hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess;
     ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_init_resolve_wg), hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess && ok;
     ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_proj_resolve_wg1), hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess && ok;
@@ -1674,7 +1469,7 @@ extern "C" int afv_project_prepare(void) {
     ok = hipFuncSetAttribute(reinterpret_cast<const void *>(k_proj_search1<1>), hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess && ok;
     if (!ok) (void)hipGetLastError();
     // dynamic bytes a job may ask for (the kernels' static arrays take about 1 KB more); without the raised limit: what every kernel gets
-    return ok ? want - 2048 : 62 * 1024 - (int)sizeof(int2) * PW_NW * PW_LIST;
+    return ok ? want - 2048 : 62 * 1024 - (int)sizeof(int2) * AFV_FP_NW * PW_LIST;
 }
 extern "C" size_t afv_project_wg_lds(int kind_init, int n, int nq, int float_rows) {
     return kind_init ? init_wg_lds_bytes(n, nq) : proj_wg_lds_bytes(n, nq, float_rows != 0);
@@ -1686,15 +1481,15 @@ extern "C" void afv_launch_match_init(const DevProjJob *jobs, int njobs, int max
                                       hipStream_t stream) {
     const dim3 tg((max_nq + PT / 64 - 1) / (PT / 64), njobs);
     if (wg_lds && one && ticket) {  // ranking + ordered phase in one launch
-        hipLaunchKernelGGL(k_proj_search1<1>, dim3(std::max((max_nq + PW_NW - 1) / PW_NW, 1)), dim3(PW_T), wg_lds, stream, *one, ticket);
+        hipLaunchKernelGGL(k_proj_search1<1>, dim3(std::max((max_nq + AFV_FP_NW - 1) / AFV_FP_NW, 1)), dim3(AFV_FP_T), wg_lds, stream, *one, ticket);
         return;
     }
     if (wg_lds && one) {
         if (max_nq > 0) hipLaunchKernelGGL((k_proj_topk1<IK, 3>), tg, dim3(PT), 0, stream, *one);
-        hipLaunchKernelGGL(k_init_resolve_wg1, dim3(1), dim3(IW_T), wg_lds, stream, *one);
+        hipLaunchKernelGGL(k_init_resolve_wg1, dim3(1), dim3(AFV_FP_T), wg_lds, stream, *one);
     } else if (wg_lds) {
         if (max_nq > 0) hipLaunchKernelGGL((k_proj_topk<IK, 3>), tg, dim3(PT), 0, stream, jobs);
-        hipLaunchKernelGGL(k_init_resolve_wg, dim3(njobs), dim3(IW_T), wg_lds, stream, jobs);
+        hipLaunchKernelGGL(k_init_resolve_wg, dim3(njobs), dim3(AFV_FP_T), wg_lds, stream, jobs);
     } else {
         if (max_nq > 0) hipLaunchKernelGGL((k_proj_topk<IK, 2>), tg, dim3(PT), 0, stream, jobs);
         hipLaunchKernelGGL(k_init_resolve, dim3(njobs), dim3(64), 0, stream, jobs);
@@ -1713,17 +1508,17 @@ extern "C" void afv_launch_match_projection(const DevProjJob *jobs, int njobs, i
                                             hipStream_t stream) {
     const dim3 tg((max_nq + PT / 64 - 1) / (PT / 64), njobs);
     if (wg_lds && one && ticket) {  // ranking + ordered phase in one launch
-        hipLaunchKernelGGL(k_proj_search1<0>, dim3(std::max((max_nq + PW_NW - 1) / PW_NW, 1)), dim3(PW_T), wg_lds, stream, *one, ticket);
+        hipLaunchKernelGGL(k_proj_search1<0>, dim3(std::max((max_nq + AFV_FP_NW - 1) / AFV_FP_NW, 1)), dim3(AFV_FP_T), wg_lds, stream, *one, ticket);
         return;
     }
     if (wg_lds && one) {
         if (max_nq > 0) hipLaunchKernelGGL((k_proj_topk1<PK, 1>), tg, dim3(PT), 0, stream, *one);
-        hipLaunchKernelGGL(k_proj_resolve_wg1, dim3(1), dim3(PW_T), wg_lds, stream, *one);
+        hipLaunchKernelGGL(k_proj_resolve_wg1, dim3(1), dim3(AFV_FP_T), wg_lds, stream, *one);
         return;
     }
     if (wg_lds) {
         if (max_nq > 0) hipLaunchKernelGGL((k_proj_topk<PK, 1>), tg, dim3(PT), 0, stream, jobs);
-        hipLaunchKernelGGL(k_proj_resolve_wg, dim3(njobs), dim3(PW_T), wg_lds, stream, jobs);
+        hipLaunchKernelGGL(k_proj_resolve_wg, dim3(njobs), dim3(AFV_FP_T), wg_lds, stream, jobs);
         return;
     }
     if (max_nq > 0) hipLaunchKernelGGL((k_proj_topk<PK, 0>), tg, dim3(PT), 0, stream, jobs);

@@ -13,6 +13,7 @@
 //      per-element test (float)SAD >= 1.5f * 1.4f * median.
 //   3. k_stereo_rgbd — the depth gather, one thread per feature.
 #include "afv_device.h"
+#include "afv_wave.h"
 #include "afv_runtime.h"  // the launchers below are declared there: a signature that drifts is a compile error
 
 #define ST_THREADS 256
