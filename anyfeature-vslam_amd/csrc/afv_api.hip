@@ -1,7 +1,8 @@
 // afv_api.hip — host runtime behind the C-ABI of include/afv_hip.h: the context and what does not belong to one pipeline.
-// Owns the HIP streams and the device scratch of one context (create / destroy), its settings and the stage profile; the brute-force,
-// L2 and projection matchers, ComputeDistinctiveDescriptors and the vocabulary.  The ORB32 extractor's host side (geometry, staging,
-// the kernel pipeline, its entry points) is afv_extract.hip; the BoW-guided matchers are afv_match_jobs.hip.
+// Owns the HIP streams and the device scratch of one context (create / destroy), its settings and the stage profile; the brute-force pair
+// and L2 matchers, ComputeDistinctiveDescriptors and the vocabulary.  The ORB32 extractor's host side (geometry, staging, the kernel
+// pipeline, its entry points) is afv_extract.hip; the BoW-guided matchers are afv_match_jobs.hip; the projection searches are
+// afv_project.hip.
 // No CPU fallback exists: without a HIP device afv_create fails with AFV_ENODEV.
 #include "afv_runtime.h"
 
@@ -341,11 +342,11 @@ extern "C" int afv_match_triangulation(afv_ctx *c, const afv_tri_job *jobs, int 
     return guarded(c, [&] { return afv_match_triangulation_impl(c, jobs, njobs, match12, nmatches); });
 }
 
-// a pair whose fixed point hit its pass guard carries nmatches = -0x7fffffff (k_match_resolve_wg): entry points that hand results to the
+// a pair whose fixed point hit its pass guard carries nmatches = AFV_PASS_GUARD (k_match_resolve_wg): entry points that hand results to the
 // host report it (never observed outside the test hook afv_debug_pass_cap)
 int afv_check_resolve_guard(afv_ctx *c, const int32_t *nmatches, int n) {
     for (int i = 0; i < n; ++i)
-        if (nmatches[i] == -0x7fffffff) {
+        if (nmatches[i] == AFV_PASS_GUARD) {
             c->last_error = "pair matcher: the fixed point of pair " + std::to_string(i) + " hit its pass guard; afv_set_match_resolve(ctx, 0) selects the ordered walk";
             return AFV_EHIP;
         }
@@ -445,7 +446,7 @@ static int afv_match_l2_impl(afv_ctx *c, const float *desc1, int n1, const float
     const size_t ok = b.reserve_scratch(afv_match_l2_scratch_bytes(n1, n2, &ntiles, &cols_per_tile));
     const int rc = ensure_match_buffer(c, b.h.size());
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, b.upload(in_bytes));
     const float *p1 = reinterpret_cast<const float *>(c->d_match + o1), *p2 = reinterpret_cast<const float *>(c->d_match + o2);
     const uint8_t *pv1 = valid1 ? c->d_match + ov1 : nullptr, *pv2 = valid2 ? c->d_match + ov2 : nullptr;
     int *pout = reinterpret_cast<int *>(c->d_match + oo), *pn = reinterpret_cast<int *>(c->d_match + on);
@@ -454,8 +455,7 @@ static int afv_match_l2_impl(afv_ctx *c, const float *desc1, int n1, const float
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, b.fetch(match12, oo, (size_t)n1 * 4, c->stream));
     HIPCHK(c, b.fetch(nmatches, on, 4, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.finish();
+    HIPCHK(c, b.wait());
     return AFV_OK;
 }
 extern "C" int afv_match_l2(afv_ctx *c, const float *desc1, int n1, const float *desc2, int n2, int dim, const uint8_t *valid1,
@@ -502,325 +502,6 @@ extern "C" int afv_match_l2_pairs_device(afv_ctx *c, const float *d_desc, const 
     });
 }
 
-// ---- projection-guided matching ----
-// One implementation behind afv_match_projection / _fuse / _initialization / _sim3 (host arrays on both sides) and the afv_frame_* forms
-// (afv_frame.hip: the feature side, its grid and possibly the queries' descriptors are already on the device: `dev`).  The grid of
-// Frame::AssignFeaturesToGrid is built ON THE DEVICE in both cases (k_frame_grid): the host-array form uploads x / y / size and runs the
-// same kernel a resident frame ran when it was extracted.
-int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, int32_t *assign, int32_t *nmatches, int kind,
-                              const ProjFeatureSide *dev) {
-    const bool fuse = kind == AFV_KIND_FUSE, per_query = kind != AFV_KIND_PROJ;
-    if (!c || !jobs || njobs < 1 || !assign || !nmatches) return AFV_EINVAL;
-    if (dev && njobs != 1) return AFV_EINVAL;
-    PointQueries *const pq = dev ? dev->pq : nullptr;  // the query side comes from resident map points (afv_points.hip)
-    for (int i = 0; i < njobs; ++i) {
-        const afv_proj_job &j = jobs[i];
-        if (j.n < 0 || j.n > AFV_MAX_SIDE || j.nq < 0 || j.nq > 65535) return AFV_EINVAL;
-        if (j.float_dim != 0) {  // float descriptors (L2^2): rows of float_dim floats
-            if (j.float_dim < 4 || j.float_dim > 1024 || (j.float_dim & 3)) return AFV_EINVAL;
-        } else if (j.desc_bytes < 1 || j.desc_bytes > 64) {
-            return AFV_EINVAL;
-        }
-        if (j.grid_cols < 1 || j.grid_rows < 1 || (long)j.grid_cols * j.grid_rows > 8192) return AFV_EINVAL;
-        if (!dev && j.n > 0 && (!j.desc || !j.x || !j.y || !j.size)) return AFV_EINVAL;
-        if (j.nq > 0 && !pq && ((!j.qdesc && !(dev && (dev->qdesc_dev || dev->qref_table))) || !j.qu || !j.qv || !j.qr || !j.qmin_size || !j.qmax_size)) return AFV_EINVAL;
-        if (pq && !pq->ids && j.nq > 0) return AFV_EINVAL;
-        const bool has_angle = dev ? dev->angle != nullptr : j.angle != nullptr;
-        const bool has_qangle = j.qangle != nullptr || (dev && dev->qangle_dev);
-        if (kind == AFV_KIND_INIT && j.check_orientation && ((j.n > 0 && !has_angle) || (j.nq > 0 && !has_qangle))) return AFV_EINVAL;
-        if (kind == AFV_KIND_PROJ && j.mode != AFV_PROJ_LOCALMAP && j.mode != AFV_PROJ_LASTFRAME) return AFV_EINVAL;
-        if (kind == AFV_KIND_PROJ && j.mode == AFV_PROJ_LASTFRAME && j.check_orientation && ((j.n > 0 && !has_angle) || (j.nq > 0 && !has_qangle)))
-            return AFV_EINVAL;
-        // stereo frames: the queries' right-image coordinate (and, for the projection searches, their gate) come with mvuRight
-        if (j.u_right && (kind == AFV_KIND_PROJ || kind == AFV_KIND_FUSE) && j.nq > 0 && (!j.q_ur || (kind == AFV_KIND_PROJ && !j.q_er_max)))
-            return AFV_EINVAL;
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    Blob b(c);
-    struct Off { size_t fd, x, y, size, angle, occ, inf, cptr, cent, qd, qrs, qri, qvalid, qu, qv, qr, qmin, qmax, qang, qocc, keys, ncand, ori, ur, qur, qer, pids, pcount; int words; bool stereo; };
-    std::vector<Off> offs(njobs);
-    size_t total_out = 0;
-    int max_nq = 0, max_n = 0;
-    size_t grid_lds = 0;
-    bool any_float = false;
-    for (int i = 0; i < njobs; ++i) {
-        const afv_proj_job &j = jobs[i];
-        Off &o = offs[i];
-        o = Off{};
-        o.words = j.float_dim ? j.float_dim : (j.desc_bytes <= 32 ? 8 : 16);  // dwords of one row
-        any_float = any_float || j.float_dim != 0;
-        if (dev && dev->words != o.words) return AFV_EINVAL;
-        // mvuRight branches: FeatureMatcher.cc:114-119, :1367-1372, :880-894.  A resident frame always carries the plane (-1 = monocular);
-        // it takes part when the caller sends the queries' side of the gate
-        const bool ur_here = dev ? (dev->u_right != nullptr && (j.q_ur != nullptr || (pq && pq->stereo))) : j.u_right != nullptr;
-        o.stereo = ur_here && (kind == AFV_KIND_PROJ || kind == AFV_KIND_FUSE);
-        if (o.stereo && kind == AFV_KIND_PROJ && j.nq > 0 && !j.q_er_max && !pq) return AFV_EINVAL;
-        if (!dev) {
-            o.fd = j.float_dim ? b.put(j.desc, (size_t)j.n * j.float_dim * 4) : put_desc(b, j.desc, j.n, j.desc_bytes, o.words);
-            o.x = b.put(j.x, (size_t)j.n * 4); o.y = b.put(j.y, (size_t)j.n * 4); o.size = b.put(j.size, (size_t)j.n * 4);
-            o.angle = j.angle ? b.put(j.angle, (size_t)j.n * 4) : 0;
-            o.inf = (fuse && j.inf) ? b.put(j.inf, (size_t)j.n * 4) : 0;
-            o.ur = o.stereo ? b.put(j.u_right, (size_t)j.n * 4) : 0;
-            grid_lds = std::max(grid_lds, afv_frame_grid_lds(j.grid_cols, j.grid_rows, std::max(j.n, 1)));
-        }
-        o.occ = (j.occupied && kind != AFV_KIND_INIT) ? b.put(j.occupied, (size_t)j.n) : 0;
-        o.qur = (o.stereo && !pq) ? b.put(j.q_ur, (size_t)j.nq * 4) : 0;
-        o.qer = (o.stereo && kind == AFV_KIND_PROJ && !pq) ? b.put(j.q_er_max, (size_t)j.nq * 4) : 0;
-        if (pq) o.pids = b.put(pq->ids, (size_t)j.nq * 4);
-        const bool by_ref = dev && dev->qref_table && !dev->qdesc_dev;
-        if (by_ref) {
-            // MapPoint descriptors by reference (rows of a keyframe table): checked here, gathered on the device behind the upload
-            const afv_table *qt = dev->qref_table;
-            if (qt->c != c || !dev->qref_slot || !dev->qref_idx || j.float_dim != qt->float_dim || j.desc_bytes != qt->desc_bytes) return AFV_EINVAL;
-            for (int q = 0; q < j.nq; ++q) {
-                const int sl = dev->qref_slot[q];
-                if (sl < 0 || sl >= qt->nsets || dev->qref_idx[q] < 0 || dev->qref_idx[q] >= qt->h_n[sl]) return AFV_EINVAL;
-            }
-            o.qrs = b.put(dev->qref_slot, (size_t)j.nq * 4);
-            o.qri = b.put(dev->qref_idx, (size_t)j.nq * 4);
-        } else if (!(dev && dev->qdesc_dev) && !pq) {
-            o.qd = j.float_dim ? b.put(j.qdesc, (size_t)j.nq * j.float_dim * 4) : put_desc(b, j.qdesc, j.nq, j.desc_bytes, o.words);
-        }
-        o.qvalid = (j.qvalid && !(dev && dev->qvalid_dev)) ? b.put(j.qvalid, (size_t)j.nq) : 0;
-        if (!pq) {
-            o.qu = b.put(j.qu, (size_t)j.nq * 4); o.qv = b.put(j.qv, (size_t)j.nq * 4); o.qr = b.put(j.qr, (size_t)j.nq * 4);
-            o.qmin = b.put(j.qmin_size, (size_t)j.nq * 4); o.qmax = b.put(j.qmax_size, (size_t)j.nq * 4);
-        }
-        o.qang = (j.qangle && !(dev && dev->qangle_dev)) ? b.put(j.qangle, (size_t)j.nq * 4) : 0;
-        o.qocc = j.qoccupies ? b.put(j.qoccupies, (size_t)j.nq) : 0;
-        total_out += (size_t)(per_query ? j.nq : j.n);
-        max_nq = std::max(max_nq, j.nq);
-        max_n = std::max(max_n, j.n);
-    }
-    // records the kernels read: the search jobs and, for staged feature sides, the grid jobs (uploaded with the inputs)
-    const size_t jobs_off = b.reserve((size_t)njobs * sizeof(DevProjJob));
-    const size_t gjobs_off = dev ? 0 : b.reserve((size_t)njobs * sizeof(DevGridJob));
-    const size_t nm_off = b.reserve((size_t)njobs * 4);
-    const size_t in_bytes = b.h.size();
-    for (int i = 0; i < njobs; ++i) {  // device-only scratch
-        const afv_proj_job &j = jobs[i];
-        offs[i].keys = b.reserve_scratch((size_t)std::max(j.nq, 1) * 64);  // 64-byte record / 8 keys per query
-        offs[i].ncand = b.reserve_scratch((size_t)std::max(j.nq, 1) * 4);
-        offs[i].ori = b.reserve_scratch((size_t)std::max(j.nq, 1) * 8);
-        if (dev && dev->qref_table && !dev->qdesc_dev) offs[i].qd = b.reserve_scratch((size_t)std::max(j.nq, 1) * dev->qref_table->words * 4);
-        if (pq) {  // what k_points_project writes: the whole query side
-            Off &o = offs[i];
-            const size_t nq4 = (size_t)std::max(j.nq, 1) * 4;
-            o.qu = b.reserve_scratch(nq4); o.qv = b.reserve_scratch(nq4); o.qr = b.reserve_scratch(nq4);
-            o.qmin = b.reserve_scratch(nq4); o.qmax = b.reserve_scratch(nq4); o.qur = b.reserve_scratch(nq4); o.qer = b.reserve_scratch(nq4);
-            o.qvalid = b.reserve_scratch(nq4 / 4); o.qocc = b.reserve_scratch(nq4 / 4);
-            o.qd = b.reserve_scratch(nq4 * o.words);
-            o.pcount = b.reserve_scratch(16);
-        }
-        if (!dev) {
-            offs[i].cptr = b.reserve_scratch(((size_t)j.grid_cols * j.grid_rows + 1) * 4);
-            offs[i].cent = b.reserve_scratch((size_t)std::max(j.n, 1) * 16);
-        }
-    }
-    const size_t out_off = b.reserve_scratch(std::max<size_t>(total_out, 1) * 4);
-    int rc = ensure_match_buffer(c, b.h.size());
-    if (rc) return rc;
-    // ordered phase: the workgroup fixed point when the largest job's tables fit the LDS it may use
-    size_t wg_lds = 0;
-    // (float descriptors: the projection searches' fixed point carries float distances; SearchForInitialization's packs them in 16 bits and
-    // float jobs take its ordered walk)
-    if (!fuse && !(any_float && kind == AFV_KIND_INIT) && c->proj_engine != 0 && c->proj_wg_lds_max > 0 && (kind != AFV_KIND_INIT || max_nq <= 32767)) {
-        for (int i = 0; i < njobs; ++i) wg_lds = std::max(wg_lds, afv_project_wg_lds(kind == AFV_KIND_INIT, jobs[i].n, jobs[i].nq, any_float ? 1 : 0));
-        if (wg_lds > (size_t)c->proj_wg_lds_max) wg_lds = 0;
-    }
-    // results straight into the pinned arena (device-visible host memory) when the kernels write them once and never read them back
-    const bool zero_copy = c->stage_pinned && (fuse || wg_lds != 0);
-    // ... and, for ONE job against a resident frame, the inputs straight out of it: the job record is the kernel argument, the queries
-    // (a few KB per array, read once by the ranking kernel) come over the link without a copy-engine hop ahead of the launch
-    // (not with an occupancy mask: that one is gathered per candidate, which belongs in device memory)
-    // (nor with float rows: a query row is 4 * dim bytes and is read once per CANDIDATE - that belongs in device memory too)
-    const bool zero_copy_in = zero_copy && dev && njobs == 1 && !any_float && !(jobs[0].occupied && kind != AFV_KIND_INIT);
-    uint8_t *B = c->d_match, *H = b.h.data();
-    uint8_t *IN = zero_copy_in ? H : B;  // where the kernels find the staged inputs
-    uint8_t *QIN = pq ? B : IN;          // ... and the query arrays: k_points_project writes them into device memory
-    size_t acc = 0;
-    for (int i = 0; i < njobs; ++i) {
-        const afv_proj_job &j = jobs[i];
-        const Off &o = offs[i];
-        DevProjJob &d = reinterpret_cast<DevProjJob *>(H + jobs_off)[i];
-        d = DevProjJob{};
-        d.n = j.n; d.words = j.float_dim ? 0 : o.words; d.fdim = j.float_dim;
-        if (dev) {
-            d.fdesc = dev->fdesc; d.x = dev->x; d.y = dev->y; d.size = dev->size; d.angle = dev->angle;
-            d.inf = fuse ? dev->inf : nullptr;
-            d.u_right = o.stereo ? dev->u_right : nullptr;
-            d.cell_ptr = dev->cell_ptr; d.cell_ent = dev->cell_ent;
-        } else {
-            d.fdesc = reinterpret_cast<const uint32_t *>(B + o.fd);
-            d.x = reinterpret_cast<const float *>(B + o.x); d.y = reinterpret_cast<const float *>(B + o.y);
-            d.size = reinterpret_cast<const float *>(B + o.size);
-            d.angle = j.angle ? reinterpret_cast<const float *>(B + o.angle) : nullptr;
-            d.inf = (fuse && j.inf) ? reinterpret_cast<const float *>(B + o.inf) : nullptr;
-            d.u_right = o.stereo ? reinterpret_cast<const float *>(B + o.ur) : nullptr;
-            d.cell_ptr = reinterpret_cast<const int *>(B + o.cptr); d.cell_ent = reinterpret_cast<const int4 *>(B + o.cent);
-            DevGridJob &g = reinterpret_cast<DevGridJob *>(H + gjobs_off)[i];
-            g = DevGridJob{};
-            g.n = j.n; g.cap = std::max(j.n, 1);
-            g.x = const_cast<float *>(d.x); g.y = const_cast<float *>(d.y); g.size = const_cast<float *>(d.size);
-            g.min_x = j.min_x; g.min_y = j.min_y; g.inv_w = j.grid_inv_w; g.inv_h = j.grid_inv_h; g.cols = j.grid_cols; g.rows = j.grid_rows;
-            g.cell_ptr = reinterpret_cast<int *>(B + o.cptr); g.cell_ent = reinterpret_cast<int4 *>(B + o.cent);
-        }
-        d.occupied = (j.occupied && kind != AFV_KIND_INIT) ? IN + o.occ : nullptr;
-        d.min_x = j.min_x; d.min_y = j.min_y; d.inv_w = j.grid_inv_w; d.inv_h = j.grid_inv_h; d.cols = j.grid_cols; d.rows = j.grid_rows;
-        d.nq = j.nq;
-        d.qdesc = (dev && dev->qdesc_dev) ? dev->qdesc_dev
-                                          : reinterpret_cast<const uint32_t *>(((dev && dev->qref_table) ? B : QIN) + o.qd);
-        d.qvalid = (dev && dev->qvalid_dev) ? dev->qvalid_dev : ((j.qvalid || pq) ? QIN + o.qvalid : nullptr);
-        d.qu = reinterpret_cast<const float *>(QIN + o.qu); d.qv = reinterpret_cast<const float *>(QIN + o.qv);
-        d.qr = reinterpret_cast<const float *>(QIN + o.qr); d.qmin = reinterpret_cast<const float *>(QIN + o.qmin);
-        d.qmax = reinterpret_cast<const float *>(QIN + o.qmax);
-        d.qangle = (dev && dev->qangle_dev) ? dev->qangle_dev : (j.qangle ? reinterpret_cast<const float *>(IN + o.qang) : nullptr);
-        d.qocc = (j.qoccupies || pq) ? QIN + o.qocc : nullptr;
-        d.th = j.th_high; d.ratio = j.nnratio; d.tol = j.size_tol; d.inv_tol = j.inv_size_tol;
-        d.check_ori = j.check_orientation != 0; d.mode = j.mode;
-        d.pass_cap = afv_debug_pass_cap;
-        d.keys = reinterpret_cast<unsigned long long *>(B + o.keys); d.ncand = reinterpret_cast<int *>(B + o.ncand);
-        d.orilist = reinterpret_cast<int *>(B + o.ori);
-        d.q_ur = o.stereo ? reinterpret_cast<const float *>(QIN + o.qur) : nullptr;
-        d.q_er = (o.stereo && kind == AFV_KIND_PROJ) ? reinterpret_cast<const float *>(QIN + o.qer) : nullptr;
-        d.stereo_gate = (o.stereo && kind == AFV_KIND_PROJ) ? 1 : 0;
-        uint8_t *R = zero_copy ? H : B;
-        d.assign = reinterpret_cast<int *>(R + out_off + acc * 4); d.nmatches = reinterpret_cast<int *>(R + nm_off + (size_t)i * 4);
-        acc += (size_t)(per_query ? j.nq : j.n);
-    }
-    if (!zero_copy_in) HIPCHK(c, hipMemcpyAsync(B, H, in_bytes, hipMemcpyHostToDevice, c->stream));
-    if (!dev) {
-        if (grid_lds > (size_t)c->frame_lds_max) {
-            c->last_error = "projection search: the grid of the feature side does not fit the LDS of one workgroup (cells x features too large)";
-            return AFV_EUNSUPPORTED;
-        }
-        afv_launch_frame_grid(reinterpret_cast<const DevGridJob *>(B + gjobs_off), njobs, grid_lds, c->stream);
-    }
-    if (dev && dev->qref_table && !dev->qdesc_dev) {
-        const afv_table *qt = dev->qref_table;
-        afv_launch_frame_gather(qt->d_desc, qt->d_n, qt->nsets, qt->cap, reinterpret_cast<const int *>(IN + offs[0].qrs),
-                                reinterpret_cast<const int *>(IN + offs[0].qri), jobs[0].nq, B + offs[0].qd, nullptr, qt->words, c->stream);
-    }
-    if (pq && jobs[0].nq > 0) {  // geometry and descriptor gather: the one launch a search through ids adds
-        const Off &o = offs[0];
-        DevPointsJob &pj = pq->job;
-        pj.ids = reinterpret_cast<const int *>(IN + o.pids);
-        pj.nq = jobs[0].nq;
-        pj.qu = reinterpret_cast<float *>(B + o.qu); pj.qv = reinterpret_cast<float *>(B + o.qv); pj.qr = reinterpret_cast<float *>(B + o.qr);
-        pj.qmin = reinterpret_cast<float *>(B + o.qmin); pj.qmax = reinterpret_cast<float *>(B + o.qmax);
-        pj.q_ur = reinterpret_cast<float *>(B + o.qur); pj.q_er = reinterpret_cast<float *>(B + o.qer);
-        pj.qvalid = B + o.qvalid; pj.qocc = B + o.qocc;
-        pj.qd = reinterpret_cast<uint4 *>(B + o.qd);
-        pj.count = c->d_points_count;
-        pj.ticket = c->d_points_count + 1;
-        pj.count_out = reinterpret_cast<int *>(B + o.pcount);
-        pj.o_size = pj.o_sigma = pj.o_cos = nullptr;
-        afv_launch_points_project(&pj, c->stream);
-        HIPCHK(c, hipGetLastError());
-    }
-    const DevProjJob *dj = reinterpret_cast<const DevProjJob *>(B + jobs_off);
-    const DevProjJob *one = zero_copy_in ? reinterpret_cast<const DevProjJob *>(H + jobs_off) : nullptr;
-    // one launch for ranking + ordered phase: the projection searches (a few candidates per query).  SearchForInitialization keeps two: its
-    // ranking walks 100-pixel windows (hundreds of cells per query) and is better off on 250 four-wave workgroups than on 63 sixteen-wave
-    // ones (measured: 59.6 us against 72.5 host to host)
-    int *ticket = (one && wg_lds && c->proj_fuse && kind == AFV_KIND_PROJ && !any_float) ? c->d_proj_ticket : nullptr;  // (the one-launch kernel is binary-only)
-    if (fuse) afv_launch_match_fuse(dj, njobs, max_nq, one, c->stream);
-    else if (kind == AFV_KIND_INIT) afv_launch_match_init(dj, njobs, max_nq, wg_lds, one, ticket, c->stream);
-    else afv_launch_match_projection(dj, njobs, max_nq, wg_lds, one, ticket, c->stream);
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            if (ticket) (void)hipMemsetAsync(ticket, 0, sizeof(int), c->stream);  // a launch that did not go out must not leave the ticket armed
-            c->last_error = std::string("projection search launch: ") + hipGetErrorString(e);
-            return AFV_EHIP;
-        }
-    }
-    if (!zero_copy) {
-        HIPCHK(c, b.fetch(assign, out_off, total_out * 4, c->stream));
-        if (!fuse) HIPCHK(c, b.fetch(nmatches, nm_off, (size_t)njobs * 4, c->stream));
-    }
-    if (pq) {
-        pq->n_in_view = 0;
-        if (jobs[0].nq > 0) {
-            if (pq->in_view) HIPCHK(c, b.fetch(pq->in_view, offs[0].qvalid, (size_t)jobs[0].nq, c->stream));
-            HIPCHK(c, b.fetch(&pq->n_in_view, offs[0].pcount, 4, c->stream));
-        }
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (zero_copy) {
-        std::memcpy(assign, H + out_off, total_out * 4);
-        if (!fuse) std::memcpy(nmatches, H + nm_off, (size_t)njobs * 4);
-    }
-    b.finish();
-    if (fuse) {  // independent queries: the count is just the number of hits
-        size_t at = 0;
-        for (int i = 0; i < njobs; ++i) {
-            int found = 0;
-            for (int q = 0; q < jobs[i].nq; ++q) found += assign[at + q] >= 0;
-            nmatches[i] = found;
-            at += (size_t)jobs[i].nq;
-        }
-    } else {
-        for (int i = 0; i < njobs; ++i)
-            if (nmatches[i] == -0x7fffffff) {  // AFV_FP_GUARD (afv_wave.h): the fixed point did not settle within its pass guard (never observed)
-                c->last_error = "projection search: the fixed point hit its pass guard; afv_set_projection_resolve(ctx, 0) selects the ordered walk";
-                return AFV_EHIP;
-            }
-    }
-    return AFV_OK;
-}
-
-// job arrays arrive with the layout the caller was compiled against (struct_size): bring them to the current one
-static int proj_jobs_entry(afv_ctx *c, const afv_proj_job *jobs, int njobs, int32_t *out, int32_t *nm, int kind) {
-    return guarded(c, [&]() -> int {
-        std::vector<afv_proj_job> J;
-        if (!afv_load_jobs(jobs, njobs, offsetof(afv_proj_job, u_right), J)) return AFV_EINVAL;
-        return afv_match_projection_core(c, J.data(), njobs, out, nm, kind, nullptr);
-    });
-}
-extern "C" int afv_match_projection(afv_ctx *c, const afv_proj_job *jobs, int njobs, int32_t *assign, int32_t *nmatches) {
-    return proj_jobs_entry(c, jobs, njobs, assign, nmatches, AFV_KIND_PROJ);
-}
-extern "C" int afv_match_fuse(afv_ctx *c, const afv_proj_job *jobs, int njobs, int32_t *best, int32_t *nfound) {
-    return proj_jobs_entry(c, jobs, njobs, best, nfound, AFV_KIND_FUSE);
-}
-extern "C" int afv_match_initialization(afv_ctx *c, const afv_proj_job *jobs, int njobs, int32_t *match12, int32_t *nmatches) {
-    return proj_jobs_entry(c, jobs, njobs, match12, nmatches, AFV_KIND_INIT);
-}
-static int afv_match_sim3_impl(afv_ctx *c, const afv_proj_job *j12, const afv_proj_job *j21, int32_t *match12, int32_t *nfound) {
-    if (!c || !j12 || !j21 || !match12 || !nfound) return AFV_EINVAL;
-    std::vector<afv_proj_job> A, Bv;
-    if (!afv_load_jobs(j12, 1, offsetof(afv_proj_job, u_right), A) || !afv_load_jobs(j21, 1, offsetof(afv_proj_job, u_right), Bv)) return AFV_EINVAL;
-    if (A[0].nq != Bv[0].n || Bv[0].nq != A[0].n) return AFV_EINVAL;
-    afv_proj_job jobs[2] = {A[0], Bv[0]};
-    jobs[0].inf = nullptr;  // no reprojection gate in SearchBySim3
-    jobs[1].inf = nullptr;
-    jobs[0].u_right = jobs[1].u_right = nullptr;  // ... and no stereo branch (FeatureMatcher.cc:1066-1287)
-    std::vector<int32_t> best((size_t)jobs[0].nq + (size_t)jobs[1].nq + 1);
-    int32_t nf[2];
-    const int rc = afv_match_projection_core(c, jobs, 2, best.data(), nf, AFV_KIND_FUSE, nullptr);
-    if (rc) return rc;
-    const int32_t *m1 = best.data(), *m2 = best.data() + jobs[0].nq;
-    int found = 0;
-    for (int i1 = 0; i1 < jobs[0].nq; ++i1) {  // FeatureMatcher.cc:1268-1284
-        const int idx2 = m1[i1];
-        const bool agree = idx2 >= 0 && m2[idx2] == i1;
-        match12[i1] = agree ? idx2 : -1;
-        found += agree;
-    }
-    *nfound = found;
-    return AFV_OK;
-}
-extern "C" int afv_match_sim3(afv_ctx *c, const afv_proj_job *j12, const afv_proj_job *j21, int32_t *match12, int32_t *nfound) {
-    return guarded(c, [&] { return afv_match_sim3_impl(c, j12, j21, match12, nfound); });
-}
-extern "C" int afv_set_projection_resolve(afv_ctx *c, int engine) {
-    if (!c || engine < 0 || engine > 3) return AFV_EINVAL;
-    c->proj_fuse = engine != 3;          // 3 = the fixed point as two launches (ranking, then ordered phase): the A / B of the one-launch form
-    c->proj_engine = engine == 3 ? 1 : engine;
-    return AFV_OK;
-}
-
 // ---- MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:279-349) for a batch of map points ----
 extern "C" int afv_distinctive_descriptors(afv_ctx *c, const uint8_t *desc, int desc_bytes, const int32_t *set_ptr, int nsets, int32_t *best_idx,
                                            int32_t *best_median) {
@@ -841,14 +522,13 @@ extern "C" int afv_distinctive_descriptors(afv_ctx *c, const uint8_t *desc, int 
         const size_t bi_off = b.reserve((size_t)nsets * 4), bm_off = b.reserve((size_t)nsets * 4);
         const int rc = ensure_match_buffer(c, b.h.size());
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, b.upload(in_bytes));
         afv_launch_distinctive(reinterpret_cast<const uint32_t *>(c->d_match + d_off), reinterpret_cast<const int *>(c->d_match + p_off), nsets, words,
                                desc_bytes, reinterpret_cast<int *>(c->d_match + bi_off), reinterpret_cast<int *>(c->d_match + bm_off), c->stream);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, b.fetch(best_idx, bi_off, (size_t)nsets * 4, c->stream));
         if (best_median) HIPCHK(c, b.fetch(best_median, bm_off, (size_t)nsets * 4, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        b.finish();
+        HIPCHK(c, b.wait());
         return AFV_OK;
     });
 }
@@ -871,14 +551,13 @@ extern "C" int afv_distinctive_descriptors_f32(afv_ctx *c, const float *desc, in
         const size_t bi_off = b.reserve((size_t)nsets * 4), bm_off = b.reserve((size_t)nsets * 4);
         const int rc = ensure_match_buffer(c, b.h.size());
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, b.upload(in_bytes));
         afv_launch_distinctive_f32(reinterpret_cast<const float *>(c->d_match + d_off), dim, reinterpret_cast<const int *>(c->d_match + p_off), nsets,
                                    reinterpret_cast<int *>(c->d_match + bi_off), reinterpret_cast<float *>(c->d_match + bm_off), c->stream);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, b.fetch(best_idx, bi_off, (size_t)nsets * 4, c->stream));
         if (best_median) HIPCHK(c, b.fetch(best_median, bm_off, (size_t)nsets * 4, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        b.finish();
+        HIPCHK(c, b.wait());
         return AFV_OK;
     });
 }
@@ -1055,7 +734,7 @@ extern "C" int afv_bow_vector(afv_ctx *c, const afv_vocab *v, const int32_t *lea
         const size_t n_off = b.reserve_scratch(16), word_off = b.reserve_scratch((size_t)n * 4), val_off = b.reserve_scratch((size_t)n * 8);
         const int rc = ensure_match_buffer(c, b.h.size());
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, b.upload(in_bytes));
         afv_launch_bowvec_build(reinterpret_cast<const int *>(c->d_match + leaf_off), n, v->d_weight, v->d_word_id, v->d_word_weight,
                                 reinterpret_cast<int32_t *>(c->d_match + word_off), reinterpret_cast<double *>(c->d_match + val_off),
                                 reinterpret_cast<int *>(c->d_match + n_off), c->stream);
@@ -1064,8 +743,7 @@ extern "C" int afv_bow_vector(afv_ctx *c, const afv_vocab *v, const int32_t *lea
         HIPCHK(c, b.fetch(n_out, n_off, 4, c->stream));
         HIPCHK(c, b.fetch(word, word_off, (size_t)n * 4, c->stream));
         HIPCHK(c, b.fetch(value, val_off, (size_t)n * 8, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        b.finish();
+        HIPCHK(c, b.wait());
         return AFV_OK;
     });
 }
@@ -1096,14 +774,13 @@ static int afv_bow_transform_impl(afv_ctx *c, const afv_vocab *v, const uint8_t 
     const size_t leaf_off = b.reserve((size_t)n * 4), nid_off = b.reserve((size_t)n * 4);
     const int rc = ensure_match_buffer(c, b.h.size());
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, b.upload(in_bytes));
     afv_launch_bow_transform(&v->dev, reinterpret_cast<const uint32_t *>(c->d_match + d_off), n, levelsup,
                              reinterpret_cast<int *>(c->d_match + leaf_off), reinterpret_cast<int *>(c->d_match + nid_off), nullptr, c->stream);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, b.fetch(leaf_node, leaf_off, (size_t)n * 4, c->stream));
     HIPCHK(c, b.fetch(node_at_level, nid_off, (size_t)n * 4, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    b.finish();
+    HIPCHK(c, b.wait());
     return AFV_OK;
 }
 extern "C" int afv_bow_transform(afv_ctx *c, const afv_vocab *v, const uint8_t *desc, int n, int levelsup, int32_t *leaf_node,
@@ -1123,15 +800,14 @@ extern "C" int afv_bow_transform_f32(afv_ctx *c, const afv_vocab *v, const float
         const size_t leaf_off = b.reserve((size_t)n * 4), nid_off = b.reserve((size_t)n * 4);
         const int rc = ensure_match_buffer(c, b.h.size());
         if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->d_match, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, b.upload(in_bytes));
         if (!afv_launch_bow_transform_f32(&v->dev, reinterpret_cast<const float *>(c->d_match + d_off), n, v->float_dim, levelsup,
                                           reinterpret_cast<int *>(c->d_match + leaf_off), reinterpret_cast<int *>(c->d_match + nid_off), nullptr, c->stream))
             return AFV_EUNSUPPORTED;
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, b.fetch(leaf_node, leaf_off, (size_t)n * 4, c->stream));
         HIPCHK(c, b.fetch(node_at_level, nid_off, (size_t)n * 4, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        b.finish();
+        HIPCHK(c, b.wait());
         return AFV_OK;
     });
 }

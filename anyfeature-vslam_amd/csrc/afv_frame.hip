@@ -414,34 +414,21 @@ extern "C" int afv_frame_get_bowvec(afv_frame *f, int32_t *word, double *value, 
 }
 
 // ---- the projection searches against a resident frame ----
-static void frame_side(const afv_frame *f, ProjFeatureSide &S) {
-    S.fdesc = reinterpret_cast<const uint32_t *>(f->d_desc);
-    S.n = f->n;
-    S.words = f->words;
-    S.x = f->d_x; S.y = f->d_y; S.size = f->d_size; S.angle = f->d_angle; S.inf = f->d_inf; S.u_right = f->d_ur;
-    S.cell_ptr = f->d_cell_ptr;
-    S.cell_ent = f->d_cell_ent;
-}
-
-static int frame_proj_job(const afv_frame *f, const afv_proj_queries &q, afv_proj_job &j) {
-    j = afv_proj_job{};
-    j.struct_size = sizeof(afv_proj_job);
-    j.n = f->n;
-    j.desc_bytes = f->desc_bytes;
-    j.float_dim = f->float_dim;
-    j.min_x = f->p.min_x; j.min_y = f->p.min_y; j.grid_inv_w = f->inv_w; j.grid_inv_h = f->inv_h;
-    j.grid_cols = f->p.grid_cols; j.grid_rows = f->p.grid_rows;
-    j.occupied = q.occupied;
-    j.nq = q.nq;
-    j.qdesc = q.qdesc; j.qvalid = q.qvalid;
-    j.qu = q.qu; j.qv = q.qv; j.qr = q.qr; j.qmin_size = q.qmin_size; j.qmax_size = q.qmax_size;
-    j.qangle = q.qangle; j.qoccupies = q.qoccupies;
-    j.th_high = q.th_high; j.nnratio = q.nnratio;
-    j.size_tol = f->c->p.scale_factor;              // Frame.cc:73: sizeTolerance = extractor->GetScaleFactor()
-    j.inv_size_tol = 1.0f / j.size_tol;             // Frame.cc:74
-    j.check_orientation = q.check_orientation; j.mode = q.mode;
-    j.q_ur = q.q_ur; j.q_er_max = q.q_er_max;
-    return AFV_OK;
+// the frame as the feature side of a search - everything is on the device, the grid was built when the features arrived - and its size tolerance
+ProjJobSpec afv_frame_proj_spec(const afv_frame *f, bool with_inf) {
+    ProjJobSpec J;
+    ProjSide &S = J.f;
+    S.on_device = true;
+    S.n = f->n; S.desc_bytes = f->desc_bytes; S.words = f->words; S.fdim = f->float_dim;
+    S.desc = f->d_desc;
+    S.x = f->d_x; S.y = f->d_y; S.size = f->d_size; S.angle = f->d_angle; S.u_right = f->d_ur;
+    S.inf = with_inf ? f->d_inf : nullptr;
+    S.cell_ptr = f->d_cell_ptr; S.cell_ent = f->d_cell_ent;
+    S.min_x = f->p.min_x; S.min_y = f->p.min_y; S.inv_w = f->inv_w; S.inv_h = f->inv_h;
+    S.grid_cols = f->p.grid_cols; S.grid_rows = f->p.grid_rows;
+    J.tol = f->c->p.scale_factor;  // Frame.cc:73: sizeTolerance = extractor->GetScaleFactor()
+    J.inv_tol = 1.0f / J.tol;      // Frame.cc:74
+    return J;
 }
 
 static int frame_match(afv_frame *f, const afv_proj_queries *caller_q, int kind, int use_inf_gate, int32_t *out, int32_t *nm) {
@@ -456,18 +443,17 @@ static int frame_match(afv_frame *f, const afv_proj_queries *caller_q, int kind,
         if (q.nq < 0 || q.nq > 65535) return AFV_EINVAL;
         if (q.nq > 0 && q.desc_bytes != f->desc_bytes && !q.qref_table) return AFV_EINVAL;
         if (q.qref_table && (f->float_dim != q.qref_table->float_dim || f->desc_bytes != q.qref_table->desc_bytes)) return AFV_EUNSUPPORTED;  // rows of another width / kind
-        ProjFeatureSide S;
-        frame_side(f, S);
-        if (kind == AFV_KIND_FUSE && !use_inf_gate) S.inf = nullptr;
         HIPCHK(c, hipSetDevice(c->device));
+        ProjJobSpec J = afv_frame_proj_spec(f, kind == AFV_KIND_FUSE && use_inf_gate);
+        afv_proj_host_fields(q, J);
         if (q.qref_table && q.nq > 0 && !q.qdesc) {  // MapPoint descriptors as rows of a keyframe table: gathered on the device
-            S.qref_table = q.qref_table;
-            S.qref_slot = q.qref_slot;
-            S.qref_idx = q.qref_idx;
+            J.q.from = ProjQueries::TABLE_ROWS;
+            J.q.ref_table = q.qref_table;
+            J.q.ref_slot = q.qref_slot;
+            J.q.ref_idx = q.qref_idx;
         }
-        afv_proj_job j;
-        frame_proj_job(f, q, j);
-        return afv_match_projection_core(c, &j, 1, out, nm, kind, &S);
+        J.stereo = q.q_ur != nullptr;  // the caller sends the queries' side of the gate
+        return afv_project_run(c, &J, 1, kind, out, nm);
     });
 }
 
@@ -494,27 +480,16 @@ extern "C" int afv_frame_match_initialization(afv_frame *f1, afv_frame *f2, cons
         // from it for non-default scale factors / level counts)
         const float max_size = powf(1.2f, float(8 - 1.0));
         std::vector<float> r((size_t)std::max(n1, 1), window_size), mn((size_t)std::max(n1, 1), 0.0f), mx((size_t)std::max(n1, 1), max_size);
-        ProjFeatureSide S;
-        S.fdesc = reinterpret_cast<const uint32_t *>(f2->d_desc);
-        S.n = f2->n;
-        S.words = f2->words;
-        S.x = f2->d_x; S.y = f2->d_y; S.size = f2->d_size; S.angle = f2->d_angle;
-        S.cell_ptr = f2->d_cell_ptr; S.cell_ent = f2->d_cell_ent;
-        S.qdesc_dev = reinterpret_cast<const uint32_t *>(f1->d_desc);
-        S.qangle_dev = f1->d_angle;
-        S.qvalid_dev = f1->d_oct0;  // level1 > 0 -> skipped (:487-489); the mask was written when F1 was extracted
-        afv_proj_job j{};
-        j.struct_size = sizeof(afv_proj_job);
-        j.n = f2->n;
-        j.desc_bytes = f2->desc_bytes;
-        j.float_dim = f2->float_dim;
-        j.min_x = f2->p.min_x; j.min_y = f2->p.min_y; j.grid_inv_w = f2->inv_w; j.grid_inv_h = f2->inv_h;
-        j.grid_cols = f2->p.grid_cols; j.grid_rows = f2->p.grid_rows;
-        j.nq = n1;
-        j.qu = prev_x; j.qv = prev_y; j.qr = r.data(); j.qmin_size = mn.data(); j.qmax_size = mx.data();
-        j.th_high = th_low; j.nnratio = nnratio;
-        j.size_tol = c->p.scale_factor; j.inv_size_tol = 1.0f / j.size_tol;
-        j.check_orientation = check_orientation;
-        return afv_match_projection_core(c, &j, 1, match12, nmatches, AFV_KIND_INIT, &S);
+        ProjJobSpec J = afv_frame_proj_spec(f2, false);
+        ProjQueries &Q = J.q;
+        Q.nq = n1;
+        Q.from = ProjQueries::DEVICE_ROWS;
+        Q.desc = f1->d_desc;
+        Q.angle = f1->d_angle; Q.angle_on_device = true;
+        Q.valid = f1->d_oct0; Q.valid_on_device = true;  // level1 > 0 -> skipped (:487-489); the mask was written when F1 was extracted
+        Q.u = prev_x; Q.v = prev_y; Q.r = r.data(); Q.min_size = mn.data(); Q.max_size = mx.data();
+        J.th = th_low; J.ratio = nnratio;
+        J.check_ori = check_orientation;
+        return afv_project_run(c, &J, 1, AFV_KIND_INIT, match12, nmatches);
     });
 }

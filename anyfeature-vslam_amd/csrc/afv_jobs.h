@@ -1,8 +1,13 @@
 // afv_jobs.h - the job records the host stages for the matcher / vocabulary kernels: ONE definition for the kernels (k_match.hip,
-// k_project.hip, k_bow.hip) and the runtime (afv_api.hip, afv_comm.hip) that fills them.  (Until round 4 every record was written down
-// twice, kernel side and host side, and kept equal by hand.)
+// k_project.hip, k_bow.hip) and the host files that fill them (afv_match_jobs.hip, afv_project.hip, afv_frame.hip, afv_api.hip, afv_comm.hip).
+// (Until round 4 every record was written down twice, kernel side and host side, and kept equal by hand.)
 #pragma once
 #include <stdint.h>
+
+// The match count a fixed-point engine reports when its pass guard trips (never observed): the host turns it into AFV_EHIP
+// (afv_check_resolve_guard in afv_api.hip, the collection of afv_project_run in afv_project.hip).  The kernels write it as AFV_FP_GUARD
+// (afv_wave.h), the same value.
+#define AFV_PASS_GUARD (-0x7fffffff)
 
 struct Seg {
     int s1, n1, s2, n2;  // ranges into idx1/idx2 (or identity when the idx pointer is null)

@@ -400,34 +400,25 @@ static int search_points(afv_frame *f, const afv_point_search *caller, int kind,
         PointQueries pq;
         fill_points_job(f, s, pq.job);
         pq.ids = s.ids;
-        pq.stereo = s.flavour != AFV_PT_RELOC;
         pq.in_view = in_view;
-        ProjFeatureSide S;
-        S.fdesc = reinterpret_cast<const uint32_t *>(f->d_desc);
-        S.n = f->n;
-        S.words = f->words;
-        S.x = f->d_x; S.y = f->d_y; S.size = f->d_size; S.angle = f->d_angle; S.u_right = f->d_ur;
-        S.inf = (kind == AFV_KIND_FUSE && use_inf_gate) ? f->d_inf : nullptr;
-        S.cell_ptr = f->d_cell_ptr;
-        S.cell_ent = f->d_cell_ent;
-        S.pq = &pq;
-        if (s.qframe && (s.flavour == AFV_PT_LASTFRAME || (s.flavour == AFV_PT_RELOC && !s.qangle))) S.qangle_dev = s.qframe->d_angle;
-        afv_proj_job j{};
-        j.struct_size = sizeof(afv_proj_job);
-        j.n = f->n;
-        j.desc_bytes = f->desc_bytes;
-        j.float_dim = f->float_dim;
-        j.min_x = f->p.min_x; j.min_y = f->p.min_y; j.grid_inv_w = f->inv_w; j.grid_inv_h = f->inv_h;
-        j.grid_cols = f->p.grid_cols; j.grid_rows = f->p.grid_rows;
-        j.occupied = kind == AFV_KIND_FUSE ? nullptr : s.occupied;
-        j.nq = s.nq;
-        j.qangle = (s.flavour == AFV_PT_RELOC) ? s.qangle : nullptr;
-        j.th_high = s.th_high; j.nnratio = s.nnratio;
-        j.size_tol = c->p.scale_factor;
-        j.inv_size_tol = 1.0f / j.size_tol;
-        j.check_orientation = (s.flavour == AFV_PT_FRUSTUM || kind == AFV_KIND_FUSE) ? 0 : s.check_orientation;
-        j.mode = s.flavour == AFV_PT_FRUSTUM ? AFV_PROJ_LOCALMAP : AFV_PROJ_LASTFRAME;
-        const int rc = afv_match_projection_core(c, &j, 1, out, nm, kind, &S);
+        ProjJobSpec J = afv_frame_proj_spec(f, kind == AFV_KIND_FUSE && use_inf_gate);
+        J.f.occupied = kind == AFV_KIND_FUSE ? nullptr : s.occupied;
+        ProjQueries &Q = J.q;
+        Q.nq = s.nq;
+        Q.from = ProjQueries::POINT_IDS;
+        Q.points = &pq;
+        // the angles alone are not made from the ids: the last frame's / the keyframe's, from a resident frame in that role or (RELOC) a host array
+        if (s.qframe && (s.flavour == AFV_PT_LASTFRAME || (s.flavour == AFV_PT_RELOC && !s.qangle))) {
+            Q.angle = s.qframe->d_angle;
+            Q.angle_on_device = true;
+        } else if (s.flavour == AFV_PT_RELOC) {
+            Q.angle = s.qangle;
+        }
+        J.th = s.th_high; J.ratio = s.nnratio;
+        J.check_ori = (s.flavour == AFV_PT_FRUSTUM || kind == AFV_KIND_FUSE) ? 0 : s.check_orientation;
+        J.mode = s.flavour == AFV_PT_FRUSTUM ? AFV_PROJ_LOCALMAP : AFV_PROJ_LASTFRAME;
+        J.stereo = s.flavour != AFV_PT_RELOC;  // every flavour but RELOC has a stereo gate
+        const int rc = afv_project_run(c, &J, 1, kind, out, nm);
         if (rc) return points_call_failed(c, rc);
         if (n_in_view) *n_in_view = pq.n_in_view;
         return AFV_OK;
@@ -463,7 +454,7 @@ extern "C" int afv_frame_project_points(afv_frame *f, const afv_point_search *ca
         const int rc = ensure_match_buffer(c, b.h.size());
         if (rc) return rc;
         uint8_t *B = c->d_match;
-        HIPCHK(c, hipMemcpyAsync(B, b.h.data(), in_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, b.upload(in_bytes));
         DevPointsJob J;
         fill_points_job(f, s, J);
         J.ids = reinterpret_cast<const int *>(B + o_ids);
@@ -484,8 +475,7 @@ extern "C" int afv_frame_project_points(afv_frame *f, const afv_point_search *ca
                 if (outs[k]) HIPCHK(c, b.fetch(outs[k], o_f[k], nq4, c->stream));
             if (host_out->in_view) HIPCHK(c, b.fetch(host_out->in_view, o_valid, (size_t)s.nq, c->stream));
             HIPCHK(c, b.fetch(&host_out->n_in_view, o_count, 4, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            b.finish();
+            HIPCHK(c, b.wait());
             return AFV_OK;
         }());
     });

@@ -1,5 +1,6 @@
-// afv_runtime.h — host-side internals shared by the translation units behind the C-ABI (afv_api.hip, afv_extract.hip, afv_comm.hip, afv_match_jobs.hip):
-// the context, the pinned staging arena (Blob) and the kernel launcher prototypes.  Not part of the public interface.
+// afv_runtime.h — host-side internals shared by the translation units behind the C-ABI (afv_api.hip, afv_extract.hip, afv_comm.hip,
+// afv_match_jobs.hip, afv_project.hip, afv_frame.hip, afv_points.hip, afv_stereo.hip): the context, the pinned staging arena (Blob), the
+// kernel launcher prototypes and the job descriptions of the matcher pipelines.  Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,9 @@
 
 #include "afv_device.h"
 #include "afv_jobs.h"
+
+// internal functions that cross translation units without entering the library's dynamic symbol table
+#define AFV_LOCAL __attribute__((visibility("hidden")))
 
 // ---- kernel launchers (k_*.hip) ----
 extern "C" void afv_launch_resize(const uint8_t *src, int sw, int sh, int spitch, size_t sframe, uint8_t *dst, int dw, int dh,
@@ -497,6 +501,14 @@ struct Blob {
         for (const Pending &p : pending) std::memcpy(p.dst, h.data() + p.off, p.bytes);
         pending.clear();
     }
+    // the call's one host -> device copy: the first in_bytes of the image (the inputs and the records) on the context's stream
+    AFV_LOCAL hipError_t upload(size_t in_bytes) { return hipMemcpyAsync(h.c->d_match, h.data(), in_bytes, hipMemcpyHostToDevice, h.c->stream); }
+    // the end of a call: the host waits for the stream, then the fetched ranges go to the caller's arrays
+    AFV_LOCAL hipError_t wait() {
+        const hipError_t e = hipStreamSynchronize(h.c->stream);
+        if (e == hipSuccess) finish();
+        return e;
+    }
 };
 
 // scratch of a column-sliced phase 1 over `npairs` pairs (grow-only; growing implies a device sync, tickets are zeroed once)
@@ -579,7 +591,7 @@ struct afv_table {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
-// ---- shared between afv_api.hip and afv_comm.hip ----
+// ---- the pair matchers (afv_api.hip), shared with afv_comm.hip ----
 int afv_match_pairs_core(afv_ctx *c, const uint8_t *d_desc, const float *d_ang, int ang_stride, const int32_t *d_n, int cap,
                          const int32_t *d_pair_a, const int32_t *d_pair_b, int npairs, float th_low, float nnratio,
                          int check_orientation, int32_t *d_match, int32_t *d_nmatches, hipStream_t s, int words);
@@ -641,36 +653,73 @@ int afv_extract_into_frame(afv_ctx *c, afv_frame *f, const uint8_t *gray, int wi
 // what afv_create (afv_api.hip) needs from the extractor's geometry (afv_extract.hip): level sizes, quotas and buffer layout of `max_batch`
 // frames of w x h, and the bytes of the pyramid / the elements of a candidate array that layout takes.  Hidden: the library's
 // dynamic symbol table stays as it was when one file held both sides
-#define AFV_LOCAL __attribute__((visibility("hidden")))
 AFV_LOCAL int afv_build_geometry(const afv_orb_params &p, int w, int h, int max_batch, Geo &g);
 AFV_LOCAL size_t afv_geo_pyr_bytes(const Geo &g, int max_batch);
 AFV_LOCAL size_t afv_geo_cand_elems(const Geo &g, int max_batch);
 // the host side of E12 (FeatureExtractor.cpp:132-172): keyPtsSize of octave `o` as afv_orb_size_sigma computes it
 float afv_size_of_octave(const afv_ctx *c, int octave);
-// projection searches over a feature side that is already on the device (afv_frame.hip) share the staging / launch code of the host-pointer
-// entry points (afv_api.hip)
-struct ProjFeatureSide {      // device pointers of the feature side; null fdesc = stage it from the job's host arrays
-    const uint32_t *fdesc = nullptr;
-    int n = 0, words = 8;
+// ---- the projection searches (afv_project.hip): one staging and launch path behind the host-array entry points (afv_project.hip), the
+// searches against a resident frame (afv_frame.hip) and the searches through map-point ids (afv_points.hip).  A route describes each job
+// once - where every array lives - and afv_project_run stages, launches and collects ----
+enum { AFV_KIND_PROJ = 0, AFV_KIND_FUSE = 1, AFV_KIND_INIT = 2 };
+struct ProjSide {  // the feature side of a job: the frame searched in
+    int n = 0, desc_bytes = 32, words = 8, fdim = 0;  // features; row width, dwords per device row, floats per row (0: binary)
+    // desc .. u_right are device pointers and the grid (cell_ptr / cell_ent) comes with them (a resident frame); else they are host arrays
+    // to stage (desc: n packed rows of desc_bytes) and k_frame_grid builds the grid behind the upload
+    bool on_device = false;
+    const void *desc = nullptr;
     const float *x = nullptr, *y = nullptr, *size = nullptr, *angle = nullptr, *inf = nullptr, *u_right = nullptr;
     const int *cell_ptr = nullptr;
     const int4 *cell_ent = nullptr;
-    const uint32_t *qdesc_dev = nullptr;  // queries' descriptors already on the device (another frame's rows)
-    const afv_table *qref_table = nullptr;  // ... or rows (slot, idx) of a keyframe table, gathered on the device (host arrays of nq ints)
-    const int32_t *qref_slot = nullptr, *qref_idx = nullptr;
-    const float *qangle_dev = nullptr;
-    const uint8_t *qvalid_dev = nullptr;
-    // ... or the whole query side made on the device from the ids of resident map points (afv_points.hip): k_points_project runs ahead of
-    // the search kernels and writes qu .. q_er_max, qvalid, qoccupies and the gathered rows into the call's staging area
-    struct PointQueries *pq = nullptr;
+    float min_x = 0, min_y = 0, inv_w = 0, inv_h = 0;  // Frame::AssignFeaturesToGrid: mnMinX / mnMinY, mfGridElementWidthInv / HeightInv
+    int grid_cols = 0, grid_rows = 0;
+    const uint8_t *occupied = nullptr;  // [n] or null; host, always
 };
+// the whole query side made on the device from the ids of resident map points (afv_points.hip): k_points_project runs ahead of the search
+// kernels and writes qu .. q_er_max, qvalid, qoccupies and the gathered rows into the call's staging area
 struct PointQueries {
-    DevPointsJob job{};            // planes, pose, flavour, rules; the core fills in ids and the outputs
+    DevPointsJob job{};            // planes, pose, flavour, rules; afv_project_run fills in ids and the outputs
     const int32_t *ids = nullptr;  // host [nq]
-    bool stereo = false;           // the flavour has a stereo gate (every one but RELOC)
     uint8_t *in_view = nullptr;    // host [nq] out, may be null
     int32_t n_in_view = 0;         // out
 };
-enum { AFV_KIND_PROJ = 0, AFV_KIND_FUSE = 1, AFV_KIND_INIT = 2 };
-int afv_match_projection_core(afv_ctx *c, const afv_proj_job *jobs, int njobs, int32_t *assign, int32_t *nmatches, int kind,
-                              const ProjFeatureSide *dev_side);
+struct ProjQueries {  // the query side of a job: where each of its arrays comes from
+    int nq = 0;
+    enum Rows { HOST_ROWS, DEVICE_ROWS, TABLE_ROWS, POINT_IDS } from = HOST_ROWS;
+    const void *desc = nullptr;              // HOST_ROWS: nq packed rows to stage; DEVICE_ROWS: rows of the feature side's pitch (another frame's)
+    const afv_table *ref_table = nullptr;    // TABLE_ROWS: rows (slot, idx) of a keyframe table, gathered on the device behind the upload
+    const int32_t *ref_slot = nullptr, *ref_idx = nullptr;  // ... host arrays of nq ints
+    PointQueries *points = nullptr;          // POINT_IDS: rows, geometry, qvalid, qoccupies and the stereo pair are made on the device
+    const uint8_t *valid = nullptr;          // [nq] or null ...
+    const float *angle = nullptr;
+    bool valid_on_device = false, angle_on_device = false;  // ... each a host array to stage or a device pointer
+    const float *u = nullptr, *v = nullptr, *r = nullptr, *min_size = nullptr, *max_size = nullptr;  // host
+    const float *ur = nullptr, *er_max = nullptr;                                                   // host, stereo only
+    const uint8_t *occupies = nullptr;                                                              // host, [nq] or null
+};
+struct ProjJobSpec {
+    ProjSide f;
+    ProjQueries q;
+    float th = 0, ratio = 0, tol = 0, inv_tol = 0;
+    int check_ori = 0, mode = 0;
+    // mvuRight takes part (FeatureMatcher.cc:114-119, :1367-1372, :880-894) - decided by the route: host arrays that carry u_right; a
+    // resident frame (it always carries the plane, -1 = monocular) when the caller sends the queries' side of the gate.
+    // SearchForInitialization has no such branch whatever this says
+    bool stereo = false;
+};
+// what afv_proj_job and afv_proj_queries both carry - the queries as host arrays, the occupancy mask, the settings - into a spec
+template <class T>
+static inline void afv_proj_host_fields(const T &j, ProjJobSpec &J) {
+    J.f.occupied = j.occupied;
+    ProjQueries &q = J.q;
+    q.nq = j.nq; q.desc = j.qdesc; q.valid = j.qvalid; q.angle = j.qangle; q.occupies = j.qoccupies;
+    q.u = j.qu; q.v = j.qv; q.r = j.qr; q.min_size = j.qmin_size; q.max_size = j.qmax_size;
+    q.ur = j.q_ur; q.er_max = j.q_er_max;
+    J.th = j.th_high; J.ratio = j.nnratio; J.check_ori = j.check_orientation; J.mode = j.mode;
+}
+// kind: AFV_KIND_*; assign: n ints per job (PROJ) or nq (FUSE, INIT), packed in job order; nmatches[njobs].  A side or a query array on the
+// device: njobs == 1
+AFV_LOCAL int afv_project_run(afv_ctx *c, const ProjJobSpec *specs, int njobs, int kind, int32_t *assign, int32_t *nmatches);
+// afv_frame.hip: the spec fields a resident frame decides - the frame as feature side (with_inf: keyPtsInf for the chi-square gate of Fuse)
+// and the size tolerance (Frame.cc:73-74)
+AFV_LOCAL ProjJobSpec afv_frame_proj_spec(const afv_frame *f, bool with_inf);

@@ -470,3 +470,39 @@ def size_regimes():
     out["grid-8192-cells"] = synthetic(2000, 1500, 241, r=9.0, grid_cols=128, grid_rows=64)
     out["grid-1x1"] = synthetic(150, 300, 251, r=30.0, grid_cols=1, grid_rows=1)
     return out
+
+
+# ---- one scene for every route into the projection searches (tests/test_gpu_proj_scenes.py::test_one_scene_through_every_projection_route) ----
+INIT_MAX_SIZE = 3.5831808   # 1.2^7: the size band 0 .. F1.maxKeyPtSize a SearchForInitialization between resident frames applies
+
+
+def every_route_scene(desc="b32"):
+    """70 features on the default grid, clustered in a 50 x 40 box around one descriptor prototype so that neighbours are contested, and 65
+    queries (a wavefront and one lane) with holes in qvalid, angles, non-occupying queries and an occupancy mask on a few features.
+    desc "f64": the same scene with rows of 64 floats - twice the first 64 bits of the binary rows, so that every L2^2 is four times a
+    Hamming distance, exact in any summation order.  Returns a dict:
+      F, Q      the scene (F.occupied set; F.u_right None)
+      Fs, Qs    its stereo twin: mvuRight on two features in three, the queries' ur / er_max placed so that some candidates fail the gate
+      Qi        the queries as a SearchForInitialization between resident frames states them: one window, band 0 .. 1.2^7, no mask
+      F1, Q2    the reverse direction of a SearchBySim3 pair: the queries as 65 features, the features as 70 queries"""
+    F, Q = synthetic(70, 65, 977, r=14.0, cluster=(280.0, 200.0, 50.0, 40.0), protos=1)
+    Q.valid[:] = 1
+    Q.valid[[3, 17, 40, 63]] = 0          # (query 64, the one-lane tail, searches)
+    F.occupied[:] = 0
+    F.occupied[[5, 22, 41, 58]] = 1
+    if desc == "f64":
+        fl = lambda D: np.ascontiguousarray(np.unpackbits(D[:, :8], axis=1).astype(np.float32) * f32(2))
+        F.descriptors, Q.descriptors = fl(F.descriptors), fl(Q.descriptors)
+    else:
+        assert desc == "b32"
+    G = GRIDS["default"]
+    pts = np.stack([F.x, F.y], 1)
+    ur = np.where(np.arange(F.N) % 3 == 2, f32(-1), F.x - f32(20)).astype(np.float32)
+    Fs = afv.FrameGridView(F.descriptors, pts, F.sizes, angles=F.angles, occupied=F.occupied, u_right=ur, **G)
+    qur = (Q.u - f32(20) + (S.lcg_states(991, Q.n) % 13).astype(np.float32) - f32(6)).astype(np.float32)
+    Qs = afv.ProjectionQueries(Q.descriptors, Q.u, Q.v, Q.r, Q.min_size, Q.max_size, valid=Q.valid, angles=Q.angles, occupies=Q.occupies,
+                               ur=qur, er_max=np.full(Q.n, 4.0, np.float32))
+    Qi = afv.ProjectionQueries(Q.descriptors, Q.u, Q.v, Q.r, np.zeros(Q.n, np.float32), np.full(Q.n, INIT_MAX_SIZE, np.float32), angles=Q.angles)
+    F1 = afv.FrameGridView(Q.descriptors, np.stack([Q.u, Q.v], 1), (Q.min_size * f32(1.2)).astype(np.float32), angles=Q.angles, **G)
+    Q2 = afv.ProjectionQueries(F.descriptors, F.x, F.y, np.full(F.N, 14.0, np.float32), F.sizes / f32(1.3), F.sizes * f32(1.3), angles=F.angles)
+    return dict(F=F, Q=Q, Fs=Fs, Qs=Qs, Qi=Qi, F1=F1, Q2=Q2)

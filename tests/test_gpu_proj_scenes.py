@@ -308,3 +308,117 @@ def test_job_batches(afv, oracle, gpu_ctx, kind, entry, k):
         assert got[i][1] == wn and np.array_equal(got[i][0], want), ("job %d of %d differs from the oracle" % (i, k))
         single = _run_batch(afv, gpu_ctx, entry, [items[i]], kind)[0]
         assert single[1] == got[i][1] and np.array_equal(single[0], got[i][0]), ("job %d of %d differs from the single-job call" % (i, k))
+
+
+# ---- one scene through every route ----
+def _points_scene(flavour, desc):
+    """65 ids of a seeded map-point scene against its first 70 features, a few of them occupied before a FRUSTUM search; desc "f64": the
+    same geometry with rows of 64 floats"""
+    import _points_scenes as MS
+    import test_gpu_points as TP
+    base = TP.random_scene(1, flavour)
+    P, feat = TP._with_rows(base, 256, 64) if desc == "f64" else (base.P, base.feat)
+    feat = MS.Features(feat.x[:70], feat.y[:70], feat.sizes[:70], feat.desc[:70], angles=feat.angles[:70])
+    occ = None
+    if flavour == TP.R.FRUSTUM:
+        occ = np.zeros(70, np.uint8)
+        occ[[2, 9, 30]] = 1
+    return MS.Scene(base.name + "-65", None, flavour, P, base.cam, base.ids[:65], None, radius_th=base.radius_th, feat=feat, th=64.0,
+                    nnratio=base.nnratio, occupied=occ)
+
+
+@pytest.mark.parametrize("desc", ["b32", "f64"])
+def test_one_scene_through_every_projection_route(afv, oracle, gpu_ctx, desc):
+    """PS.every_route_scene through every entry point that can state it - host arrays alone and as the middle job of a batch of three, a
+    resident frame with the queries' rows by value and by reference into a keyframe table, with and without the occupancy mask and the
+    stereo gate, Fuse alone / as one direction of a SearchBySim3 pair / against the frame with and without the chi-square gate,
+    SearchForInitialization from host arrays and between two resident frames - and a map-point scene of the same size through ids: every
+    answer equals the oracle's AND the host-array answer, so a pointer taken from the wrong base on one route shows as a difference.
+    tests/test_proj_ref_cpu.py shows that the scene's answer hangs on its masks and its histogram."""
+    import copy
+    import test_gpu_points as TP
+    s = PS.every_route_scene(desc)
+    F, Q, Fs, Qs, Qi, F1, Q2 = (s[k] for k in ("F", "Q", "Fs", "Qs", "Qi", "F1", "Q2"))
+    assert F.N == 70 and Q.n == 65 and (F.grid_cols, F.grid_rows) == (64, 48)
+    fl = desc == "f64"
+    afv.FeatureMatcher.setDescriptorDistanceThresholds(75.0)
+    same = lambda got, want, what: (got[1] == want[1] and np.array_equal(got[0], want[0])) or pytest.fail(what)
+    fr = _resident(afv, gpu_ctx, Fs)   # carries mvuRight: the plane takes part only when the queries bring their side of the gate
+    assert fr is not None
+    f1 = afv.Frame(gpu_ctx, cap=Q.n, desc_bytes=32, float_dim=64 if fl else 0)
+    table = afv.table.DescriptorTable(gpu_ctx, 2, 40, float_dim=64) if fl else afv.table.DescriptorTable(gpu_ctx, 2, 40, desc_bytes=32)
+    rigs = []
+    try:
+        # SearchByProjection(CurrentFrame, LastFrame) with the orientation check
+        kw = dict(th_high=75.0, nnratio=0.9, check_orientation=True, last_frame=True)
+        m = afv.FeatureMatcher(0.9, True, ctx=gpu_ctx)
+        slots = (np.arange(Q.n) % 2).astype(np.int32)
+        idx = (np.arange(Q.n) // 2).astype(np.int32)
+        for sl in (0, 1):
+            table.set(sl, Q.descriptors[slots == sl])
+        Fa, Qa = PS.synthetic(33, 17, 978)
+        Fb, Qb = PS.synthetic(21, 40, 979)
+        for masked in (True, False):
+            Fm = F if masked else copy.copy(F)
+            if not masked:
+                Fm.occupied = None
+            want = oracle.match_projection(Fm, Q, **kw)
+            host = m.SearchByProjection(Fm, Q, last_frame=True)
+            same(host, want, ("host arrays", masked))
+            batch = _run_batch(afv, gpu_ctx, "afv_match_projection", [(Fa, Qa, kw), (Fm, Q, kw), (Fb, Qb, kw)], "proj")
+            same(batch[1], host, ("middle of a batch of three", masked))
+            same(batch[0], oracle.match_projection(Fa, Qa, **kw), "first of the batch")
+            same(batch[2], oracle.match_projection(Fb, Qb, **kw), "last of the batch")
+            same(fr.SearchByProjection(m, Q, last_frame=True, occupied=Fm.occupied), host, ("resident frame, rows by value", masked))
+            same(fr.SearchByProjection(m, Q, last_frame=True, occupied=Fm.occupied, qref=(table, slots, idx)), host,
+                 ("resident frame, rows by reference", masked))
+        want = oracle.match_projection(Fs, Qs, **kw)
+        assert not np.array_equal(want[0], oracle.match_projection(F, Q, **kw)[0])   # the gate decides something
+        host = m.SearchByProjection(Fs, Qs, last_frame=True)
+        same(host, want, "host arrays, stereo")
+        same(fr.SearchByProjection(m, Qs, last_frame=True, occupied=Fs.occupied), host, "resident frame, stereo")
+        # Fuse
+        m6 = afv.FeatureMatcher(0.6, False, ctx=gpu_ctx)
+        fkw = dict(th_high=75.0, fuse=True)
+        want = oracle.match_projection(F, Q, **fkw)
+        back = oracle.match_projection(F1, Q2, **fkw)
+        host = m6.Fuse(F, Q)
+        same(host, want, "Fuse, host arrays")
+        pair = _run_batch(afv, gpu_ctx, "afv_match_fuse", [(F, Q, fkw), (F1, Q2, fkw)], "fuse")
+        same(pair[0], host, "Fuse, first of two jobs")
+        same(pair[1], back, "Fuse, second of two jobs")
+        m12 = pair[0][0].copy()
+        hit = m12 >= 0
+        m12[hit] = np.where(pair[1][0][m12[hit]] == np.flatnonzero(hit), m12[hit], -1)
+        sim3 = m.SearchBySim3(F1, Q, F, Q2)
+        same(sim3, (m12, int((m12 >= 0).sum())), "SearchBySim3 = the two directions where they agree")
+        same(sim3, oracle.match_sim3(F, Q, F1, Q2, th_high=75.0), "SearchBySim3")
+        same(fr.Fuse(m6, Q, use_inf_gate=False), host, "Fuse, resident frame, no gate")
+        Fi = copy.copy(F)
+        Fi.inf = (np.float32(1.0) / (F.sizes * F.sizes)).astype(np.float32)   # keyPtsInf as a frame derives it from keyPtsSize
+        want = oracle.match_projection(Fi, Q, **fkw)
+        assert want[1] < host[1]                                              # the gate rejects something
+        gated = m6.Fuse(Fi, Q)
+        same(gated, want, "Fuse with the chi-square gate, host arrays")
+        same(fr.Fuse(m6, Q, use_inf_gate=True), gated, "Fuse with the chi-square gate, resident frame")
+        # SearchForInitialization
+        ikw = dict(th_low=75.0, nnratio=0.9, check_orientation=True)
+        same(m.SearchForInitialization(Q, F), oracle.match_initialization(F, Q, **ikw), "initialization, host arrays, masked queries")
+        want = oracle.match_initialization(F, Qi, **ikw)
+        host = m.SearchForInitialization(Qi, F)
+        same(host, want, "initialization, host arrays")
+        kps = np.zeros(Q.n, afv.KP_DTYPE)
+        kps["x"], kps["y"], kps["angle"] = Q.u, Q.v, Q.angles
+        f1.set_features(kps, Q.descriptors, sizes=np.ones(Q.n, np.float32))
+        same(f1.SearchForInitialization(m, fr, np.stack([Q.u, Q.v], 1), windowSize=float(Q.r[0])), host, "initialization, resident frames")
+        # map points by id: check_search holds the search through ids to the restatement and to afv_frame_match_projection / _fuse fed with
+        # the projected queries
+        for flavour in (TP.R.FRUSTUM, TP.R.FUSE):
+            sc = _points_scene(flavour, desc)
+            rigs.append(TP.Rig(afv, gpu_ctx, sc, P=sc.P, feat=sc.feat))
+            assert TP.check_search(afv, rigs[-1], sc) >= 5
+    finally:
+        afv.FeatureMatcher.setDescriptorDistanceThresholds(75.0)
+        for r in rigs:
+            r.close()
+        table.close(); f1.close(); fr.close()

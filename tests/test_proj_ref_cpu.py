@@ -8,7 +8,7 @@ The constants of the kernels the scenes are built to exceed (nothing is imported
   IK = 8         csrc/k_project.hip:38   keys per query of SearchForInitialization
   PW_LIST = 256  csrc/k_project.hip:178  slots of the dense candidate list; a chunk is 64 lanes x PW_CPL = 4 cells = 256 cells (:128)
   PW_T = 1024    csrc/k_project.hip:675  threads of the fixed point: live queries are taken 1024 at a time (`tid < nlive`)
-  the fixed point runs when its tables fit 150 KiB - 32 KiB - 2 KiB of LDS (k_project.hip:1668-1677, afv_api.hip:1891-1893);
+  the fixed point runs when its tables fit 150 KiB - 32 KiB - 2 KiB of LDS (afv_project_prepare in k_project.hip, choose_route in afv_project.hip);
   the ordered walk stages the queries' records in LDS while 33920 + 64 * nq <= 128 KiB (k_project.hip:421-422, :1731-1732).
 """
 import numpy as np
@@ -166,7 +166,7 @@ def test_size_regimes_lie_on_both_sides_of_the_limits():
     # the two walk regimes with the fixed point out of reach: staged below 1520 queries, unstaged above
     assert WALK_FIXED + WALK_REC * 1500 <= WALK_MAX < WALK_FIXED + WALK_REC * 2500
     # SearchForInitialization on the same scenes (tests/test_gpu_proj_scenes.py sends every regime through it): its fixed point runs on the
-    # small ones only, and never above 32767 queries (16-bit tables, afv_api.hip)
+    # small ones only, and never above 32767 queries (16-bit tables, choose_route in afv_project.hip)
     iside = {k: init_wg_lds(F.N, Q.n) <= WG_LDS_MAX and Q.n <= 32767 for k, (F, Q) in REGIMES.items()}
     assert iside["grid-1x1"] and iside["chunk-256"] and iside["n3000-cluster-64x48"]
     assert not iside["live2500-rescans"] and not iside["n8192-nq1"] and not iside["grid-8192-cells"]
@@ -216,3 +216,47 @@ def test_size_regime_scenes(oracle, name):
                 assert len(live) > 2 * PW_T and (pos >= PW_T).any() and (pos >= 2 * PW_T).any()
     if name.startswith(("n3000-cluster", "chunk-")) or name == "live2500-rescans":
         assert visits <= MAX_VISITS, "this scene's branch reach is proved by the restatement's trace"
+
+
+@pytest.mark.parametrize("desc", ["b32", "f64"])
+def test_the_every_route_scene_needs_its_masks_its_histogram_and_its_order(oracle, desc):
+    """PS.every_route_scene (tests/test_gpu_proj_scenes.py::test_one_scene_through_every_projection_route): the oracle equals the
+    restatement on every search the GPU test sends it through; a third of the queries match; a query's first choice is held by an earlier
+    query of the same call, and SearchForInitialization sees features change hands; the answer changes when the occupancy mask, the holes
+    in qvalid, the orientation check, the stereo gate or the chi-square gate is taken away - so a route that drops one of them shows"""
+    import copy
+    s = PS.every_route_scene(desc)
+    F, Q = s["F"], s["Q"]
+    assert F.N == 70 and Q.n == 65 and 0 < int(F.occupied.sum()) < 8 and 0 < int((Q.valid == 0).sum()) < 8 and Q.valid[64]
+    kw = dict(th_high=75.0, nnratio=0.9, check_orientation=True, last_frame=True)
+    got, n, tr = R.match_projection(F, Q, **kw)
+    want, wn = oracle.match_projection(F, Q, **kw)
+    assert n == wn and np.array_equal(got, want)
+    assert 3 * n >= Q.n
+    assert tr["longest_chain"] >= 1 and tr["drop"]["occupied"] > 0
+    bare = copy.copy(F); bare.occupied = None
+    assert not np.array_equal(oracle.match_projection(bare, Q, **kw)[0], want)
+    allq = copy.copy(Q); allq.valid = None
+    assert not np.array_equal(oracle.match_projection(F, allq, **kw)[0], want)
+    assert oracle.match_projection(F, Q, **dict(kw, check_orientation=False))[1] > n
+    gs, ns, trs = R.match_projection(s["Fs"], s["Qs"], **kw)
+    ws, wsn = oracle.match_projection(s["Fs"], s["Qs"], **kw)
+    assert ns == wsn and np.array_equal(gs, ws) and trs["drop"]["stereo"] > 0 and not np.array_equal(ws, want) and 3 * ns >= Q.n
+    fkw = dict(th_high=75.0, fuse=True)
+    for Fx, Qx in ((F, Q), (s["F1"], s["Q2"])):
+        g, gn, _ = R.match_projection(Fx, Qx, **fkw)
+        w, wn2 = oracle.match_projection(Fx, Qx, **fkw)
+        assert gn == wn2 and np.array_equal(g, w) and 3 * gn >= Qx.n
+    Fi = copy.copy(F); Fi.inf = (np.float32(1.0) / (F.sizes * F.sizes)).astype(np.float32)
+    g, gn, trf = R.match_projection(Fi, Q, **fkw)
+    w, wn2 = oracle.match_projection(Fi, Q, **fkw)
+    assert gn == wn2 and np.array_equal(g, w) and trf["drop"]["chi2_2dof"] > 0 and gn < oracle.match_projection(F, Q, **fkw)[1]
+    g, gn, _ = R.match_sim3(F, Q, s["F1"], s["Q2"], th_high=75.0)
+    w, wn2 = oracle.match_sim3(F, Q, s["F1"], s["Q2"], th_high=75.0)
+    assert gn == wn2 and np.array_equal(g, w) and 3 * gn >= Q.n
+    ikw = dict(th_low=75.0, nnratio=0.9, check_orientation=True)
+    for Qx in (s["Qi"], Q):
+        g, gn, tri = R.match_initialization(F, Qx, **ikw)
+        w, wn2 = oracle.match_initialization(F, Qx, **ikw)
+        assert gn == wn2 and np.array_equal(g, w) and 3 * gn >= Q.n and tri["steals"] >= 1
+    assert float(F.sizes.max()) < PS.INIT_MAX_SIZE and bool(np.all(Q.r == Q.r[0]))   # what the call between resident frames can state
