@@ -121,6 +121,21 @@ class PointProjection(C.Structure):
 
 
 PT_FRUSTUM, PT_LASTFRAME, PT_RELOC, PT_FUSE = 0, 1, 2, 3
+
+
+class PoseJob(C.Structure):
+    """afv_pose_job: one Optimizer::PoseOptimization on a resident frame"""
+    _fields_ = [("struct_size", C.c_uint32), ("pts", C.c_void_p), ("Rcw", C.c_void_p), ("tcw", C.c_void_p)]
+
+
+class PoseResult(C.Structure):
+    """afv_pose_result: the pose, the counts, mvbOutlier and the per-round trace of afv_frame_pose_optimize"""
+    _fields_ = [("struct_size", C.c_uint32), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("n_good", C.c_int32), ("n_edges", C.c_int32),
+                ("rounds", C.c_int32), ("outlier", C.c_void_p), ("iterations", C.c_int32 * 4), ("trials", C.c_int32 * 4),
+                ("chi2", C.c_double * 4), ("lambda_", C.c_double * 4)]
+
+
+POSE_MAX_JOBS = 64
 POINTS_MAX_CAPACITY = 1 << 22
 PTF_SET, PTF_BAD, PTF_OBSERVED = 1, 2, 4   # afv_points_get's flag bits
 
@@ -243,6 +258,7 @@ SYMBOLS = {
     "afv_frame_search_points": (_i, [_vp, C.POINTER(PointSearch), _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_frame_fuse_points": (_i, [_vp, C.POINTER(PointSearch), _i, _vp, _vp]),
     "afv_frame_project_points": (_i, [_vp, C.POINTER(PointSearch), C.POINTER(PointProjection)]),
+    "afv_frame_pose_optimize": (_i, [_vp, _vp, C.POINTER(PoseJob), _i, C.POINTER(PoseResult)]),
     "afv_vocab_set_weights": (_i, [_vp, _vp, _vp, _vp]),
     "afv_bow_vector": (_i, [_vp, _vp, _vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_frame_get_bowvec": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),

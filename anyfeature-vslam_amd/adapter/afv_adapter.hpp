@@ -387,6 +387,38 @@ class DeviceFrame {
     void SetPose(const float Rcw[9], const float tcw[3], const float Ow[3], float fx, float fy, float cx, float cy, float mbf) {
         const int rc = afv_frame_set_pose(f, Rcw, tcw, Ow, fx, fy, cx, cy, mbf);
         if (rc != AFV_OK) fatal("afv_frame_set_pose", rc, ctx);
+        for (int k = 0; k < 9; ++k) mRcw[k] = Rcw[k];
+        for (int k = 0; k < 3; ++k) { mtcw[k] = tcw[k]; mOw[k] = Ow[k]; }
+        mK[0] = fx; mK[1] = fy; mK[2] = cx; mK[3] = cy; mK[4] = mbf;
+        mHasPose = true;
+    }
+    // the pose last handed to SetPose: Rcw[9], tcw[3], Ow[3] (PoseOptimization with setPose updates it)
+    const float *Rcw() const { return mRcw; }
+    const float *tcw() const { return mtcw; }
+    const float *Ow() const { return mOw; }
+    // Optimizer::PoseOptimization(this) (Optimizer.cc:245-448; Tracking.cc:637, :760, :802, :1247-1278) in one launch: pts[i] = the id of
+    // the map point of feature i | -1.  Returns nInitialCorrespondences - nBad and fills mvbOutlier[N]; setPose: pFrame->SetPose (:445) -
+    // the optimised pose goes back into the frame with Ow = -Rcw^T tcw in float (Frame.cc:270-273), so the next search runs on it.  The
+    // host still walks mvbOutlier as Tracking.cc does (it clears pts[i] of the outliers and counts the inliers with observations)
+    int PoseOptimization(DeviceMapPoints &points, const std::vector<int32_t> &pts, std::vector<uint8_t> &mvbOutlier, bool setPose = true) {
+        afv_pose_job job{};
+        job.struct_size = sizeof(job);
+        job.pts = pts.data();
+        afv_pose_result r{};
+        r.struct_size = sizeof(r);
+        mvbOutlier.assign((size_t)std::max(N(), 0) + 1, 0);
+        r.outlier = mvbOutlier.data();
+        const int rc = afv_frame_pose_optimize(f, points.handle(), &job, 1, &r);
+        if (rc != AFV_OK) fatal("afv_frame_pose_optimize", rc, ctx);
+        mvbOutlier.resize((size_t)std::max(N(), 0));
+        if (setPose) {
+            // the intrinsics handed back are those of this object's SetPose: a pose set on the raw handle alone is unknown here
+            if (!mHasPose) fatal("DeviceFrame::PoseOptimization(setPose): the pose was not set through DeviceFrame::SetPose", AFV_EINVAL, ctx);
+            float Ow[3];
+            for (int k = 0; k < 3; ++k) Ow[k] = -r.Rcw[k] * r.tcw[0] + (-r.Rcw[3 + k] * r.tcw[1] + -r.Rcw[6 + k] * r.tcw[2]);
+            SetPose(r.Rcw, r.tcw, Ow, mK[0], mK[1], mK[2], mK[3], mK[4]);
+        }
+        return r.n_good;
     }
     // Tracking::SearchLocalPoints (Tracking.cc:988-1028): isInFrustum of every point of `ids` and SearchByProjection(F, vpMapPoints, th)
     // in one call.  assign[N] = index INTO ids of the point now in F.pts[i] | -1; inView[ids.size()] = mbTrackInView (IncreaseVisible)
@@ -432,6 +464,9 @@ class DeviceFrame {
     afv_ctx *context() { return ctx; }
 
   private:
+    float mRcw[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, mtcw[3] = {0, 0, 0}, mOw[3] = {0, 0, 0};  // the pose last handed to SetPose
+    float mK[5] = {0, 0, 0, 0, 0};                                                          // ... and fx fy cx cy mbf
+    bool mHasPose = false;
     afv_point_search PointSearch(DeviceMapPoints &points, const std::vector<int32_t> &ids, int flavour, float radiusTh, float th, float nnratio,
                                  bool checkOrientation, const uint8_t *occupied) const {
         afv_point_search s{};

@@ -28,6 +28,11 @@ static void points_free(afv_points *p) {
     delete p;
 }
 
+bool afv_points_is_live(const afv_points *p) {
+    std::lock_guard<std::mutex> lk(g_points_mutex);
+    return p && g_live_points.count(p);
+}
+
 void afv_points_release_all(afv_ctx *c) {
     std::vector<afv_points *> mine;
     mine.swap(c->points);

@@ -158,6 +158,27 @@ extern "C" void afv_launch_points_move(const DevPointsMove *job, hipStream_t str
 extern "C" void afv_launch_points_rows(const DevPointPlanes *P, const int *ids, int n, uint8_t *packed, const uint8_t *table, int table_cap,
                                        const int *slot, const int *idx, int gather, hipStream_t stream);
 
+// ---- k_poseopt.hip: Optimizer::PoseOptimization on a resident frame (host side: afv_poseopt.hip) ----
+struct DevPoseOut {          // what the workgroup of a job leaves
+    float R[9], t[3];
+    int n_good, n_edges, rounds;
+    int iterations[4], trials[4];
+    double chi2[4], lambda[4];
+};
+struct DevPoseArgs {         // k_pose_optimize: a kernel argument
+    const float *pos[3];     // the store: XYZ planes and flags over `cap` ids
+    const uint8_t *flags;
+    int cap;
+    const float *x, *y, *ur, *inf;  // the frame: mvKeysUn, mvuRight, keyPtsInf over n features, read in place
+    int n;
+    float fx, fy, cx, cy, bf;
+    const int *pts;          // [njobs][n] point id | -1
+    const float *poses;      // [njobs][12] Rcw row-major, tcw
+    DevPoseOut *out;         // [njobs]
+    uint8_t *outlier;        // [njobs][n]
+};
+extern "C" void afv_launch_pose_optimize(const DevPoseArgs *args, int njobs, hipStream_t stream);
+
 extern "C" void afv_launch_bow_transform(const DevVocab *v, const uint32_t *desc, int n, int levelsup, int *leaf_node,
                                          int *node_at_level, int *rank_at_level, hipStream_t stream);
 extern "C" int afv_launch_bow_transform_f32(const DevVocab *v, const float *desc, int n, int dim, int levelsup, int *leaf_node, int *node_at_level,
@@ -645,6 +666,7 @@ void afv_table_release_all(afv_ctx *c);  // afv_destroy: tables / communicators 
 void afv_frame_release_all(afv_ctx *c);  // ... and so do its frames
 bool afv_frame_is_live(const afv_frame *f);  // afv_frame.hip: the pointer names a frame that was not destroyed
 void afv_points_release_all(afv_ctx *c); // ... and its map-point stores
+bool afv_points_is_live(const afv_points *p);  // afv_points.hip: the pointer names a store that was not destroyed
 int afv_frame_after_extract(afv_frame *f, hipStream_t s);  // afv_frame.hip: k_frame_grid behind the describe kernel of afv_frame_extract
 // afv_stereo.hip: a keep_pyramid frame takes device copies of the levels of frame slot 0 of the extraction that just ran on stream s
 int afv_frame_keep_pyramid(afv_frame *f, const FrameSrc &src, hipStream_t s);

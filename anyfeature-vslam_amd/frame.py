@@ -277,6 +277,7 @@ class Frame:
         o = np.ascontiguousarray(Ow, np.float32).reshape(3)
         self.ctx.check(self.lib.afv_frame_set_pose(self.handle, ptr(R), ptr(t), ptr(o), float(fx), float(fy), float(cx), float(cy), float(mbf)),
                        "afv_frame_set_pose")
+        self._intrinsics = (fx, fy, cx, cy, mbf)  # what PoseOptimization hands back to set_pose with the optimised pose
 
     def _point_search(self, points, ids, flavour, radiusTh, viewingCosLimit=0.5, th=0.0, nnratio=0.0, check_orientation=False, qframe=None,
                       qangle=None, occupied=None, radius_scale=None):
@@ -352,3 +353,48 @@ class Frame:
         nm = np.zeros(1, np.int32)
         self.ctx.check(self.lib.afv_frame_fuse_points(self.handle, C.byref(s), int(bool(use_inf_gate)), ptr(out), ptr(nm)), "afv_frame_fuse_points")
         return out[:s.nq].copy(), int(nm[0])
+
+    # ---- Optimizer::PoseOptimization on the device ----
+    def PoseOptimizationBatch(self, points, jobs):
+        """afv_frame_pose_optimize over several jobs on this frame (the relocalisation loop, Tracking.cc:1247-1278: one per candidate
+        keyframe).  jobs: a list of pts[N] (point id | -1; the frame's pose) or of (pts, Rcw, tcw).  Returns a list of dicts: n_good, outlier
+        (bool [N]), Tcw (4 x 4 float32), Rcw, tcw, n_edges, rounds, and the per-round trace iterations, trials, chi2, lam.  The frame's
+        stored pose does not change."""
+        n, nj = self.N, len(jobs)
+        J = (_lib.PoseJob * max(nj, 1))()
+        Rs = (_lib.PoseResult * max(nj, 1))()
+        keep, flags = [], np.zeros((max(nj, 1), max(n, 1)), np.uint8)
+        for j, job in enumerate(jobs):
+            pts, R, t = job if isinstance(job, tuple) else (job, None, None)
+            pts = np.ascontiguousarray(pts, np.int32).reshape(-1)
+            if len(pts) != n:
+                raise ValueError("pts has %d entries, the frame %d features" % (len(pts), n))
+            R = None if R is None else np.ascontiguousarray(R, np.float32).reshape(9)
+            t = None if t is None else np.ascontiguousarray(t, np.float32).reshape(3)
+            keep.append((pts, R, t))
+            J[j].struct_size = C.sizeof(_lib.PoseJob)
+            J[j].pts, J[j].Rcw, J[j].tcw = ptr(pts), ptr(R), ptr(t)
+            Rs[j].struct_size = C.sizeof(_lib.PoseResult)
+            Rs[j].outlier = flags[j].ctypes.data_as(C.c_void_p)
+        self.ctx.check(self.lib.afv_frame_pose_optimize(self.handle, points.handle, J, nj, Rs), "afv_frame_pose_optimize")
+        out = []
+        for j in range(nj):
+            r = Rs[j]
+            Rcw, tcw = np.array(r.Rcw, np.float32).reshape(3, 3), np.array(r.tcw, np.float32)
+            Tcw = np.eye(4, dtype=np.float32)
+            Tcw[:3, :3], Tcw[:3, 3] = Rcw, tcw
+            out.append(dict(n_good=int(r.n_good), outlier=flags[j, :n] != 0, Tcw=Tcw, Rcw=Rcw, tcw=tcw, n_edges=int(r.n_edges), rounds=int(r.rounds),
+                            iterations=np.array(r.iterations, np.int32), trials=np.array(r.trials, np.int32), chi2=np.array(r.chi2, np.float64),
+                            lam=np.array(r.lambda_, np.float64)))
+        return out
+
+    def PoseOptimization(self, points, pts, set_pose=True):
+        """Optimizer::PoseOptimization(&frame) (Optimizer.cc:245-448): pts[i] = the id of the map point of feature i | -1.  Returns
+        (nGood, mvbOutlier [N] bool, Tcw 4 x 4).  set_pose: pFrame->SetPose(Tcw) (:445) - the optimised pose goes to set_pose with
+        Ow = -Rcw^T tcw in float32 (Frame.cc:270-273), so the next search runs on it without the pose leaving this call."""
+        r = self.PoseOptimizationBatch(points, [pts])[0]
+        if set_pose:
+            Rcw, tcw = r["Rcw"], r["tcw"]
+            Ow = np.array([-Rcw[0, k] * tcw[0] + (-Rcw[1, k] * tcw[1] + -Rcw[2, k] * tcw[2]) for k in range(3)], np.float32)  # float32 products and sums
+            self.set_pose(Rcw, tcw, Ow, *self._intrinsics)
+        return r["n_good"], r["outlier"], r["Tcw"]

@@ -696,6 +696,51 @@ int afv_frame_fuse_points(afv_frame *f, const afv_point_search *s, int use_inf_g
 /* the projection alone, any flavour (tests; hosts that want mTrackProjX and the like) */
 int afv_frame_project_points(afv_frame *f, const afv_point_search *s, afv_point_projection *host_out);
 
+/* ---- pose optimisation: Optimizer::PoseOptimization (src/Optimizer.cc:245-448) for a resident frame.  It is what Tracking calls between
+ * the searches (Tracking.cc:637, :760, :802 and, per candidate keyframe, :1247, :1263, :1278).  Everything it reads is on the device: mvKeysUn,
+ * mvuRight and keyPtsInf with the frame, XYZ per point id in the store, the intrinsics and mbf with the frame's pose (afv_frame_set_pose).
+ * A call uploads pts[N] (4 bytes per feature) and the initial pose of each job and runs ONE launch, one 1024-thread workgroup per job: the
+ * four rounds, the Levenberg iterations and trials, the 6 x 6 solve and the classification all happen in the kernel (csrc/k_poseopt.hip).
+ *
+ * g2o is an empty directory in the reference: the arithmetic is restated after upstream g2o as bundled with ORB-SLAM2 - parity unpinned.
+ * The normative semantics are tests/_poseopt_ref.py; the device is held to it bit for bit.  Feature i is an edge when pts[i] >= 0 and that
+ * id was set in the store (isBad is not consulted, :282; a never-set id is no point); mvuRight[i] < 0 makes it a mono edge, else stereo.
+ * Fewer than 3 edges: n_good = 0, rounds = 0, the pose comes back as it went in and no flag is set (:362).
+ * Deliberate deviations from upstream:
+ *   P1  every edge is classified at the round's final ACCEPTED pose (upstream leaves an inlier edge with the error of the last trial,
+ *       rejected or not, when the call ends on a rejection).
+ *   P2  a chi2 that is not finite is an outlier (upstream: NaN > th is false).
+ *   P3  the state is R (3 x 3) and t in double; a step is R <- dR R, t <- dR t + V upsilon, no quaternion in between.
+ *   P4  the coefficients of the exponential map are fixed 16-term Horner polynomials in theta^2, no library sin / cos; a step with
+ *       theta^2 > pi^2 is a failed trial.  Their accuracy: (1 - cos)/theta^2 and (theta - sin)/theta^3 within 4 ulp of their values over
+ *       [0, pi] (measured 2.9 and 1.6); sin/theta within 4 ulp of its value up to theta = 2 (2.3) and within 2^-52 ABSOLUTE (1.9e-16)
+ *       beyond - 5.8 ulp of its value at 2.5, 29 at 3.0, 88 at 3.1, no relative accuracy at pi, where it crosses zero.
+ *   P5  every sum over the edges is a perfect binary tree over the feature index (leaves: the smallest power of two >= max(N, 1); no active
+ *       edge = +0.0); the 6 x 6 solve is an unpivoted L L^T in a fixed loop order, a pivot that is not positive and finite is a failed
+ *       trial; a round with no active edge leaves the pose as it is.
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+typedef struct {
+    uint32_t struct_size;         /* sizeof(afv_pose_job) */
+    const int32_t *pts;           /* [N] host: point id | -1, N = the frame's feature count */
+    const float *Rcw, *tcw;       /* the initial pose (9 floats row-major, 3 floats); both NULL = the frame's pose */
+} afv_pose_job;
+typedef struct {
+    uint32_t struct_size;         /* sizeof(afv_pose_result), set by the caller */
+    float Rcw[9], tcw[3];         /* out: the pose of the last round run (Converter::toMatrix4f) */
+    int32_t n_good, n_edges, rounds; /* out: nInitialCorrespondences - nBad; nInitialCorrespondences; rounds run (0, 1 or 4) */
+    uint8_t *outlier;             /* [N] host, may be NULL: mvbOutlier */
+    int32_t iterations[4], trials[4]; /* out, per round: calls of OptimizationAlgorithmLevenberg::solve; trials in them */
+    double chi2[4], lambda[4];    /* out, per round: the robust chi2 at its final pose; the final lambda (the trace the tests compare) */
+} afv_pose_result;
+/* njobs 1 .. 64 jobs on one frame (the relocalisation loop: one per candidate keyframe); synchronous; the frame's stored pose does not
+ * change.  The intrinsics and mbf are the frame's, so the frame must have been given a pose once (afv_frame_set_pose) even when every job
+ * brings its own.  AFV_EINVAL before any launch: NULL arguments, a frame without features (or whose mvKeysUn are missing), without a pose,
+ * a job with only one of Rcw / tcw, more than AFV_POSE_MAX_FEATURES features, store and frame on different contexts, an id at or beyond the capacity, njobs out of range, an
+ * unknown struct_size in either array.  The descriptor kind of the store does not matter here. */
+int afv_frame_pose_optimize(afv_frame *f, afv_points *points, const afv_pose_job *jobs, int njobs, afv_pose_result *results);
+#define AFV_POSE_MAX_JOBS 64
+#define AFV_POSE_MAX_FEATURES 8192 /* features of the frame a call takes (eight per thread of the workgroup); more: AFV_EINVAL */
+
 /* engine of the ordered phase of the projection searches / SearchForInitialization (identical results):
  *   1: one fixed point over all live queries of a job on a 1024-thread workgroup (round 5)   0: the ordered walk of rounds 1-4 on one
  *   wavefront   2 (default): 1 whenever the job's tables fit the workgroup's LDS, else 0   3: as 1, but ranking and ordered phase as two
