@@ -10,9 +10,12 @@
 // 512 rotated test locations inside the 37x37 neighbourhood of a keypoint are ever sampled, so each wavefront stages
 // the 43x43 UNBLURRED patch around its keypoint in LDS (reflect-101 at the image edge = cv::ORB's apron), computes
 // the intensity-centroid moments from it, runs the ROW pass of the blur over the patch once (integer taps
-// [18,34,49,55,49,34,18], two v_dot4_u32_u8 per output on funnel-shifted dwords, exact in 16 bits) and evaluates the COLUMN
-// pass + round-half-even(S/65536) only at the sampled locations.  A test that falls outside the level ROI reads the unblurred apron pixel, as in OpenCV
-// where only the ROI is blurred in place.  No blurred image ever touches HBM.
+// [18,34,49,55,49,34,18], v_dot4_u32_u8 on the aligned dwords with the taps laid out per output, exact in 16 bits; the lane -> (row group,
+// dword group) mapping is fixed, the loop unrolled, the loads of a step issued before the store of the step before) and evaluates the COLUMN
+// pass + round-half-even(S/65536) only at the sampled locations.  The row-filtered plane is stored as INTERLEAVED ROW PAIRS (one dword =
+// rows 2j and 2j + 1 of a column): the seven rows of a sample are four dwords at one address + immediates, four v_dot2_u32_u16
+// (-DDS_ROW_MAJOR_PLANE keeps the u16 row-major plane of rounds 1-6 for A / B runs).  A test that falls outside the level ROI reads the
+// unblurred apron pixel, as in OpenCV where only the ROI is blurred in place.  No blurred image ever touches HBM.
 #include "afv_device.h"
 #include "afv_wave.h"
 #include "afv_runtime.h"  // the launchers below are declared there: a signature that drifts is a compile error, not a silent ABI mismatch
@@ -121,43 +124,75 @@ __device__ __forceinline__ void wave_sync() {
 __device__ __forceinline__ uint32_t blur_round(uint32_t S) { return __builtin_amdgcn_cvt_pk_u8_f32((float)S * (1.0f / 65536.0f), 0, 0u); }
 
 // Row pass of the separable 8U filter over the whole staged patch, once per keypoint: H[r][xh] = sum_k taps[k] * P[r][xh + k]
-// for xh = 0..39 (<= 257 * 255 = 65535: exact in 16 bits).  One lane per group of 4 adjacent outputs: 3 aligned dwords in, two
-// v_dot4_u32_u8 per output on funnel-shifted dwords, 4 x u16 out.
+// for xh = 0..39 (<= 257 * 255 = 65535: exact in 16 bits).  One lane per group of 4 adjacent outputs: 3 aligned dwords in, ten
+// v_dot4_u32_u8, 4 x u16 out.
 #ifndef HP
-#define HP 40  // u16 pitch of the row-filtered plane (80 bytes: 8-byte aligned rows, no padding: 44 cost a workgroup of occupancy per CU)
+#define HP 40  // u16 pitch of a plane row (80 bytes: 8-byte aligned rows, no padding: 44 cost a workgroup of occupancy per CU)
 #endif
-__device__ __forceinline__ void blur_rows(const uint8_t *P, uint16_t *H, int lane) {
-    // output k of a group = taps over bytes k .. k + 6 of the 12-byte window (d0, d1, d2): instead of shifting the DATA to the taps
-    // (two funnel shifts per output) the TAPS are laid out at the byte positions of every k - eleven constants in scalar registers,
-    // 2 + 3 + 3 + 3 dot products and no shifts for the four outputs
+#define ROW_GROUPS 10                 // dword groups of a plane row (HP / 4)
+#define ROW_LANES 6                   // (pair-)rows per wave step: lane = (lane / 10, lane % 10), lanes 60..63 idle
+#define GP (4 * HP)                   // interleaved plane: bytes of a pair-row (HP dwords)
+#define PAIR_ROWS ((PS + 1) / 2)      // 22: pair-row 21 = (row 42, 0)
+static_assert(HP == 4 * ROW_GROUPS && ROW_GROUPS * ROW_LANES <= 64, "row pass: lane mapping");
+static_assert(4 * (ROW_GROUPS - 1) + 12 <= PP, "row pass: the three dwords of the last group lie inside the patch row");
+
+// the four outputs of a group: output k = taps over bytes k .. k + 6 of the 12-byte window (d0, d1, d2).  Instead of shifting the DATA to the taps
+// (two funnel shifts per output) the TAPS are laid out at the byte positions of every k - constants in scalar registers,
+// 2 + 2 + 3 + 3 dot products and no shifts
+__device__ __forceinline__ void row_taps4(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t (&o)[4]) {
     constexpr unsigned long long TAPS = 18ull | (34ull << 8) | (49ull << 16) | (55ull << 24) | (49ull << 32) | (34ull << 40) | (18ull << 48);
-    for (int i = lane; i < PS * 10; i += 64) {
-        const int r = i / 10, g = i - r * 10;
-        const uint32_t *row = reinterpret_cast<const uint32_t *>(P + r * PP + g * 4);
-        const uint32_t d0 = row[0], d1 = row[1], d2 = row[2];
-        uint32_t o[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            // the 7 taps shifted up by k bytes inside a 96-bit field: its three dwords
-            const unsigned __int128 F = (unsigned __int128)TAPS << (8 * k);
-            const uint32_t t0 = (uint32_t)F, t1 = (uint32_t)(F >> 32), t2 = (uint32_t)(F >> 64);
-            uint32_t a = __builtin_amdgcn_udot4(d1, t1, __builtin_amdgcn_udot4(d0, t0, 0u, false), false);
-            if (t2) a = __builtin_amdgcn_udot4(d2, t2, a, false);
-            o[k] = a;
-        }
-        uint2 w;
-        w.x = o[0] | (o[1] << 16);
-        w.y = o[2] | (o[3] << 16);
-        *reinterpret_cast<uint2 *>(&H[r * HP + g * 4]) = w;
+    for (int k = 0; k < 4; ++k) {
+        // the 7 taps shifted up by k bytes inside a 96-bit field: its three dwords
+        const unsigned __int128 F = (unsigned __int128)TAPS << (8 * k);
+        const uint32_t t0 = (uint32_t)F, t1 = (uint32_t)(F >> 32), t2 = (uint32_t)(F >> 64);
+        uint32_t a = __builtin_amdgcn_udot4(d1, t1, __builtin_amdgcn_udot4(d0, t0, 0u, false), false);
+        if (t2) a = __builtin_amdgcn_udot4(d2, t2, a, false);
+        o[k] = a;
     }
 }
 
-// column pass + rounding at patch position (row y, column x), taps centred: exact integer arithmetic of the separable filter,
-// then round-half-even(S / 65536)
 typedef unsigned short ushort2d __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int blur_at(const uint16_t *H, int x, int y) {
-    const uint16_t *c = H + (__umul24((uint32_t)(y - 3), (uint32_t)HP) + (uint32_t)(x - 3));  // 24-bit multiply (y - 3 is 0 .. 36): a plain int product is a quarter-rate v_mul_lo_u32
+
+// (a & 0xffffff) * b + c with b a wave-uniform 24-bit constant, as ONE v_mad_u32_u24: written as a + b * ... in C the compiler re-associates
+// the sum with the shift-add that feeds it and ends up with a multiply, a shift and a three-input add
+__device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
+    return r;
+}
+
+#ifdef DS_ROW_MAJOR_PLANE
+// ---- u16 row-major plane (rounds 1-6; kept for A / B runs): H[r][xh] at u16 index r * HP + xh ----
+#define PLANE_BYTES (PS * HP * 2)
+#define ROW_STEPS ((PS + ROW_LANES - 1) / ROW_LANES)  // 8: rows rg, rg + 6, ..., rg + 42 (the last one for rg = 0 only)
+__device__ __forceinline__ void blur_rows(const uint8_t *P, uint8_t *plane, int lane) {
+    const uint32_t rg = ((uint32_t)lane * 205u) >> 11, g = (uint32_t)lane - rg * ROW_GROUPS;  // lane / 10, lane % 10 (lane < 64)
+    if (lane >= ROW_GROUPS * ROW_LANES) return;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(P + rg * PP + g * 4);
+    uint2 *dst = reinterpret_cast<uint2 *>(plane + rg * (2 * HP) + g * 8);
+    uint32_t d[3] = {src[0], src[1], src[2]}, n[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < ROW_STEPS; ++k) {
+        const bool last = (k + 1) * ROW_LANES + ROW_LANES > PS;  // step k + 1 has rows past the patch
+        // the loads of step k + 1 BEFORE the store of step k (the slice layout below: that store cannot reach them)
+        if (k + 1 < ROW_STEPS && (!last || rg < PS - (k + 1) * ROW_LANES)) {
+            const uint32_t *s = src + (k + 1) * ROW_LANES * (PP / 4);
+            n[0] = s[0], n[1] = s[1], n[2] = s[2];
+        }
+        uint32_t o[4];
+        row_taps4(d[0], d[1], d[2], o);
+        uint2 w;
+        w.x = o[0] | (o[1] << 16);
+        w.y = o[2] | (o[3] << 16);
+        if (k * ROW_LANES + ROW_LANES <= PS || rg < PS - k * ROW_LANES) dst[k * ROW_LANES * (2 * HP / 8)] = w;
+        d[0] = n[0], d[1] = n[1], d[2] = n[2];
+    }
+}
+
+// column pass + rounding with c = &H[yy][xh] (yy = y - 3, xh = x - 3: taps centred on patch position (x, y)): exact integer arithmetic
+// of the separable filter, then round-half-even(S / 65536)
+__device__ __forceinline__ int blur_col(const uint16_t *c) {
     // symmetric taps: rows k and 6 - k share a weight -> three v_dot2_u32_u16 on (row k, row 6 - k) pairs + the centre row
     ushort2d p0, p1, p2, t0, t1, t2;
     p0.x = c[0];
@@ -175,6 +210,95 @@ __device__ __forceinline__ int blur_at(const uint16_t *H, int x, int y) {
     S = __builtin_amdgcn_udot2(p2, t2, S, false);
     return (int)blur_round(S);
 }
+__device__ __forceinline__ int blur_at(const uint8_t *plane, int x, int y) {
+    // 24-bit multiply (y - 3 is 0 .. 36): a plain int product is a quarter-rate v_mul_lo_u32
+    return blur_col(reinterpret_cast<const uint16_t *>(plane) + (__umul24((uint32_t)(y - 3), (uint32_t)HP) + (uint32_t)(x - 3)));
+}
+// interior sample straight from the float bits fx = 0x4B400000 + ix, fy = 0x4B400000 + iy (the rounding trick of the caller): byte address
+// lds(plane) + 2 ((18 + iy) HP + 18 + a + ix) = 2 HP * (fy & 0xffffff) + 2 fx + k_addr (mod 2^32) - one shift-add, one 24-bit multiply-add
+__device__ __forceinline__ uint32_t blur_addr_const(uint32_t lds_plane, int a) {
+    return lds_plane + 2u * (uint32_t)((PR - 3) * HP + PR - 3 + a) - 2u * 0x4B400000u - (uint32_t)(2 * HP) * 0x400000u;
+}
+__device__ __forceinline__ int blur_bits(int fx, int fy, uint32_t k_addr) {
+    const uint32_t addr = mad_u24((uint32_t)fy, (uint32_t)(2 * HP), ((uint32_t)fx << 1) + k_addr);
+    return blur_col((const uint16_t *)(__attribute__((address_space(3))) const uint16_t *)(uintptr_t)addr);
+}
+#else
+// ---- plane of interleaved row pairs: G[j][xh] = H[2j][xh] | H[2j + 1][xh] << 16, j = 0..21, one dword per column, pair-rows GP = 160 bytes
+// apart; H[43] (no such patch row) = 0.  Item = (pair-row, dword group): two patch rows in, 20 dot products, 4 v_lshl_or, one 16-byte store ----
+#define PLANE_BYTES (PAIR_ROWS * GP)
+#define ROW_STEPS ((PAIR_ROWS + ROW_LANES - 1) / ROW_LANES)  // 4: pair-rows jg, jg + 6, jg + 12, jg + 18 (the last one for jg < 4)
+__device__ __forceinline__ void blur_rows(const uint8_t *P, uint8_t *plane, int lane) {
+    const uint32_t jg = ((uint32_t)lane * 205u) >> 11, g = (uint32_t)lane - jg * ROW_GROUPS;  // lane / 10, lane % 10 (lane < 64)
+    if (lane >= ROW_GROUPS * ROW_LANES) return;
+    constexpr int LAST = (ROW_STEPS - 1) * ROW_LANES;        // first pair-row of the last step
+    constexpr bool ODD_TAIL = (PS & 1) != 0;                 // the last pair-row has no upper row
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(P + jg * (2 * PP) + g * 4);
+    uint4 *dst = reinterpret_cast<uint4 *>(plane + jg * GP + g * 16);
+    uint32_t d[6] = {src[0], src[1], src[2], src[PP / 4], src[PP / 4 + 1], src[PP / 4 + 2]}, n[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < ROW_STEPS; ++k) {
+        // the loads of step k + 1 BEFORE the store of step k (the slice layout below: that store cannot reach them).  Nothing past the
+        // slice is read: pair-rows >= PAIR_ROWS are skipped and the missing upper row of the last pair-row stays 0
+        if (k + 1 < ROW_STEPS) {
+            const uint32_t *s = src + (k + 1) * ROW_LANES * (2 * PP / 4);
+            const bool tail = k + 1 == ROW_STEPS - 1;
+            if (!tail || jg < PAIR_ROWS - LAST) n[0] = s[0], n[1] = s[1], n[2] = s[2];
+            if (!tail || jg < PAIR_ROWS - LAST - (ODD_TAIL ? 1 : 0)) n[3] = s[PP / 4], n[4] = s[PP / 4 + 1], n[5] = s[PP / 4 + 2];
+        }
+        uint32_t e[4], o[4];
+        row_taps4(d[0], d[1], d[2], e);
+        row_taps4(d[3], d[4], d[5], o);
+        uint4 w;
+        w.x = e[0] | (o[0] << 16);
+        w.y = e[1] | (o[1] << 16);
+        w.z = e[2] | (o[2] << 16);
+        w.w = e[3] | (o[3] << 16);
+        if (k < ROW_STEPS - 1 || jg < PAIR_ROWS - LAST) dst[k * ROW_LANES * (GP / 16)] = w;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) d[i] = n[i], n[i] = 0u;
+    }
+}
+
+// column pass + rounding with c = &G[yy >> 1][xh] and sh = 16 * (yy & 1) in its low five bits (yy = y - 3, xh = x - 3: taps centred on
+// patch position (x, y)).  The seven rows yy .. yy + 6 are the u16 slots (yy & 1) .. (yy & 1) + 6 of the four dwords c[0], c[HP], c[2 HP],
+// c[3 HP]: funnel-shifted down by the parity they meet the tap pairs (18, 34) (49, 55) (49, 34) (18, 0) - no permutes, no centre multiply.
+// yy <= 36, so the last dword is pair-row <= 21; slot 7 (weight 0) is H[43] = 0 at most.  Exact integer arithmetic of the separable filter,
+// then round-half-even(S / 65536)
+__device__ __forceinline__ int blur_col(const uint32_t *c, uint32_t sh) {
+    const uint32_t d0 = c[0], d1 = c[HP], d2 = c[2 * HP], d3 = c[3 * HP];
+    const uint32_t e0 = __builtin_amdgcn_alignbit(d1, d0, sh), e1 = __builtin_amdgcn_alignbit(d2, d1, sh), e2 = __builtin_amdgcn_alignbit(d3, d2, sh),
+                   e3 = d3 >> (sh & 31u);
+    ushort2d t0, t1, t2, t3;
+    t0.x = 18, t0.y = 34;
+    t1.x = 49, t1.y = 55;
+    t2.x = 49, t2.y = 34;
+    t3.x = 18, t3.y = 0;
+    uint32_t S = __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2d, e0), t0, 0u, false);
+    S = __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2d, e1), t1, S, false);
+    S = __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2d, e2), t2, S, false);
+    S = __builtin_amdgcn_udot2(__builtin_bit_cast(ushort2d, e3), t3, S, false);
+    return (int)blur_round(S);
+}
+__device__ __forceinline__ int blur_at(const uint8_t *plane, int x, int y) {
+    const uint32_t yy = (uint32_t)(y - 3);  // 0 .. 36
+    // 24-bit multiply: a plain int product is a quarter-rate v_mul_lo_u32
+    return blur_col(reinterpret_cast<const uint32_t *>(plane) + (__umul24(yy >> 1, (uint32_t)HP) + (uint32_t)(x - 3)), yy << 4);
+}
+// interior sample straight from the float bits fx = 0x4B400000 + ix, fy = 0x4B400000 + iy (the rounding trick of the caller): with
+// jb = (fy & 0xffffff) >> 1 = 0x200000 + (iy >> 1) (0x400000 and PR - 3 = 18 are even: the floor commutes) the byte address is
+// lds(plane) + GP ((18 + iy) >> 1) + 4 (18 + a + ix) = GP * jb + 4 fx + k_addr (mod 2^32) - a bit-field extract, one shift-add, one 24-bit
+// multiply-add; the parity of yy = 18 + iy is bit 0 of fy
+static_assert(((PR - 3) & 1) == 0, "blur_bits: the parity of a plane row is the parity of iy");
+__device__ __forceinline__ uint32_t blur_addr_const(uint32_t lds_plane, int a) {
+    return lds_plane + (uint32_t)(GP * ((PR - 3) / 2) + 4 * (PR - 3 + a)) - 4u * 0x4B400000u - (uint32_t)GP * 0x200000u;
+}
+__device__ __forceinline__ int blur_bits(int fx, int fy, uint32_t k_addr) {
+    const uint32_t jb = ((uint32_t)fy >> 1) & 0x7fffffu;
+    const uint32_t addr = mad_u24(jb, (uint32_t)GP, ((uint32_t)fx << 2) + k_addr);
+    return blur_col((const uint32_t *)(__attribute__((address_space(3))) const uint32_t *)(uintptr_t)addr, (uint32_t)fy << 4);
+}
+#endif
 
 // MODE 0: the extraction pipeline (keypoints of the quadtree survivors + their descriptors: detectAndCompute);
 // MODE 1: keypoints only - position, IC angle, response (afv_orb_detect: detectKeypoints + filterKeypoints, Feature_orb32.cpp:26-40, :63-65);
@@ -187,15 +311,32 @@ __device__ __forceinline__ void describe_body(const Geo *__restrict__ geo_p, con
                                               int frame_base, int per_frame, int total_blocks, const DescribeMirror mir,
                                               const afv_keypoint *__restrict__ given) {
     // One LDS slice per wavefront holds BOTH the staged patch (u8, rows PP = 52 bytes apart: 13 dwords, odd -> rows spread over all
-    // LDS banks) and the row-filtered plane H (u16, rows 2 HP = 80 bytes apart) that is computed from it: H starts at byte 0, the patch
-    // at byte SLICE - PS * PP, and H row r ends at or before patch row r + 1 begins (80 r + 80 <= P_OFF + 52 (r + 1) for r <= 42), so the
-    // ascending row pass only ever overwrites patch rows it has consumed (rows sharing a wave iteration are read before anything of
-    // that iteration is written: DS operations of a wave execute in order).  3440 instead of 6028 bytes per keypoint: 8 instead of 6
-    // workgroups per CU.  The patch is dead after the row pass: the IC moments are taken first, and the rare test of a border keypoint
-    // that falls outside the level reads its (unblurred, reflected) pixel from the level image itself.
-    constexpr int SLICE = PS * HP * 2, P_OFF = SLICE - PS * PP;
-    static_assert(P_OFF % 4 == 0 && P_OFF >= 0 && 2 * HP * PS <= SLICE, "slice layout");
+    // LDS banks) and the row-filtered plane that is computed from it: the plane starts at byte 0, the patch ends where the slice ends
+    // (byte P_OFF = SLICE - PS * PP on).  The row pass walks the plane upwards, ROW_LANES (pair-)rows per step, and within a step every
+    // load precedes the store (DS operations of a wave execute in order; the loads of step k + 1 are even issued before the store of
+    // step k), so all it takes is that the plane rows of steps 0 .. k end at or before the first patch row of step k + 1 begins:
+    //   interleaved pairs: step k stores pair-rows < 6 (k + 1) = bytes < 960 (k + 1) and step k + 1 loads patch rows >= 12 (k + 1) = bytes
+    //     >= 1284 + 624 (k + 1): 336 (k + 1) <= 1284 holds for k + 1 <= 3, the last step (the static_assert below checks every step);
+    //   row-major u16: H row r ends before patch row r + 1 begins (80 r + 80 <= 1204 + 52 (r + 1) for r <= 42).
+    // The plane fills the slice exactly, and nothing past the slice is read: the row pass skips the rows a step has past the patch (patch
+    // row 43 would be the next wavefront's slice).  3520 (row-major: 3440) instead of 6028 bytes per keypoint: 14 080 bytes per workgroup,
+    // 8 workgroups (all 32 wavefronts) per CU.  The patch is dead after the row pass: the IC moments are taken first, and the rare test of
+    // a border keypoint that falls outside the level reads its (unblurred, reflected) pixel from the level image itself.
+    constexpr int SLICE = PLANE_BYTES, P_OFF = SLICE - PS * PP;
+    static_assert(P_OFF % 4 == 0 && P_OFF >= 0 && SLICE % 16 == 0, "slice layout");
+#ifdef DS_ROW_MAJOR_PLANE
     static_assert(2 * HP * (PS - 1) + 2 * HP <= P_OFF + PP * PS, "H row r must end before patch row r + 1 begins");
+#else
+    constexpr bool overlap_ok = [] {
+        for (int k = 0; k + 1 < ROW_STEPS; ++k)
+            if (GP * ROW_LANES * (k + 1) > P_OFF + PP * 2 * ROW_LANES * (k + 1)) return false;
+        return true;
+    }();
+    static_assert(overlap_ok, "the pair-rows of steps 0 .. k must end before the first patch row of step k + 1 begins");
+    static_assert(PAIR_ROWS * GP == SLICE && 2 * PAIR_ROWS - 1 == PS, "pair-row 21 holds patch row 42 and a zero upper half");
+    static_assert((PS - 1 - 6) / 2 + 3 < PAIR_ROWS, "a sample's four dwords (plane rows <= 36 + 6) lie inside the plane");
+#endif
+    static_assert(KP_PER_BLOCK * SLICE * 8 <= 160 * 1024, "8 workgroups per CU");
     __shared__ __attribute__((aligned(16))) uint8_t s_slice[KP_PER_BLOCK][SLICE];
 
     const Geo &geo = *geo_p;
@@ -267,7 +408,7 @@ __device__ __forceinline__ void describe_body(const Geo *__restrict__ geo_p, con
         pitch = L.pitch;
     }
     uint8_t *P = s_slice[wv] + P_OFF;
-    uint16_t *H = reinterpret_cast<uint16_t *>(s_slice[wv]);
+    uint8_t *H = s_slice[wv];  // the row-filtered plane
 
     // ---- 1. stage the 43x43 unblurred patch; P[r][a + c] = level(cx-21+c, cy-21+r) with reflect-101 ----
     const int px0 = cx - PR, py0 = cy - PR;
@@ -368,6 +509,10 @@ __device__ __forceinline__ void describe_body(const Geo *__restrict__ geo_p, con
     const int bx = MODE == 2 ? cx : (int)rintf(ptx * L.inv_scale), by = MODE == 2 ? cy : (int)rintf(pty * L.inv_scale);
     const int ox = bx - cx, oy = by - cy;  // 0 in practice; kept literal
     const int kox = ox - 0x4B400000, koy = oy - 0x4B400000;  // scalar: the mantissa offset of the rounding trick below and the (0) centre offset
+    // a patch inside the level whose BRIEF centre is the patch centre (always, see above): LDS addresses straight from the float bits
+    const bool direct = interior && (ox | oy) == 0;  // wave-uniform
+    uint32_t k_addr = blur_addr_const((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)H, a);
+    asm("" : "+s"(k_addr));  // one opaque scalar: the compiler would take it apart again and add its pieces per sample
     uint32_t words[8];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -383,16 +528,17 @@ __device__ __forceinline__ void describe_body(const Geo *__restrict__ geo_p, con
         const float rx0 = x0 * ca + y0 * -sb, ry0 = x0 * sb + y0 * ca, rx1 = x1 * ca + y1 * -sb, ry1 = x1 * sb + y1 * ca;
         // cvRound = round half to even: x + 1.5 * 2^23 leaves the rounded integer in the mantissa (|x| < 2^22; the addition rounds to
         // nearest even exactly where rintf does), one add per coordinate instead of v_rndne + v_cvt; the integer offset 0x4B400000
-        // folds into the address constants below
+        // folds into the address constant (direct) or is taken off with the centre offset (border)
         const float rmag = 12582912.0f;
-        const int ix0 = __float_as_int(rx0 + rmag) + kox, iy0 = __float_as_int(ry0 + rmag) + koy;
-        const int ix1 = __float_as_int(rx1 + rmag) + kox, iy1 = __float_as_int(ry1 + rmag) + koy;
+        const int fx0 = __float_as_int(rx0 + rmag), fy0 = __float_as_int(ry0 + rmag);
+        const int fx1 = __float_as_int(rx1 + rmag), fy1 = __float_as_int(ry1 + rmag);
         // inside the ROI -> blurred, outside -> unblurred apron (a patch that lies inside the level has no outside samples)
         int t0, t1;
-        if (interior) {
-            t0 = blur_at(H, PR + a + ix0, PR + iy0);
-            t1 = blur_at(H, PR + a + ix1, PR + iy1);
+        if (direct) {
+            t0 = blur_bits(fx0, fy0, k_addr);
+            t1 = blur_bits(fx1, fy1, k_addr);
         } else {
+            const int ix0 = fx0 + kox, iy0 = fy0 + koy, ix1 = fx1 + kox, iy1 = fy1 + koy;
             const int gx0 = cx + ix0, gy0 = cy + iy0, gx1 = cx + ix1, gy1 = cy + iy1;
             t0 = (gx0 >= 0 && gx0 < lw && gy0 >= 0 && gy0 < lh) ? blur_at(H, PR + a + ix0, PR + iy0)
                                                                  : (int)img[__umul24((uint32_t)afv_reflect101(gy0, lh), (uint32_t)pitch) + (uint32_t)afv_reflect101(gx0, lw)];
