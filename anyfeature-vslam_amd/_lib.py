@@ -135,6 +135,17 @@ class PoseResult(C.Structure):
                 ("chi2", C.c_double * 4), ("lambda_", C.c_double * 4)]
 
 
+class TriPointsJob(C.Structure):
+    """afv_tri_points_job: one (current keyframe, neighbour) pair of afv_table_triangulate"""
+    _fields_ = ([("struct_size", C.c_uint32)] +
+                [(k, C.c_float * n) for k, n in (("Rcw1", 9), ("tcw1", 3), ("Ow1", 3), ("Rcw2", 9), ("tcw2", 3), ("Ow2", 3))] +
+                [(k, C.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "invfx1", "invfy1", "fx2", "fy2", "cx2", "cy2", "invfx2", "invfy2",
+                                          "mb1", "mb2", "mbf1", "ratio_factor", "max_size1")])
+
+
+TRI_MAX_PAIRS = 64
+TRI_STATUS = ("no_match", "accepted", "low_parallax", "w_zero", "z1", "z2", "reproj1", "reproj2", "zero_dist", "scale_ratio", "not_finite")
+TRI_ROUTE = ("triangulated", "unproject_a", "unproject_b")
 POSE_MAX_JOBS = 64
 POINTS_MAX_CAPACITY = 1 << 22
 PTF_SET, PTF_BAD, PTF_OBSERVED = 1, 2, 4   # afv_points_get's flag bits
@@ -259,6 +270,8 @@ SYMBOLS = {
     "afv_frame_fuse_points": (_i, [_vp, C.POINTER(PointSearch), _i, _vp, _vp]),
     "afv_frame_project_points": (_i, [_vp, C.POINTER(PointSearch), C.POINTER(PointProjection)]),
     "afv_frame_pose_optimize": (_i, [_vp, _vp, C.POINTER(PoseJob), _i, C.POINTER(PoseResult)]),
+    "afv_table_set_scale": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "afv_table_triangulate": (_i, [_vp, _vp, _vp, C.POINTER(TriPointsJob), _i, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "afv_vocab_set_weights": (_i, [_vp, _vp, _vp, _vp]),
     "afv_bow_vector": (_i, [_vp, _vp, _vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_frame_get_bowvec": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),

@@ -1120,4 +1120,70 @@ class KeyFrameDatabase {
     std::vector<double> score;
 };
 
+// ---- new map points: the neighbour loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:265-472) over slots of the keyframe
+// table (include/afv_hip.h, "new map points").  The keyframes' sizes, depths and distorted keypoints sit in the table's scale planes
+// (afv_table_set_scale, or afv_table_set_from_frame at promotion); the new points land in the resident store without a host upload. ----
+class NewMapPoints {
+  public:
+    struct Created {  // one new point: its id in the store and its two observations (slot, feature)
+        int32_t id, slot1, idx1, slot2, idx2;
+    };
+    struct Result {  // per pair: rows of `cap` entries
+        std::vector<uint8_t> status, route;  // AFV_TRI_* / AFV_TRI_ROUTE_*
+        std::vector<float> x3d;              // cap x 3 per pair
+        std::vector<int32_t> new_id, n_new;  // -1 = not accepted; per pair
+    };
+    NewMapPoints(afv_ctx *ctx_, afv_table *table_, int cap_) : ctx(ctx_), table(table_), cap(cap_) {}
+
+    // the match loop (:315-461) for npairs pairs in ONE call: two launches, one wait.  match12: npairs rows of cap entries as
+    // afv_table_match_triangulation returns them; points may be null
+    Result Triangulate(const std::vector<int32_t> &pair_a, const std::vector<int32_t> &pair_b, std::vector<afv_tri_points_job> jobs,
+                       const int32_t *match12, DeviceMapPoints *points, int32_t first_id) {
+        const size_t np = pair_a.size(), cells = np * (size_t)cap;
+        Result r;
+        r.status.assign(cells, 0); r.route.assign(cells, 0); r.x3d.assign(cells * 3, 0.0f); r.new_id.assign(cells, -1); r.n_new.assign(np, 0);
+        for (afv_tri_points_job &j : jobs) j.struct_size = (uint32_t)sizeof(afv_tri_points_job);
+        const int rc = afv_table_triangulate(table, pair_a.data(), pair_b.data(), jobs.data(), (int)np, match12, points ? points->handle() : nullptr, first_id,
+                                             r.status.data(), r.route.data(), r.x3d.data(), r.new_id.data(), r.n_new.data());
+        if (rc != AFV_OK) fatal("afv_table_triangulate", rc, ctx);
+        return r;
+    }
+
+    // the loop as the reference runs it: one neighbour at a time (one afv_table_match_triangulation and one afv_table_triangulate each);
+    // between neighbours the features of `cur` and of that neighbour that received a point are marked in has_mp (one mask of cap bytes per
+    // slot, UPDATED in place).  neighbours: the slots that survived the caller's baseline tests (:272-289); jobs[k] / tri[k] belong to
+    // neighbour k (tri[k].has_mp1 / has_mp2 are set here).  Batching every neighbour into one Triangulate call is possible; a stale mask
+    // then no longer gives the reference's answer (a feature may receive a point from several neighbours).
+    std::vector<Created> CreateNewMapPoints(DeviceMapPoints &points, int32_t cur, const std::vector<int32_t> &neighbours,
+                                            const std::vector<afv_tri_points_job> &jobs, std::vector<afv_table_tri_job> tri,
+                                            std::vector<std::vector<uint8_t>> &has_mp, int32_t first_id) {
+        std::vector<Created> out;
+        std::vector<int32_t> m((size_t)cap);
+        int32_t nid = first_id;
+        for (size_t k = 0; k < neighbours.size(); ++k) {
+            const int32_t nb = neighbours[k];
+            int32_t nm = 0;
+            tri[k].struct_size = (uint32_t)sizeof(afv_table_tri_job);
+            tri[k].has_mp1 = has_mp[(size_t)cur].data();
+            tri[k].has_mp2 = has_mp[(size_t)nb].data();
+            const int rc = afv_table_match_triangulation(table, &cur, &nb, &tri[k], 1, m.data(), &nm);
+            if (rc != AFV_OK) fatal("afv_table_match_triangulation", rc, ctx);
+            const Result r = Triangulate({cur}, {nb}, {jobs[k]}, m.data(), &points, nid);
+            for (int i = 0; i < cap; ++i)
+                if (r.new_id[(size_t)i] >= 0) {
+                    out.push_back(Created{r.new_id[(size_t)i], cur, i, nb, m[(size_t)i]});
+                    has_mp[(size_t)cur][(size_t)i] = 1;
+                    has_mp[(size_t)nb][(size_t)m[(size_t)i]] = 1;
+                    ++nid;
+                }
+        }
+        return out;
+    }
+
+  private:
+    afv_ctx *ctx;
+    afv_table *table;
+    int cap;
+};
+
 }  // namespace afv

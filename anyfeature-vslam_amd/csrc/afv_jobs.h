@@ -106,6 +106,9 @@ struct PromoteArgs {
     const int *f_seg_idx;   // may be null (no FeatureVector yet)
     uint4 *t_desc;
     float *t_angle, *t_x, *t_y, *t_sigma2, *t_ur;  // geometry planes may be null (table without geometry)
+    const float *f_size, *f_depth;  // keyPtsSize; mvDepth (null: the frame has none, the slot reads -1)
+    const afv_keypoint *f_kps;      // mvKeys: the distorted points
+    float *t_size, *t_depth, *t_xd, *t_yd;  // scale planes, may be null
     int *t_idx;             // may be null
     uint8_t *t_valid;       // may be null
     int *t_n;

@@ -158,6 +158,32 @@ extern "C" void afv_launch_points_move(const DevPointsMove *job, hipStream_t str
 extern "C" void afv_launch_points_rows(const DevPointPlanes *P, const int *ids, int n, uint8_t *packed, const uint8_t *table, int table_cap,
                                        const int *slot, const int *idx, int gather, hipStream_t stream);
 
+// ---- k_triangulate.hip: the match loop of LocalMapping::CreateNewMapPoints over table slots (host side: afv_triangulate.hip) ----
+#define AFV_TRI_T 256        // lanes per workgroup: one per feature of keyframe a
+struct DevTriPair {          // one (a, b) pair: the caller's record and where the planes of the two slots start
+    float R1[9], t1[3], O1[3], R2[9], t2[3], O2[3];
+    float fx1, fy1, cx1, cy1, invfx1, invfy1, fx2, fy2, cx2, cy2, invfx2, invfy2;
+    float mb1, mb2, mbf1, ratio_factor, max_size1;
+    int n1, n2;
+    const float *x1, *y1, *sigma2_1, *ur1, *size1, *depth1, *xd1, *yd1;
+    const float *x2, *y2, *sigma2_2, *ur2, *size2, *depth2, *xd2, *yd2;
+    const uint8_t *rows1;    // the descriptor rows of slot a
+};
+struct DevTriArgs {          // a kernel argument of both launches
+    const DevTriPair *pairs;
+    const int *match12;      // [npairs][cap]
+    int npairs, cap, nblk;   // nblk = workgroups per pair
+    uint8_t *status, *route; // [npairs][cap]
+    float *x3d;              // [npairs][cap][3]
+    int *blk_count;          // [npairs][nblk] accepted matches per workgroup (launch 1 writes, launch 2 reads)
+    int *new_id, *n_new;     // [npairs][cap], [npairs]
+    int *total;              // one int: accepted matches of the call
+    DevPointPlanes P;        // the store (has_points)
+    int has_points, first_id;
+};
+extern "C" void afv_launch_tri_points(const DevTriArgs *args, hipStream_t stream);
+extern "C" void afv_launch_tri_store(const DevTriArgs *args, hipStream_t stream);
+
 // ---- k_poseopt.hip: Optimizer::PoseOptimization on a resident frame (host side: afv_poseopt.hip) ----
 struct DevPoseOut {          // what the workgroup of a job leaves
     float R[9], t[3];
@@ -592,10 +618,12 @@ struct afv_table {
     int32_t *d_n = nullptr;     // [nsets]
     int32_t *d_idx = nullptr;   // [nsets][cap] FeatureVector feature indices in node order (afv_table_set_featvec), lazily allocated
     float *d_geo = nullptr;     // [4][nsets][cap]: x, y, sigma2, mvuRight (afv_table_set_geometry / _u_right; -1 = monocular), lazily allocated
+    float *d_scale = nullptr;   // [4][nsets][cap]: keyPtsSize, mvDepth (-1 = none), distorted mvKeys x, y (afv_table_set_scale), lazily allocated
     uint8_t *d_valid = nullptr; // [nsets][cap] "map point exists && !isBad()" (afv_table_set_valid), lazily allocated, default 1
     std::vector<int32_t> h_n;
     std::vector<HostFeatVec> fv;
     std::vector<uint8_t> has_fv, has_geo;  // per set: afv_table_set_featvec / afv_table_set_geometry called since the last afv_table_set
+    std::vector<uint8_t> has_scale;        // per set: afv_table_set_scale called (or a frame promoted) since the last afv_table_set
     std::vector<uint8_t> fv_body_on_device;  // per set: the FeatureVector body came from a frame (afv_table_set_from_frame): no host copy yet
     // BowVector planes (afv_table_set_bowvec / afv_table_set_from_frame), lazily allocated together
     int32_t *d_bow_word = nullptr;  // [nsets][cap] word ids ascending

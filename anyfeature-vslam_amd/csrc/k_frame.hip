@@ -391,7 +391,7 @@ extern "C" void afv_launch_featvec_build(const int *leaf, const int *nid, const 
 
 // ---------------- k_table_promote ----------------
 // the frame's arrays into slot `set` of the table planes (descriptors as rows of Q x 16 bytes = the frame's zero-padded rows, angle,
-// x / y / sigma2 / mvuRight, FeatureVector body, validity = 1, count): one launch instead of nine small copies
+// x / y / sigma2 / mvuRight, keyPtsSize / mvDepth / the distorted mvKeys, FeatureVector body, validity = 1, count): one launch instead of nine small copies
 // Q = 0: `quads` at run time (a float row: float_dim / 4)
 template <int Q>
 __global__ __launch_bounds__(256) void k_table_promote(PromoteArgs A, int quads) {
@@ -404,6 +404,12 @@ __global__ __launch_bounds__(256) void k_table_promote(PromoteArgs A, int quads)
             A.t_y[t] = A.f_y[t];
             A.t_sigma2[t] = A.f_sigma2[t];
             A.t_ur[t] = A.f_ur[t];
+        }
+        if (A.t_size) {
+            A.t_size[t] = A.f_size[t];
+            A.t_depth[t] = A.f_depth ? A.f_depth[t] : -1.0f;
+            A.t_xd[t] = A.f_kps[t].x;
+            A.t_yd[t] = A.f_kps[t].y;
         }
     }
     if (A.t_idx && A.f_seg_idx && t < A.nkept) A.t_idx[t] = A.f_seg_idx[t];

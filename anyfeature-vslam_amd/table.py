@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import TableTriJob, ptr
+from ._lib import TableTriJob, TriPointsJob, ptr
 
 
 def _i32(a):
@@ -154,6 +154,12 @@ class DescriptorTable:
         if u_right is not None:
             u = np.ascontiguousarray(u_right, np.float32)
             self.ctx.check(self.lib.afv_table_set_u_right(self.handle, int(slot), ptr(u)), "afv_table_set_u_right")
+
+    def set_scale(self, slot, size, depth=None, x_dist=None, y_dist=None):
+        """KeyFrame::GetKeyPtSize, mvDepth and the distorted mvKeys of a slot, after set_geometry: what triangulate reads next to the
+        geometry.  depth None: -1 everywhere (monocular); x_dist / y_dist None (both or neither): the undistorted points"""
+        a = [None if v is None else np.ascontiguousarray(v, np.float32) for v in (size, depth, x_dist, y_dist)]
+        self.ctx.check(self.lib.afv_table_set_scale(self.handle, int(slot), *[ptr(v) for v in a]), "afv_table_set_scale")
 
     def set_valid(self, slot, valid):
         """valid[i] = feature i has a good map point (None = all valid); honoured by match_bow"""
@@ -353,3 +359,71 @@ class DescriptorTable:
         self.ctx.check(self.lib.afv_table_match_triangulation(self.handle, ptr(pa), ptr(pb), jobs, n, ptr(m), ptr(nm)),
                        "afv_table_match_triangulation")
         return m, nm
+
+    # ---- new map points ----
+    @staticmethod
+    def tri_points_jobs(cams_a, cams_b, ratio_factor, max_size1):
+        """afv_tri_points_job records from per-pair camera dicts {Rcw, tcw, Ow, fx, fy, cx, cy, invfx, invfy, mb, mbf} (a = the current
+        keyframe, b = the neighbour); ratio_factor = 1.5f * sizeTolerance, max_size1 = maxKeyPtSize of a: scalars or one per pair"""
+        n = len(cams_a)
+        rf = np.broadcast_to(np.asarray(ratio_factor, np.float32), (n,))
+        ms = np.broadcast_to(np.asarray(max_size1, np.float32), (n,))
+        jobs = (TriPointsJob * n)()
+        for p, (a, b) in enumerate(zip(cams_a, cams_b)):
+            j = jobs[p]
+            j.struct_size = C.sizeof(TriPointsJob)
+            for side, cam in (("1", a), ("2", b)):
+                for name, key, cnt in (("Rcw", "Rcw", 9), ("tcw", "tcw", 3), ("Ow", "Ow", 3)):
+                    v = np.asarray(cam[key], np.float32).reshape(cnt)
+                    dst = getattr(j, name + side)
+                    for k in range(cnt):
+                        dst[k] = float(v[k])
+                for key in ("fx", "fy", "cx", "cy", "invfx", "invfy"):
+                    setattr(j, key + side, float(np.float32(cam[key])))
+            j.mb1, j.mb2, j.mbf1 = float(np.float32(a["mb"])), float(np.float32(b["mb"])), float(np.float32(a["mbf"]))
+            j.ratio_factor, j.max_size1 = float(rf[p]), float(ms[p])
+        return jobs
+
+    def triangulate(self, pair_a, pair_b, jobs, match12, points=None, first_id=0):
+        """the match loop of CreateNewMapPoints (LocalMapping.cc:315-461) for every pair in one call: two launches, one wait.  jobs: a
+        TriPointsJob array (tri_points_jobs); match12 [npairs, cap] as match_triangulation returns it; points: a MapPoints store that
+        receives the new points from id first_id on, or None.  Returns status, route [npairs, cap] uint8 (_lib.TRI_STATUS / TRI_ROUTE),
+        x3d [npairs, cap, 3], new_id [npairs, cap] (-1 = not accepted), n_new [npairs]"""
+        pa, pb = _i32(pair_a), _i32(pair_b)
+        n = len(pa)
+        m = _i32(match12)
+        if len(pb) != n or len(jobs) != n or m.shape != (n, self.cap):
+            raise ValueError("DescriptorTable.triangulate: %d pairs need %d jobs and match12 of shape (%d, %d)" % (n, n, n, self.cap))
+        status, route = np.zeros((n, self.cap), np.uint8), np.zeros((n, self.cap), np.uint8)
+        x3d = np.zeros((n, self.cap, 3), np.float32)
+        new_id, n_new = np.full((n, self.cap), -1, np.int32), np.zeros(n, np.int32)
+        self.ctx.check(self.lib.afv_table_triangulate(self.handle, ptr(pa), ptr(pb), jobs, n, ptr(m), None if points is None else points.handle,
+                                                      int(first_id), ptr(status), ptr(route), ptr(x3d), ptr(new_id), ptr(n_new)),
+                       "afv_table_triangulate")
+        return status, route, x3d, new_id, n_new
+
+    def CreateNewMapPoints(self, points, cur, neighbours, cams, F12, epipoles, th_low, has_mp, first_id, only_stereo=False):
+        """the neighbour loop of LocalMapping::CreateNewMapPoints (LocalMapping.cc:265-472) as the reference runs it: one neighbour at a
+        time, each with one match_triangulation call and one triangulate call; between neighbours the features of `cur` and of that
+        neighbour that received a point are marked in the host masks, so a feature of `cur` gets at most one point.
+        cur: the slot of the current keyframe; neighbours: the slots that survived the caller's baseline tests (:272-289), in order;
+        cams: {slot: camera dict as tri_points_jobs takes it, plus "ratio_factor" and "max_size" for cur's}; F12 [nn, 9], epipoles [nn, 2]
+        per neighbour; has_mp: {slot: uint8 mask "already has a map point"} - the masks are UPDATED in place.
+        Returns a list of (id, [(slot, feature), (slot, feature)]) observations in creation order.
+        All neighbours can be batched into ONE triangulate call (it takes up to 64 pairs); the masks are then those of before the first
+        neighbour, and a stale mask no longer gives the reference's answer: a feature may receive a point from several neighbours."""
+        F12 = np.ascontiguousarray(F12, np.float32).reshape(len(neighbours), 9)
+        ep = np.ascontiguousarray(epipoles, np.float32).reshape(len(neighbours), 2)
+        out = []
+        nid = int(first_id)
+        for k, nb in enumerate(neighbours):
+            m, _ = self.match_triangulation([cur], [nb], F12[k:k + 1], ep[k:k + 1], th_low, [has_mp[cur]], [has_mp[nb]], only_stereo)
+            jobs = self.tri_points_jobs([cams[cur]], [cams[nb]], cams[cur]["ratio_factor"], cams[cur]["max_size"])
+            _, _, _, new_id, _ = self.triangulate([cur], [nb], jobs, m, points, nid)
+            for i in np.nonzero(new_id[0] >= 0)[0]:
+                j = int(m[0, i])
+                out.append((int(new_id[0, i]), [(int(cur), int(i)), (int(nb), j)]))
+                has_mp[cur][i] = 1
+                has_mp[nb][j] = 1
+                nid += 1
+        return out

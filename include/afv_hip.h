@@ -741,6 +741,58 @@ int afv_frame_pose_optimize(afv_frame *f, afv_points *points, const afv_pose_job
 #define AFV_POSE_MAX_JOBS 64
 #define AFV_POSE_MAX_FEATURES 8192 /* features of the frame a call takes (eight per thread of the workgroup); more: AFV_EINVAL */
 
+/* ---- new map points: the match loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:315-461) over slots of the keyframe table.
+ * It is what LocalMapping does with the answer of afv_table_match_triangulation: per match the parallax test, the linear triangulation
+ * through a 4 x 4 SVD or a stereo unprojection, the two depth tests, the two reprojection gates, the scale-consistency test and the creation
+ * of the map point.  One lane per (pair, feature i of keyframe a); TWO launches per call whatever the number of pairs, ONE wait
+ * (csrc/k_triangulate.hip).  The normative semantics are tests/_tri_ref.py; the device is held to it bit for bit.  Float arithmetic, one
+ * rounding per operator, three-term sums as a0 + (a1 + a2); `> 5.991 * sigmaSquare`, `> 7.8 * sigmaSquare` and `cosParallaxRays < 0.9998`
+ * are evaluated in double as the reference does.  The SVD restates OpenCV 4.x's JacobiSVDImpl_<float> (one-sided Jacobi on the transposed
+ * matrix, double accumulators, at most 30 sweeps, |p| <= eps * sqrt(a * b), descending sort) - parity unpinned, as is the whole routine.
+ * Quirks restated as written: the stereo gate of the second keyframe uses the current keyframe's mbf (:438); KeyFrame::UnprojectStereo
+ * reads the distorted keypoint (KeyFrame.cc:664-665).
+ * Deliberate deviations:
+ *   T1  cos(2 * atan2(mb / 2, depth)) is (d * d - h * h) / (d * d + h * h) in float, h = mb / 2; no library cos / atan2 is called
+ *   T2  the Jacobi rotation's hypot(p, beta) is sqrt(p * p + beta * beta) in double, correctly rounded
+ *   T3  a match whose x3D has a component that is not finite is rejected (the reference: every comparison against a NaN is false, the
+ *       point would pass all gates and enter the map)
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+/* The planes the routine reads per feature next to afv_table_set_geometry's: KeyFrame::GetKeyPtSize(i), mvDepth[i] and the distorted
+ * mvKeys[i].pt.  Called after afv_table_set_geometry of the same slot (else AFV_EINVAL), which it does not replace.  depth NULL: -1
+ * everywhere; x_dist and y_dist NULL (both or neither): the undistorted points.  afv_table_set forgets them as it forgets the geometry;
+ * afv_table_set_from_frame brings the frame's along (depth -1 for a frame without stereo / RGB-D data); afv_table_clone /
+ * afv_table_broadcast ship them. */
+int afv_table_set_scale(afv_table *t, int set, const float *size, const float *depth, const float *x_dist, const float *y_dist);
+typedef struct {
+    uint32_t struct_size;                                            /* sizeof(afv_tri_points_job) */
+    float Rcw1[9], tcw1[3], Ow1[3], Rcw2[9], tcw2[3], Ow2[3];        /* row-major; Ow as the host computes GetCameraCenter */
+    float fx1, fy1, cx1, cy1, invfx1, invfy1, fx2, fy2, cx2, cy2, invfx2, invfy2;
+    float mb1, mb2, mbf1;                                            /* KeyFrame::mb of a and b, mbf of a (:412, :438) */
+    float ratio_factor;                                              /* 1.5f * sizeTolerance (:260) */
+    float max_size1;                                                 /* KeyFrame::maxKeyPtSize of a */
+} afv_tri_points_job;
+#define AFV_TRI_MAX_PAIRS 64
+enum { AFV_TRI_NO_MATCH = 0, AFV_TRI_ACCEPTED = 1, AFV_TRI_LOW_PARALLAX = 2 /* the `else continue` at :381 */, AFV_TRI_W_ZERO = 3,
+       AFV_TRI_Z1 = 4, AFV_TRI_Z2 = 5, AFV_TRI_REPROJ1 = 6, AFV_TRI_REPROJ2 = 7, AFV_TRI_ZERO_DIST = 8, AFV_TRI_SCALE_RATIO = 9,
+       AFV_TRI_NOT_FINITE = 10 /* T3 */ };
+enum { AFV_TRI_ROUTE_TRIANGULATED = 0, AFV_TRI_ROUTE_UNPROJECT_A = 1, AFV_TRI_ROUTE_UNPROJECT_B = 2 };
+/* npairs 1 .. AFV_TRI_MAX_PAIRS pairs (a = the current keyframe, b = a neighbour), independent of each other; match12[npairs][cap] as
+ * afv_table_match_triangulation returns it (feature of b per feature of a, -1 = none).  Host outputs, any may be NULL: status / route
+ * [npairs][cap] (AFV_TRI_*), x3d [npairs][cap][3] (zeros where none was made: no match, low parallax, w == 0), new_id [npairs][cap] (-1 =
+ * not accepted), n_new[npairs].  Accepted matches get the dense ids first_id + rank, the rank counted in pair order and within a pair by
+ * ascending feature of a: the order in which the reference creates them.  With a store (`points`, may be NULL) each new id receives what
+ * MapPoint::MapPoint + UpdateNormalAndDepth (MapPoint.cc:372-418) hold for a point with exactly these two observations and a as reference:
+ * pos = x3D, normal = (n1 / |n1| + n2 / |n2|) / 2, ref_distance = |x3D - Ow1|, ref_size = size1[i], ref_sigma = sqrtf(sigma2_1[i]),
+ * max_distance = ref_distance * ref_size, min_distance = max_distance / max_size1, flags set | observed (not bad), and row i of keyframe a
+ * as descriptor, copied device to device (the semantics of afv_points_set_descriptors_from_table; afv_distinctive_descriptors recomputes
+ * it later).  first_id + the number of new points beyond the store's capacity: AFV_ECAPACITY, the store and the output arrays untouched.
+ * Before anything runs: a store of another kind or width than the table AFV_EUNSUPPORTED; AFV_EINVAL for NULL t / pair_a / pair_b / jobs /
+ * match12, npairs out of range, first_id < 0, a slot out of range, a slot that holds features but lacks its geometry or its scale planes,
+ * an unknown struct_size, a store of another context, a match12 entry outside [-1, n_b) or a match at a feature i >= n_a. */
+int afv_table_triangulate(afv_table *t, const int32_t *pair_a, const int32_t *pair_b, const afv_tri_points_job *jobs, int npairs,
+                          const int32_t *match12, afv_points *points, int32_t first_id, uint8_t *status, uint8_t *route, float *x3d,
+                          int32_t *new_id, int32_t *n_new);
+
 /* engine of the ordered phase of the projection searches / SearchForInitialization (identical results):
  *   1: one fixed point over all live queries of a job on a 1024-thread workgroup (round 5)   0: the ordered walk of rounds 1-4 on one
  *   wavefront   2 (default): 1 whenever the job's tables fit the workgroup's LDS, else 0   3: as 1, but ranking and ordered phase as two
