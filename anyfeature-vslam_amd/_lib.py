@@ -272,6 +272,8 @@ SYMBOLS = {
     "afv_frame_pose_optimize": (_i, [_vp, _vp, C.POINTER(PoseJob), _i, C.POINTER(PoseResult)]),
     "afv_table_set_scale": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "afv_table_triangulate": (_i, [_vp, _vp, _vp, C.POINTER(TriPointsJob), _i, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "afv_table_create_new_points": (_i, [_vp, C.c_int32, _vp, _i, C.POINTER(TableTriJob), C.POINTER(TriPointsJob), _vp, _vp, _vp, C.c_int32,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_vocab_set_weights": (_i, [_vp, _vp, _vp, _vp]),
     "afv_bow_vector": (_i, [_vp, _vp, _vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_frame_get_bowvec": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),

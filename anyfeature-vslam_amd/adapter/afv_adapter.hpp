@@ -1180,6 +1180,36 @@ class NewMapPoints {
         return out;
     }
 
+    // the same loop with the same arguments and the same result from ONE afv_table_create_new_points call: one upload, two launches per
+    // neighbour, one wait; the masks stay on the device between the neighbours and come back updated.  A store that cannot take the
+    // points of a neighbour is fatal here as it is in the loop above (afv_table_create_new_points itself reports how far it came)
+    std::vector<Created> CreateNewMapPointsChain(DeviceMapPoints &points, int32_t cur, const std::vector<int32_t> &neighbours,
+                                                 std::vector<afv_tri_points_job> jobs, std::vector<afv_table_tri_job> tri,
+                                                 std::vector<std::vector<uint8_t>> &has_mp, int32_t first_id) {
+        const size_t nn = neighbours.size(), cells = nn * (size_t)cap;
+        std::vector<uint8_t> nb_masks(cells);
+        for (size_t k = 0; k < nn; ++k) {
+            tri[k].struct_size = (uint32_t)sizeof(afv_table_tri_job);
+            tri[k].has_mp1 = tri[k].has_mp2 = nullptr;
+            jobs[k].struct_size = (uint32_t)sizeof(afv_tri_points_job);
+            std::memcpy(nb_masks.data() + k * (size_t)cap, has_mp[(size_t)neighbours[k]].data(), (size_t)cap);
+        }
+        std::vector<int32_t> m(cells), new_id(cells), n_new(nn);
+        int32_t n_done = 0;
+        const int rc = afv_table_create_new_points(table, cur, neighbours.data(), (int)nn, tri.data(), jobs.data(), has_mp[(size_t)cur].data(),
+                                                   nb_masks.data(), points.handle(), first_id, m.data(), nullptr, nullptr, nullptr, new_id.data(),
+                                                   n_new.data(), &n_done);
+        if (rc != AFV_OK) fatal("afv_table_create_new_points", rc, ctx);
+        std::vector<Created> out;
+        for (size_t k = 0; k < nn; ++k) {
+            const size_t o = k * (size_t)cap;
+            for (int i = 0; i < cap; ++i)
+                if (new_id[o + (size_t)i] >= 0) out.push_back(Created{new_id[o + (size_t)i], cur, i, neighbours[k], m[o + (size_t)i]});
+            std::memcpy(has_mp[(size_t)neighbours[k]].data(), nb_masks.data() + o, (size_t)cap);
+        }
+        return out;
+    }
+
   private:
     afv_ctx *ctx;
     afv_table *table;

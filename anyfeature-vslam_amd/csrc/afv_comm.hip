@@ -502,7 +502,7 @@ extern "C" int afv_table_match_pairs(afv_table *t, const int32_t *pair_a, const 
 // the table; per call only the merge-joined segment lists (host work, FeatureMatcher.cc:205-276) are uploaded.  The routes below check
 // their arguments and describe the sides; afv_match_jobs.hip stages and launches ----
 // a slot as one side of a job: everything but the FeatureVector's node structure is on the device
-static MatchSide table_side(const afv_table *t, int slot) {
+AFV_LOCAL MatchSide table_side(const afv_table *t, int slot) {
     const size_t row0 = (size_t)slot * t->cap, plane = (size_t)t->nsets * t->cap;
     const HostFeatVec &fv = t->fv[slot];
     MatchSide s;
@@ -523,7 +523,7 @@ static MatchSide table_side(const afv_table *t, int slot) {
 }
 
 // "no shared node" must not be confused with "FeatureVector never stored" (or, for triangulation, geometry never stored)
-static int check_slot_ready(const afv_table *t, int s, bool need_geo, const char *who) {
+AFV_LOCAL int check_slot_ready(const afv_table *t, int s, bool need_geo, const char *who) {
     if (t->h_n[s] > 0 && (!t->has_fv[s] || (need_geo && !t->has_geo[s]))) {
         t->c->last_error = std::string(who) + ": set " + std::to_string(s) + (need_geo ? " lacks its FeatureVector or geometry"
                                                                                         : " holds features but no FeatureVector (afv_table_set_featvec)");
@@ -769,7 +769,7 @@ extern "C" int afv_table_set_from_frame(afv_table *t, int slot, afv_frame *f) {
 }
 
 // host copy of a slot's FeatureVector body when it was promoted from a frame (device to device): fetched once, on first need
-static int table_fetch_fv_body(afv_table *t, int slot) {
+AFV_LOCAL int table_fetch_fv_body(afv_table *t, int slot) {
     if (!t->fv_body_on_device[slot]) return AFV_OK;
     afv_ctx *c = t->c;
     HostFeatVec &f = t->fv[slot];

@@ -31,7 +31,7 @@ int afv_featvec_check(const int32_t *node_id, const int32_t *seg_ptr, const int3
 }
 
 // merge-join of two FeatureVectors (FeatureMatcher.cc:205-276): appends one (range1, range2) per shared node id
-static void join_featvecs(const MatchSide &A, const MatchSide &B, bool whole_range, std::vector<Seg> &segs) {
+AFV_LOCAL void join_featvecs(const MatchSide &A, const MatchSide &B, bool whole_range, std::vector<Seg> &segs) {
     if (whole_range && (A.nnodes == 0 || B.nnodes == 0)) {
         segs.push_back(Seg{0, A.n, 0, B.n});
         return;
@@ -54,7 +54,7 @@ static void join_featvecs(const MatchSide &A, const MatchSide &B, bool whole_ran
 // [0, n1) is AFV_EINVAL.  Host-array jobs cannot get there: afv_featvec_check has seen every index of seg_idx[0 .. seg_ptr[nnodes]), the
 // segments are sub-ranges of it, and the whole-range segment of a brute-force job names 0 .. n1 - 1; a table slot cannot either while
 // afv_table_sync_counts drops the FeatureVector of a slot that shrank under it
-static int build_row_seg(const MatchSide &A, const Seg *segs, int nseg, std::vector<int> &row_seg) {
+AFV_LOCAL int build_row_seg(const MatchSide &A, const Seg *segs, int nseg, std::vector<int> &row_seg) {
     const int32_t *idx = A.on_device ? A.idx_host : A.idx;
     row_seg.assign((size_t)std::max(A.n, 1), -1);
     for (int s = 0; s < nseg; ++s)

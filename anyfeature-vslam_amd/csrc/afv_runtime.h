@@ -184,6 +184,27 @@ struct DevTriArgs {          // a kernel argument of both launches
 extern "C" void afv_launch_tri_points(const DevTriArgs *args, hipStream_t stream);
 extern "C" void afv_launch_tri_store(const DevTriArgs *args, hipStream_t stream);
 
+// ---- k_newpoints.hip: the neighbour loop of CreateNewMapPoints as a chain of launches (host side: afv_newpoints.hip) ----
+struct DevNewPtsArgs {       // a kernel argument of both launches of every neighbour; the neighbour index is the second argument
+    const DevTriJob *search; // [nn] the search of neighbour k: valid1 = mask_cur, valid2 = row k of mask_nb
+    const DevTriPair *pairs; // [nn] a = the current keyframe, b = neighbour k
+    int nn, cap, nblk;       // nblk = workgroups per launch
+    uint8_t *mask_cur;       // [cap] "already has a map point" of the current keyframe: the store launch of neighbour k writes, the judge
+                             // launch of neighbour k + 1 reads
+    uint8_t *mask_nb;        // [nn][cap] the neighbours' masks
+    int *match12;            // [nn][cap]
+    uint8_t *status, *route; // [nn][cap]
+    float *x3d;              // [nn][cap][3]
+    int *new_id, *n_new;     // [nn][cap], [nn]
+    int *blk_count;          // [nn][nblk] accepted matches per workgroup (the judge launch writes, the store launch reads)
+    int *next_id;            // [nn + 1] the id base of neighbour k: launch k reads cell k, one thread of it writes cell k + 1
+    int *stop;               // [nn + 1] the capacity rule: set from the first neighbour on whose points do not fit the store
+    DevPointPlanes P;        // the store (has_points)
+    int has_points;
+};
+extern "C" void afv_launch_newpts_judge(const DevNewPtsArgs *args, int k, hipStream_t stream);
+extern "C" void afv_launch_newpts_store(const DevNewPtsArgs *args, int k, hipStream_t stream);
+
 // ---- k_poseopt.hip: Optimizer::PoseOptimization on a resident frame (host side: afv_poseopt.hip) ----
 struct DevPoseOut {          // what the workgroup of a job leaves
     float R[9], t[3];
@@ -686,6 +707,17 @@ struct MatchBatch {
 };
 // out may be null (counts only); rows start at -1, nmatches[njobs]
 int afv_match_jobs_run(afv_ctx *c, const MatchBatch &B, int32_t *out, int32_t *nmatches);
+// the pieces of the table routes that afv_newpoints.hip stages itself (its launches are not those of afv_match_jobs_run):
+// afv_match_jobs.hip - the merge-join of two FeatureVectors and the feature -> shared node map of side 1;
+// afv_comm.hip - a slot as a side, "the slot holds what the call needs", the host copy of a promoted slot's FeatureVector body;
+// afv_triangulate.hip - the slot check of afv_table_triangulate and the device record of a pair
+AFV_LOCAL void join_featvecs(const MatchSide &A, const MatchSide &B, bool whole_range, std::vector<Seg> &segs);
+AFV_LOCAL int build_row_seg(const MatchSide &A, const Seg *segs, int nseg, std::vector<int> &row_seg);
+AFV_LOCAL MatchSide table_side(const afv_table *t, int slot);
+AFV_LOCAL int check_slot_ready(const afv_table *t, int s, bool need_geo, const char *who);
+AFV_LOCAL int table_fetch_fv_body(afv_table *t, int slot);
+AFV_LOCAL int tri_check_slot(const afv_table *t, int s);
+AFV_LOCAL void tri_fill_pair(const afv_table *t, int a, int b, const afv_tri_points_job &j, DevTriPair &D);
 // plain brute-force KF-KF jobs over 32-byte rows take the two-phase pair matcher (top-k + resolve over a table of two sets per job);
 // *taken = false: the batch is not of that kind, nothing was done
 int afv_match_bow_plain32(afv_ctx *c, const afv_match_job *jobs, int njobs, int32_t *out, int32_t *nmatches, bool *taken);

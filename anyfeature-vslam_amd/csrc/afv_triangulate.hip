@@ -6,7 +6,7 @@
 // accepted ones and writes the new points into the resident store.
 #include "afv_runtime.h"
 
-static int tri_check_slot(const afv_table *t, int s) {
+AFV_LOCAL int tri_check_slot(const afv_table *t, int s) {
     if (t->h_n[s] > 0 && (!t->has_geo[s] || !t->has_scale[s])) {
         t->c->last_error = "afv_table_triangulate: set " + std::to_string(s) + " lacks its geometry (afv_table_set_geometry) or its scale planes (afv_table_set_scale)";
         return AFV_EINVAL;
@@ -20,6 +20,28 @@ static void tri_side(const afv_table *t, int slot, const float **geo4, const flo
         geo4[k] = t->d_geo + k * plane + row0;
         scale4[k] = t->d_scale + k * plane + row0;
     }
+}
+
+// the device record of one (a, b) pair: the caller's job and where the planes of the two slots start
+AFV_LOCAL void tri_fill_pair(const afv_table *t, int a, int b, const afv_tri_points_job &j, DevTriPair &D) {
+    const int cap = t->cap;
+    D = DevTriPair{};
+    std::memcpy(D.R1, j.Rcw1, sizeof(D.R1)); std::memcpy(D.t1, j.tcw1, sizeof(D.t1)); std::memcpy(D.O1, j.Ow1, sizeof(D.O1));
+    std::memcpy(D.R2, j.Rcw2, sizeof(D.R2)); std::memcpy(D.t2, j.tcw2, sizeof(D.t2)); std::memcpy(D.O2, j.Ow2, sizeof(D.O2));
+    D.fx1 = j.fx1; D.fy1 = j.fy1; D.cx1 = j.cx1; D.cy1 = j.cy1; D.invfx1 = j.invfx1; D.invfy1 = j.invfy1;
+    D.fx2 = j.fx2; D.fy2 = j.fy2; D.cx2 = j.cx2; D.cy2 = j.cy2; D.invfx2 = j.invfx2; D.invfy2 = j.invfy2;
+    D.mb1 = j.mb1; D.mb2 = j.mb2; D.mbf1 = j.mbf1; D.ratio_factor = j.ratio_factor; D.max_size1 = j.max_size1;
+    D.n1 = t->h_n[a]; D.n2 = t->h_n[b];
+    if (t->d_geo && t->d_scale) {
+        const float *g[4], *s[4];
+        tri_side(t, a, g, s);
+        D.x1 = g[0]; D.y1 = g[1]; D.sigma2_1 = g[2]; D.ur1 = g[3]; D.size1 = s[0]; D.depth1 = s[1]; D.xd1 = s[2]; D.yd1 = s[3];
+        tri_side(t, b, g, s);
+        D.x2 = g[0]; D.y2 = g[1]; D.sigma2_2 = g[2]; D.ur2 = g[3]; D.size2 = s[0]; D.depth2 = s[1]; D.xd2 = s[2]; D.yd2 = s[3];
+    } else {
+        D.n1 = D.n2 = 0;
+    }
+    D.rows1 = t->d_desc + (size_t)a * cap * t->words * 4;
 }
 
 static int triangulate_impl(afv_table *t, const int32_t *pair_a, const int32_t *pair_b, const afv_tri_points_job *caller_jobs, int npairs,
@@ -46,25 +68,7 @@ static int triangulate_impl(afv_table *t, const int32_t *pair_a, const int32_t *
     const size_t cells = (size_t)npairs * cap;
     std::vector<DevTriPair> dp((size_t)npairs);
     for (int p = 0; p < npairs; ++p) {
-        const afv_tri_points_job &j = jobs[(size_t)p];
-        DevTriPair &D = dp[(size_t)p];
-        D = DevTriPair{};
-        std::memcpy(D.R1, j.Rcw1, sizeof(D.R1)); std::memcpy(D.t1, j.tcw1, sizeof(D.t1)); std::memcpy(D.O1, j.Ow1, sizeof(D.O1));
-        std::memcpy(D.R2, j.Rcw2, sizeof(D.R2)); std::memcpy(D.t2, j.tcw2, sizeof(D.t2)); std::memcpy(D.O2, j.Ow2, sizeof(D.O2));
-        D.fx1 = j.fx1; D.fy1 = j.fy1; D.cx1 = j.cx1; D.cy1 = j.cy1; D.invfx1 = j.invfx1; D.invfy1 = j.invfy1;
-        D.fx2 = j.fx2; D.fy2 = j.fy2; D.cx2 = j.cx2; D.cy2 = j.cy2; D.invfx2 = j.invfx2; D.invfy2 = j.invfy2;
-        D.mb1 = j.mb1; D.mb2 = j.mb2; D.mbf1 = j.mbf1; D.ratio_factor = j.ratio_factor; D.max_size1 = j.max_size1;
-        D.n1 = t->h_n[pair_a[p]]; D.n2 = t->h_n[pair_b[p]];
-        if (t->d_geo && t->d_scale) {
-            const float *g[4], *s[4];
-            tri_side(t, pair_a[p], g, s);
-            D.x1 = g[0]; D.y1 = g[1]; D.sigma2_1 = g[2]; D.ur1 = g[3]; D.size1 = s[0]; D.depth1 = s[1]; D.xd1 = s[2]; D.yd1 = s[3];
-            tri_side(t, pair_b[p], g, s);
-            D.x2 = g[0]; D.y2 = g[1]; D.sigma2_2 = g[2]; D.ur2 = g[3]; D.size2 = s[0]; D.depth2 = s[1]; D.xd2 = s[2]; D.yd2 = s[3];
-        } else {
-            D.n1 = D.n2 = 0;
-        }
-        D.rows1 = t->d_desc + (size_t)pair_a[p] * cap * t->words * 4;
+        tri_fill_pair(t, pair_a[p], pair_b[p], jobs[(size_t)p], dp[(size_t)p]);
     }
     Blob b(c);
     const size_t o_pairs = b.put(dp.data(), dp.size() * sizeof(DevTriPair));

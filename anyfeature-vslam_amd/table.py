@@ -427,3 +427,64 @@ class DescriptorTable:
                 has_mp[nb][j] = 1
                 nid += 1
         return out
+
+    def create_new_points(self, cur, neighbours, F12, epipoles, th_low, jobs, has_mp_cur, has_mp_nb, points=None, first_id=0, only_stereo=False):
+        """the neighbour loop of CreateNewMapPoints in ONE call (afv_table_create_new_points): one upload, two launches per neighbour on the
+        context's stream, one wait; the masks stay on the device between the neighbours.  F12 [nn, 9], epipoles [nn, 2]; jobs: a
+        TriPointsJob array (tri_points_jobs, a = cur, b = neighbours[k]); has_mp_cur uint8 [cap] and has_mp_nb uint8 [nn, cap] (row k: the
+        mask of neighbours[k]) are C-contiguous arrays UPDATED in place.
+        Returns match12, status, route [nn, cap], x3d [nn, cap, 3], new_id [nn, cap], n_new [nn], n_done.  n_done < nn: the points of
+        neighbour n_done did not fit the store (AFV_ECAPACITY): the neighbours before it stand, its rows and the later ones are empty -
+        this is an answer, not an exception; every other error raises"""
+        from ._lib import ECAPACITY
+        nbs = _i32(neighbours)
+        n = len(nbs)
+        F12 = np.ascontiguousarray(F12, np.float32).reshape(n, 9)
+        ep = np.ascontiguousarray(epipoles, np.float32).reshape(n, 2)
+        for name, a, shape in (("has_mp_cur", has_mp_cur, (self.cap,)), ("has_mp_nb", has_mp_nb, (n, self.cap))):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.shape == shape and a.flags.c_contiguous and a.flags.writeable):
+                raise ValueError("DescriptorTable.create_new_points: %s must be a writeable C-contiguous uint8 array of shape %s" % (name, shape))
+        if len(jobs) != n:
+            raise ValueError("DescriptorTable.create_new_points: %d neighbours need %d jobs" % (n, n))
+        search = (TableTriJob * max(n, 1))()
+        for k in range(n):
+            j = search[k]
+            j.struct_size = C.sizeof(TableTriJob)
+            for q in range(9):
+                j.F12[q] = float(F12[k, q])
+            j.ex, j.ey, j.th_low = float(ep[k, 0]), float(ep[k, 1]), float(th_low)
+            j.only_stereo = int(bool(only_stereo))
+        m = np.full((n, self.cap), -1, np.int32)
+        status, route = np.zeros((n, self.cap), np.uint8), np.zeros((n, self.cap), np.uint8)
+        x3d = np.zeros((n, self.cap, 3), np.float32)
+        new_id, n_new = np.full((n, self.cap), -1, np.int32), np.zeros(n, np.int32)
+        n_done = C.c_int32(0)
+        rc = self.lib.afv_table_create_new_points(self.handle, int(cur), ptr(nbs), n, search, jobs, ptr(has_mp_cur), ptr(has_mp_nb),
+                                                  None if points is None else points.handle, int(first_id), ptr(m), ptr(status), ptr(route),
+                                                  ptr(x3d), ptr(new_id), ptr(n_new), C.byref(n_done))
+        if rc != ECAPACITY:
+            self.ctx.check(rc, "afv_table_create_new_points")
+        return m, status, route, x3d, new_id, n_new, int(n_done.value)
+
+    def CreateNewMapPointsChain(self, points, cur, neighbours, cams, F12, epipoles, th_low, has_mp, first_id, only_stereo=False):
+        """CreateNewMapPoints with the same arguments, the same observation list and the same in-place update of the masks, from ONE
+        create_new_points call instead of two calls per neighbour.  A store that cannot take the points of neighbour k raises AfvError
+        (ECAPACITY) as the loop does at its k-th triangulate call; the masks then hold what neighbours 0 .. k - 1 marked"""
+        from ._lib import AfvError, ECAPACITY
+        nn = len(neighbours)
+        jobs = self.tri_points_jobs([cams[cur]] * nn, [cams[nb] for nb in neighbours], cams[cur]["ratio_factor"], cams[cur]["max_size"])
+        m_cur = np.zeros(self.cap, np.uint8)
+        m_nb = np.zeros((nn, self.cap), np.uint8)
+        m_cur[:len(has_mp[cur])] = has_mp[cur]
+        for k, nb in enumerate(neighbours):
+            m_nb[k, :len(has_mp[nb])] = has_mp[nb]
+        m, _, _, _, new_id, _, n_done = self.create_new_points(cur, neighbours, F12, epipoles, th_low, jobs, m_cur, m_nb, points, first_id, only_stereo)
+        out = []
+        for k, nb in enumerate(neighbours[:n_done]):
+            for i in np.nonzero(new_id[k] >= 0)[0]:
+                out.append((int(new_id[k, i]), [(int(cur), int(i)), (int(nb), int(m[k, i]))]))
+            has_mp[nb][:] = m_nb[k, :len(has_mp[nb])]
+        has_mp[cur][:] = m_cur[:len(has_mp[cur])]
+        if n_done < nn:
+            raise AfvError(ECAPACITY, "afv_table_create_new_points " + self.lib.afv_last_error(self.ctx.handle).decode())
+        return out

@@ -5,6 +5,8 @@ keyframe and 20 neighbours of 1000 features each, about 150 matches per neighbou
 Host-to-host times over --calls calls each, median and spread, one JSON line per figure:
 
   the CreateNewMapPoints loop of DescriptorTable (per neighbour one match_triangulation and one triangulate call, masks updated between)
+  the same loop in ONE call (CreateNewMapPointsChain: afv_table_create_new_points, the masks stay on the device between the neighbours);
+    its observation list and masks are compared with the loop's once
   the match_triangulation calls of that loop alone
   ONE batched triangulate call over all 20 pairs (the matches of one batched match_triangulation call, masks of before the first neighbour)
   the host program fed those matches; the upload of its points
@@ -14,7 +16,7 @@ The batched call's answers are compared with the host program's, bit for bit.
     python tools/time_triangulate.py [--calls 200]
 
 Kernel time: run it again under  rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/time_triangulate.py --calls 20
-(k_tri_points, k_tri_store)"""
+(k_tri_points, k_tri_store, k_match_tri; k_newpts_judge, k_newpts_store)"""
 import argparse
 import ctypes as C
 import importlib
@@ -125,6 +127,24 @@ def main():
         t0 = time.perf_counter()
         table.CreateNewMapPoints(points, 0, nbs, cams, F12, ep, th, masks, 0)
         t_loop.append(time.perf_counter() - t0)
+    loop_masks, chain_masks = fresh(), fresh()
+    table.CreateNewMapPoints(points, 0, nbs, cams, F12, ep, th, loop_masks, 0)
+    chained = table.CreateNewMapPointsChain(points, 0, nbs, cams, F12, ep, th, chain_masks, 0)
+    chain_same = bool(chained == made and all(np.array_equal(loop_masks[k], chain_masks[k]) for k in loop_masks))
+    t_chain = []
+    for _ in range(a.calls):
+        masks = fresh()
+        t0 = time.perf_counter()
+        table.CreateNewMapPointsChain(points, 0, nbs, cams, F12, ep, th, masks, 0)
+        t_chain.append(time.perf_counter() - t0)
+    # the call alone: records and cap-wide masks prepared outside the clock (what a C++ caller pays)
+    chain_jobs = table.tri_points_jobs([cams[0]] * NN, [cams[nb] for nb in nbs], cams[0]["ratio_factor"], cams[0]["max_size"])
+    t_call = []
+    for _ in range(a.calls):
+        m_cur, m_nb = np.zeros(CAP, np.uint8), np.zeros((NN, CAP), np.uint8)
+        t0 = time.perf_counter()
+        table.create_new_points(0, nbs, F12, ep, th, chain_jobs, m_cur, m_nb, points, 0)
+        t_call.append(time.perf_counter() - t0)
     for _ in range(a.calls):
         masks = fresh()
         t0 = time.perf_counter()
@@ -185,6 +205,8 @@ def main():
         t_up.append(time.perf_counter() - t0)
     extra = dict(neighbours=NN, features=N, matches_per_neighbour=float(np.mean(nm)))
     stats("device: CreateNewMapPoints loop, one neighbour at a time", t_loop, new_points=len(made), **extra)
+    stats("device: the CreateNewMapPoints loop in one call (afv_table_create_new_points)", t_chain, new_points=len(chained), equal_to_the_loop=chain_same, **extra)
+    stats("device: ... create_new_points alone, job records built beforehand", t_call)
     stats("device: the %d match_triangulation calls of that loop alone" % NN, t_match)
     stats("device: one batched afv_table_triangulate over %d pairs (store written)" % NN, t_batch, new_points=int(n_new.sum()), equal_to_host_program=same, **extra)
     stats("host program over the same matches", t_host, new_points=int(n_host))
