@@ -25,29 +25,9 @@ int afv_build_geometry(const afv_orb_params &p, int w, int h, int max_batch, Geo
     g.h_x = (float)w / (float)g.n_ini;
     // quadtree quotas (FeatureExtractor.cpp:97-108)
     int quota[AFV_MAX_LEVELS], cvq[AFV_MAX_LEVELS];
-    {
-        const float factor = 1.0f / p.scale_factor;
-        float desired = (float)p.nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)p.nlevels));
-        int sum = 0;
-        for (int l = 0; l < p.nlevels - 1; ++l) {
-            quota[l] = cv_round(desired);
-            sum += quota[l];
-            desired *= factor;
-        }
-        quota[p.nlevels - 1] = std::max(p.nfeatures - sum, 0);
-    }
-    {   // cv::ORB computeKeyPoints with nfeatures*10 (Feature_orb32.cpp:22), scaleFactor held as double
-        const int nf = p.nfeatures * 10;
-        const float factor = (float)(1.0 / (double)p.scale_factor);
-        float desired = nf * (1 - factor) / (1 - (float)std::pow((double)factor, (double)p.nlevels));
-        int sum = 0;
-        for (int l = 0; l < p.nlevels - 1; ++l) {
-            cvq[l] = cv_round(desired);
-            sum += cvq[l];
-            desired *= factor;
-        }
-        cvq[p.nlevels - 1] = std::max(nf - sum, 0);
-    }
+    afv_level_quotas(p.nfeatures, 1.0f / p.scale_factor, p.nlevels, quota);
+    // cv::ORB computeKeyPoints with nfeatures*10 (Feature_orb32.cpp:22), scaleFactor held as double
+    afv_level_quotas(p.nfeatures * 10, (float)(1.0 / (double)p.scale_factor), p.nlevels, cvq);
     size_t pyr_off = 0, cand_off = 0;
     int tile_base = 0, sel_base = 0, desc_blk_base = 0;
     for (int l = 0; l < p.nlevels; ++l) {
@@ -518,20 +498,6 @@ static int begin_call(afv_ctx *c, int width, int height, bool timed = true) {
     if (rc) return rc;
     c->prof = timed && c->prof_every && (c->prof_tick_extract++ % (unsigned)c->prof_every) == 0;
     return AFV_OK;
-}
-
-// true when `p` is page-locked host memory the DMA engines can reach directly (hipHostMalloc / hipHostRegister / torch pin_memory)
-static bool is_pinned_host(const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();  // plain malloc'ed memory: "invalid value", not an error for us
-        return false;
-    }
-    return at.type == hipMemoryTypeHost;
-}
-// ... for a whole buffer: first and last byte are probed (one registration covers a buffer)
-static bool is_pinned_range(const void *p, size_t bytes) {
-    return is_pinned_host(p) && is_pinned_host(static_cast<const uint8_t *>(p) + bytes - 1);
 }
 
 // the context's staging buffer as the kernels' source, laid out for THIS geometry: frames back to back when the row pitch allows it

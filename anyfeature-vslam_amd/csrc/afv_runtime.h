@@ -2,24 +2,15 @@
 // afv_match_jobs.hip, afv_project.hip, afv_frame.hip, afv_points.hip, afv_stereo.hip): the context, the pinned staging arena (Blob), the
 // kernel launcher prototypes and the job descriptions of the matcher pipelines.  Not part of the public interface.
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
 #include <cstdio>
-#include <cstddef>
 #include <cstdlib>
 #include <cstring>
-#include <new>
-#include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "afv_device.h"
+#include "afv_host.h"  // AFV_LOCAL, HIPCHK, guarded, cv_round, align_up, the level quotas, the pinned-memory probes
 #include "afv_jobs.h"
-
-// internal functions that cross translation units without entering the library's dynamic symbol table
-#define AFV_LOCAL __attribute__((visibility("hidden")))
 
 // ---- kernel launchers (k_*.hip) ----
 extern "C" void afv_launch_resize(const uint8_t *src, int sw, int sh, int spitch, size_t sframe, uint8_t *dst, int dw, int dh,
@@ -432,16 +423,6 @@ struct StageTimer {  // RAII: record begin/end events around one stage on the la
     }
 };
 
-
-#define HIPCHK(ctx, call)                                                                            \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            (ctx)->last_error = std::string(#call) + ": " + hipGetErrorString(e_);                  \
-            return e_ == hipErrorOutOfMemory ? AFV_ENOMEM : AFV_EHIP;                                \
-        }                                                                                            \
-    } while (0)
-
 // Fills and device-to-device copies that a later launch depends on.  hipMemset / hipMemcpy(device -> device) run on the NULL stream and
 // may return before they have run; the contexts' streams are created non-blocking, so nothing orders a launch on them behind such an
 // operation (round 6: a fresh context's first sliced match could meet ticket words the fill had not reached yet - or have its counts
@@ -457,8 +438,6 @@ static inline hipError_t afv_copy_dd(afv_ctx *c, void *dst, const void *src, siz
     return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
 }
 
-static inline int cv_round(float v) { return (int)lrintf(v); }
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // the small-batch ("latency") path: kernels shaped for one or a few frames / pairs; afv_set_small_batch_path
 static inline bool small_batch_path(const afv_ctx *c, int nf) { return c->small_mode == 2 || (c->small_mode == 1 && nf <= c->small_max_frames); }
 // phase 2 of a brute-force pair call.  The workgroup-wide fixed point is the faster form while every pair has a CU to itself (one pair of
@@ -467,19 +446,6 @@ static inline bool small_batch_path(const afv_ctx *c, int nf) { return c->small_
 // and faster with the one-wavefront walk (10 000 jobs: 3.52 M jobs/s against 3.30 M)
 static inline int resolve_engine_for(const afv_ctx *c, int npairs) {
     return c->resolve_engine == 2 ? (npairs <= c->resolve_wg_max_pairs ? 1 : 0) : c->resolve_engine;
-}
-// the C-ABI never throws: host allocation failures inside the matcher entry points become AFV_ENOMEM
-template <class F>
-static inline int guarded(afv_ctx *c, F &&f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc &) {
-        if (c) c->last_error = "out of host memory";
-        return AFV_ENOMEM;
-    } catch (...) {
-        if (c) c->last_error = "unexpected exception";
-        return AFV_EHIP;
-    }
 }
 
 // versioned job arrays (include/afv_hip.h, "JOB RECORDS THAT CARRY struct_size"): the caller's array, whatever layout it was compiled

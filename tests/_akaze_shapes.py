@@ -14,8 +14,9 @@ Tile constants (anyfeature-vslam_amd/csrc/):
                           than 8 frames: the remainders 0, 1, 63 of 64 are 0, 1, 15 of 16 as well);
   * k_akaze.hip:911       k_akz_halfsample: 64 x 4 destination pixels per workgroup;
   * k_akaze_detect.hip:47-49  k_akz_cand_mask: 64-column chunks (at most AKD_MAXCHUNKS = 32: levels up to 2048 wide) x AKM_ROWS = 32 rows.
-Extractor limits: akaze_api.hip:412 (w >= 80, h >= 40, stride >= w), :155 (every halved level even: exact 2x INTER_AREA),
-:147 (2 <= sigma_size <= 8), :530 (a level wider than 2048 is refused with AFV_EUNSUPPORTED), :629 (round(w / h) quadtree roots, 1 .. 16)."""
+Extractor limits: akaze_api.hip akz_frames_ok (w >= 80, h >= 40, stride >= w), akz_detect_enqueue (a level wider than 2048 is refused with
+AFV_EUNSUPPORTED), akz_describe_enqueue (round(w / h) quadtree roots, 1 .. 16); akaze_plan.hip afv_akaze_plan_for (every halved level even:
+exact 2x INTER_AREA; 2 <= sigma_size <= 8)."""
 import numpy as np
 
 AT_W, AT_H = 64, 32
@@ -58,7 +59,7 @@ def plan_levels(plan):
 
 
 def accepted(plan):
-    """the extractor's own acceptance rules for a frame whose plan this is (akaze_api.hip:147, :155, :412, :530)"""
+    """the extractor's own acceptance rules for a frame whose plan this is (afv_akaze_plan_for, akz_frames_ok, akz_detect_enqueue)"""
     lv = plan_levels(plan)
     if plan.w < MIN_W or plan.h < MIN_H or plan.w > MAX_LEVEL_W or not 1 <= int(np.round(np.float32(plan.w) / np.float32(plan.h))) <= 16:
         return False
