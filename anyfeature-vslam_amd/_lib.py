@@ -320,6 +320,7 @@ SYMBOLS = {
     "afv_set_l2_chunk_pairs": (_i, [_vp, _i]),
     "afv_debug_pyramid_plan": (_i, [C.POINTER(OrbParams), _i, _i, _i, _i, _vp, _i, _vp, _vp, _i]),
     "afv_debug_fast_tiles": (_i, [C.POINTER(OrbParams), _i, _i, _vp, _i, _vp, C.POINTER(_i)]),
+    "afv_debug_describe_reach": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "afv_set_pipeline_chunk": (_i, [_vp, _i, _i]),
     "afv_get_geometry": (_i, [_vp, C.POINTER(Geometry)]),
     "afv_debug_get_level": (_i, [_vp, _i, _i, _vp]),

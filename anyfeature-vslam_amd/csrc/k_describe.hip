@@ -300,6 +300,239 @@ __device__ __forceinline__ int blur_bits(int fx, int fy, uint32_t k_addr) {
 }
 #endif
 
+// ---- what a BRIEF test can reach: the corners of the 43 x 43 patch are never read, at any angle ----
+// A pattern point at radius r lands, rotated and rounded, on a pixel whose unit square meets the circle of radius r: that ring bound is the
+// reachable set R (tests/test_describe_reach_cpu.py sweeps the angle with the kernel's own fp32 products and finds exactly this set: 1124 of the
+// 37 x 37 positions).  From R, all at compile time and from the pattern constants the kernel includes:
+//   H values  = R dilated by the seven rows of the column pass (1347 of 43 x 40);
+//   row items = (pair-row, dword group) of the FOUR dwords blur_col reads per sample (the eighth u16 has weight 0 but its item is computed all
+//               the same: no sample dword is ever stale), per alignment a = px0 & 3: 189 or 190 of 220 - three wave steps instead of four;
+//   patch     = the seven bytes under every H value and the IC disc of ic_make_masks, as aligned dwords per alignment: 425 .. 442 of 516 -
+//               seven load / store steps of 64 lanes instead of nine of 60.
+// The union over the four alignments fits neither budget (198 items, 460 dwords): one table per alignment, selected by a scalar.
+#define RCH_R (PR - 3)                 // 18: BRIEF reach
+#define RCH_SIDE (2 * RCH_R + 1)       // 37
+#define RCH_ROW_STEPS 3
+#define RCH_STAGE_STEPS 7
+#define RCH_PAIR_ROWS ((PS + 1) / 2)
+#define RCH_GP (4 * HP)                                  // bytes of a pair-row of the interleaved plane
+#define RCH_P_OFF (RCH_PAIR_ROWS * RCH_GP - PS * PP)     // first patch byte of the slice
+struct Reach {
+    bool R[RCH_SIDE][RCH_SIDE];          // [iy + 18][ix + 18]
+    int n_R, n_H;
+    int n_items[4], n_dwords[4];
+    uint16_t item[4][64 * RCH_ROW_STEPS];      // pair-row << 8 | dword group, sorted; padded with copies of the last one
+    uint16_t dword[4][64 * RCH_STAGE_STEPS];   // patch row << 8 | dword of the row, sorted; padded with copies of the last one
+    bool fits, covered, overlay_ok, tail_ok;
+};
+constexpr Reach reach_make() {
+    Reach t{};
+    constexpr signed char pat[1024] = {
+#include "brief_pattern.inc"
+    };
+    // has[s]: a pattern point with x^2 + y^2 = s exists; cnt = prefix sums
+    int cnt[2 * RCH_R * RCH_R + 2] = {};
+    bool in_reach = true;
+    for (int i = 0; i < 512; ++i) {
+        const int s = pat[2 * i] * pat[2 * i] + pat[2 * i + 1] * pat[2 * i + 1];
+        if (4 * s >= RCH_SIDE * RCH_SIDE) in_reach = false;  // radius >= 18.5 could round to 19
+        else cnt[s + 1] = 1;
+    }
+    for (int s = 1; s < 2 * RCH_R * RCH_R + 2; ++s) cnt[s] += cnt[s - 1];  // cnt[s] = radii^2 below s
+    // pixel (ix, iy): the squared distances of its unit square from the centre span [lo / 4, hi / 4]
+    bool H[PS][RCH_SIDE] = {};
+    for (int iy = -RCH_R; iy <= RCH_R; ++iy)
+        for (int ix = -RCH_R; ix <= RCH_R; ++ix) {
+            const int ax = ix < 0 ? -ix : ix, ay = iy < 0 ? -iy : iy;
+            const int mx = ax ? 2 * ax - 1 : 0, my = ay ? 2 * ay - 1 : 0;
+            const int lo = (mx * mx + my * my + 3) / 4;                          // smallest s with 4 s >= lo4
+            int hi = ((2 * ax + 1) * (2 * ax + 1) + (2 * ay + 1) * (2 * ay + 1)) / 4;  // largest s with 4 s <= hi4
+            if (hi > 2 * RCH_R * RCH_R) hi = 2 * RCH_R * RCH_R;
+            if (lo <= hi && cnt[hi + 1] - cnt[lo] > 0) {
+                t.R[iy + RCH_R][ix + RCH_R] = true;
+                ++t.n_R;
+                for (int k = 0; k < 7; ++k) H[iy + RCH_R + k][ix + RCH_R] = true;  // plane rows yy .. yy + 6, yy = 18 + iy
+            }
+        }
+    for (int r = 0; r < PS; ++r)
+        for (int c = 0; c < RCH_SIDE; ++c) t.n_H += H[r][c] ? 1 : 0;
+    constexpr int umax[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};  // the disc of ic_make_masks
+    t.fits = in_reach;
+    t.covered = t.overlay_ok = t.tail_ok = true;
+    for (int a = 0; a < 4; ++a) {
+        // row items: the four dwords of every reachable sample (plane column xh = 18 + a + ix)
+        bool it[RCH_PAIR_ROWS][ROW_GROUPS] = {};
+        for (int y = 0; y < RCH_SIDE; ++y)
+            for (int x = 0; x < RCH_SIDE; ++x)
+                if (t.R[y][x])
+                    for (int d = 0; d < 4; ++d) {
+                        const int j = (y >> 1) + d, g = (x + a) >> 2;
+                        if (j >= RCH_PAIR_ROWS || g >= ROW_GROUPS) t.covered = false;
+                        else it[j][g] = true;
+                    }
+        int n = 0;
+        for (int j = 0; j < RCH_PAIR_ROWS; ++j)
+            for (int g = 0; g < ROW_GROUPS; ++g)
+                if (it[j][g]) {
+                    if (n < 64 * RCH_ROW_STEPS) t.item[a][n] = (uint16_t)(j << 8 | g);
+                    ++n;
+                }
+        t.n_items[a] = n;
+        if (n > 64 * RCH_ROW_STEPS || n <= 64 * (RCH_ROW_STEPS - 1)) t.fits = false;
+        for (int i = n; i < 64 * RCH_ROW_STEPS && n > 0; ++i) t.item[a][i] = t.item[a][n - 1];
+        // the overlay: every plane byte stored in steps 0 .. k lies below the first patch byte loaded in step k + 1; the pair-row without an
+        // upper patch row (the last one) is met in the last step only
+        int store_end = 0;
+        for (int k = 0; k < RCH_ROW_STEPS; ++k) {
+            int load_lo = 1 << 30;
+            for (int i = 64 * k; i < 64 * k + 64; ++i) {
+                const int j = t.item[a][i] >> 8, g = t.item[a][i] & 255;
+                const int src = RCH_P_OFF + 2 * j * PP + 4 * g;
+                load_lo = src < load_lo ? src : load_lo;
+                if (j == RCH_PAIR_ROWS - 1 && k != RCH_ROW_STEPS - 1) t.tail_ok = false;
+            }
+            if (k > 0 && store_end > load_lo) t.overlay_ok = false;
+            for (int i = 64 * k; i < 64 * k + 64; ++i) {
+                const int end = (t.item[a][i] >> 8) * RCH_GP + 16 * (t.item[a][i] & 255) + 16;
+                store_end = end > store_end ? end : store_end;
+            }
+        }
+        // patch bytes: seven under every H value (LDS column 18 + a + ix - 3 + 3 .. + 6 = c + a .. c + a + 6), and the disc
+        bool need[PS][PP] = {};
+        for (int r = 0; r < PS; ++r)
+            for (int c = 0; c < RCH_SIDE; ++c)
+                if (H[r][c]) {
+                    if (!it[r >> 1][(c + a) >> 2]) t.covered = false;
+                    for (int k = 0; k < 7; ++k) need[r][c + a + k] = true;
+                }
+        for (int v = -15; v <= 15; ++v)
+            for (int u = -umax[v < 0 ? -v : v]; u <= umax[v < 0 ? -v : v]; ++u) need[PR + v][PR + a + u] = true;
+        n = 0;
+        for (int r = 0; r < PS; ++r)
+            for (int q = 0; q < 12; ++q)
+                if (need[r][4 * q] || need[r][4 * q + 1] || need[r][4 * q + 2] || need[r][4 * q + 3]) {
+                    if (n < 64 * RCH_STAGE_STEPS) t.dword[a][n] = (uint16_t)(r << 8 | q);
+                    ++n;
+                }
+        for (int r = 0; r < PS; ++r)
+            for (int c = 48; c < PP; ++c)
+                if (need[r][c]) t.covered = false;  // past the twelve dwords the interior path stages
+        t.n_dwords[a] = n;
+        if (n > 64 * RCH_STAGE_STEPS || n == 0) t.fits = false;
+        for (int i = n; i < 64 * RCH_STAGE_STEPS && n > 0; ++i) t.dword[a][i] = t.dword[a][n - 1];
+    }
+    return t;
+}
+constexpr Reach k_reach = reach_make();
+static_assert(k_reach.fits, "reach: <= 192 row-pass items and <= 448 staged dwords per alignment, every pattern point within radius 18 x 18");
+static_assert(k_reach.covered, "reach: every H value under the four dwords of a reachable sample lies inside a computed item, every needed byte inside the staged dwords");
+static_assert(k_reach.overlay_ok, "reach: the plane bytes stored in steps 0 .. k lie below the first patch byte loaded in step k + 1");
+static_assert(k_reach.tail_ok, "reach: the pair-row without an upper patch row belongs to the last step");
+
+// Built by default: the trimmed ROW PASS.  The trimmed STAGING is built with -DDS_REACH_STAGING only: on the device it costs more than its two
+// steps save (k_describe + 5 %: a lane's image address now waits for a table load, and the unpacking takes the vector instructions the steps
+// gave back; DESIGN_LOG round 8).  -DDS_DENSE_PATCH: the dense staging and row pass of round 7 for every keypoint (A / B runs)
+#if defined(DS_ROW_MAJOR_PLANE) || defined(DS_DENSE_PATCH)
+#define DS_DENSE_ROWS
+#undef DS_REACH_STAGING
+#endif
+
+// the per-lane tables.  Row pass: step k of lane l = item 64 k + l, packed as LDS byte offsets inside the slice: source (first of the three
+// dwords of patch row 2 j) | destination << 16; a padding slot repeats the last item of its step (same loads, same store: harmless).
+// Staging: step k of lane l = dword 64 k + l, packed as LDS byte offset of the dword inside the patch | patch row << 16
+struct ReachRowTab {
+    uint32_t e[4][64][4];
+};
+struct ReachStageTab {
+    uint32_t e[4][64][8];
+};
+constexpr ReachRowTab reach_row_tab() {
+    ReachRowTab t{};
+    for (int a = 0; a < 4; ++a)
+        for (int i = 0; i < 64 * RCH_ROW_STEPS; ++i) {
+            const uint32_t j = k_reach.item[a][i] >> 8, g = k_reach.item[a][i] & 255;
+            t.e[a][i & 63][i >> 6] = (RCH_P_OFF + 2 * j * PP + 4 * g) | (j * RCH_GP + 16 * g) << 16;
+        }
+    return t;
+}
+constexpr ReachStageTab reach_stage_tab() {
+    ReachStageTab t{};
+    for (int a = 0; a < 4; ++a)
+        for (int i = 0; i < 64 * RCH_STAGE_STEPS; ++i) {
+            const uint32_t r = k_reach.dword[a][i] >> 8, q = k_reach.dword[a][i] & 255;
+            t.e[a][i & 63][i >> 6] = (r * PP + 4 * q) | r << 16;
+        }
+    return t;
+}
+#ifndef DS_DENSE_ROWS
+__device__ __constant__ __attribute__((aligned(16))) const ReachRowTab k_reach_rows = reach_row_tab();
+#endif
+#ifdef DS_REACH_STAGING
+__device__ __constant__ __attribute__((aligned(16))) const ReachStageTab k_reach_stage = reach_stage_tab();
+#endif
+
+#ifndef DS_DENSE_ROWS
+static_assert(RCH_GP == GP && RCH_PAIR_ROWS == PAIR_ROWS && RCH_P_OFF == PLANE_BYTES - PS * PP, "reach tables: the slice layout of the kernel");
+// the row pass over the items a BRIEF test can reach (alignment a, BRIEF centre = patch centre): per-item arithmetic as in blur_rows, the loads
+// of step k + 1 before the store of step k; t = the lane's entry of k_reach_rows.  Plane entries outside the items keep stale bytes; nothing reads
+// them (k_reach.covered)
+__device__ __forceinline__ void blur_rows_reach(uint8_t *slice, const uint4 t) {
+    const uint32_t ent[RCH_ROW_STEPS] = {t.x, t.y, t.z};
+    const uint32_t *s0 = reinterpret_cast<const uint32_t *>(slice + (ent[0] & 0xffffu));
+    uint32_t d[6] = {s0[0], s0[1], s0[2], s0[PP / 4], s0[PP / 4 + 1], s0[PP / 4 + 2]}, n[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < RCH_ROW_STEPS; ++k) {
+        if (k + 1 < RCH_ROW_STEPS) {
+            const uint32_t so = ent[k + 1] & 0xffffu;
+            const uint32_t *s = reinterpret_cast<const uint32_t *>(slice + so);
+            n[0] = s[0], n[1] = s[1], n[2] = s[2];
+            // nothing past the slice is read: the last pair-row (last step only: k_reach.tail_ok) has no upper patch row; its u16 has weight 0
+            if (k + 1 < RCH_ROW_STEPS - 1 || so < (uint32_t)(RCH_P_OFF + (PS - 1) * PP)) n[3] = s[PP / 4], n[4] = s[PP / 4 + 1], n[5] = s[PP / 4 + 2];
+        }
+        uint32_t e[4], o[4];
+        row_taps4(d[0], d[1], d[2], e);
+        row_taps4(d[3], d[4], d[5], o);
+        uint4 w;
+        w.x = e[0] | (o[0] << 16);
+        w.y = e[1] | (o[1] << 16);
+        w.z = e[2] | (o[2] << 16);
+        w.w = e[3] | (o[3] << 16);
+        *reinterpret_cast<uint4 *>(slice + (ent[k] >> 16)) = w;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) d[i] = n[i];
+    }
+}
+#endif
+
+// host-only (no device, no context): the reach tables as the kernel holds them.  R: 37 x 37 bytes [iy + 18][ix + 18]; items[4][192]: pair-row << 8 |
+// dword group in schedule order (step = index / 64, lane = index % 64), dwords[4][448]: patch row << 8 | dword of the row likewise, both padded
+// with copies; counts[8]: items per alignment, staged dwords per alignment; layout[8]: row steps, staging steps, patch offset in the slice,
+// patch pitch, bytes of a pair-row, slice bytes, 1 if the kernel trims the row pass, 1 if it trims the staging
+extern "C" int afv_debug_describe_reach(uint8_t *R, uint16_t *items, uint16_t *dwords, int32_t *counts, int32_t *layout) {
+    if (!R || !items || !dwords || !counts || !layout) return AFV_EINVAL;
+    for (int y = 0; y < RCH_SIDE; ++y)
+        for (int x = 0; x < RCH_SIDE; ++x) R[y * RCH_SIDE + x] = k_reach.R[y][x] ? 1 : 0;
+    for (int a = 0; a < 4; ++a) {
+        for (int i = 0; i < 64 * RCH_ROW_STEPS; ++i) items[a * 64 * RCH_ROW_STEPS + i] = k_reach.item[a][i];
+        for (int i = 0; i < 64 * RCH_STAGE_STEPS; ++i) dwords[a * 64 * RCH_STAGE_STEPS + i] = k_reach.dword[a][i];
+        counts[a] = k_reach.n_items[a];
+        counts[4 + a] = k_reach.n_dwords[a];
+    }
+    layout[0] = RCH_ROW_STEPS, layout[1] = RCH_STAGE_STEPS, layout[2] = RCH_P_OFF, layout[3] = PP, layout[4] = RCH_GP;
+    layout[5] = RCH_PAIR_ROWS * RCH_GP;
+#ifdef DS_DENSE_ROWS
+    layout[6] = 0;
+#else
+    layout[6] = 1;
+#endif
+#ifdef DS_REACH_STAGING
+    layout[7] = 1;
+#else
+    layout[7] = 0;
+#endif
+    return AFV_OK;
+}
+
 // MODE 0: the extraction pipeline (keypoints of the quadtree survivors + their descriptors: detectAndCompute);
 // MODE 1: keypoints only - position, IC angle, response (afv_orb_detect: detectKeypoints + filterKeypoints, Feature_orb32.cpp:26-40, :63-65);
 // MODE 2: descriptors of CALLER-GIVEN keypoints at their own angle (afv_orb_compute: computeDescriptors = cv::ORB::compute, :42-53):
@@ -412,11 +645,46 @@ __device__ __forceinline__ void describe_body(const Geo *__restrict__ geo_p, con
 
     // ---- 1. stage the 43x43 unblurred patch; P[r][a + c] = level(cx-21+c, cy-21+r) with reflect-101 ----
     const int px0 = cx - PR, py0 = cy - PR;
-    int a;  // column offset of patch column 0 inside the LDS row
     const bool interior = px0 >= 0 && py0 >= 0 && px0 + 48 <= lw && py0 + PS <= lh;  // wave-uniform
+    const int a = interior ? px0 & 3 : 0;  // column offset of patch column 0 inside the LDS row: interior patches are staged as aligned dwords
+#ifndef DS_DENSE_ROWS
+    // the lane's three row-pass items, asked for before the patch: the load's latency passes behind the staging's
+    uint4 row_items = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (MODE != 1) row_items = *reinterpret_cast<const uint4 *>(k_reach_rows.e[a][lane]);
+#endif
+#ifndef DS_DENSE_PATCH
+    // so are the lane's disc masks of the IC stage (the table loads of this kernel depend on the lane alone: each one issued where it is used
+    // is a wait of a whole memory round trip per keypoint - round 8)
+    uint4 mk = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (MODE != 2) mk = *reinterpret_cast<const uint4 *>(k_ic_masks.m[lane]);
+#endif
+    // BRIEF centre = cvRound(pt * (1/scale)) with pt = level coordinate * scale (orb.cpp computeOrbDescriptors); a given keypoint's
+    // centre IS that rounding already
+    const float ptx = (float)cx * L.scale, pty = (float)cy * L.scale;
+    const int bx = MODE == 2 ? cx : (int)rintf(ptx * L.inv_scale), by = MODE == 2 ? cy : (int)rintf(pty * L.inv_scale);
+    const int ox = bx - cx, oy = by - cy;  // 0 in practice; kept literal
+    // the reach tables hold for a BRIEF centre that is the patch centre; any other keypoint takes the dense staging and row pass (wave-uniform)
+    const bool centred = (ox | oy) == 0;
+#ifdef DS_REACH_STAGING
+    // pitch >= PP: the table's LDS offset r * PP + 4 q becomes the image offset by adding r * (pitch - PP), one 24-bit multiply-add
+    if (MODE != 1 && interior && centred && pitch >= PP) {
+        // interior, staged for a descriptor: only the dwords the row pass and the IC disc read (k_reach), 64 per wave instruction
+        const uint4 *tp = reinterpret_cast<const uint4 *>(k_reach_stage.e[a][lane]);
+        const uint4 ta = tp[0], tb = tp[1];
+        const uint32_t ent[RCH_STAGE_STEPS] = {ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, tb.z};
+        // 32-bit byte offsets from a scalar base, as below
+        uint32_t o_patch = (uint32_t)py0 * (uint32_t)pitch + (uint32_t)(px0 - a), dp = (uint32_t)(pitch - PP);
+        asm("" : "+s"(o_patch), "+s"(dp));
+        const uint8_t *ip = img + o_patch;
+        uint32_t v[RCH_STAGE_STEPS];  // loads first, then the LDS writes
+#pragma unroll
+        for (int k = 0; k < RCH_STAGE_STEPS; ++k) v[k] = *reinterpret_cast<const uint32_t *>(ip + mad_u24(ent[k] >> 16, dp, ent[k] & 0xffffu));
+#pragma unroll
+        for (int k = 0; k < RCH_STAGE_STEPS; ++k) *reinterpret_cast<uint32_t *>(P + (ent[k] & 0xffffu)) = v[k];
+    } else
+#endif
     if (interior) {
         // interior: 12 aligned dwords per row, 5 rows per wave instruction
-        a = px0 & 3;
         const int ax0 = px0 - a;
         const int rr = lane / 12, rq = lane - rr * 12;
         if (lane < 60) {
@@ -439,7 +707,6 @@ __device__ __forceinline__ void describe_body(const Geo *__restrict__ geo_p, con
         }
     } else {
         // border: lane = patch column (reflected once), rows reflected per iteration (wave-uniform)
-        a = 0;
         if (lane < PS) {
             const int x = afv_reflect101(px0 + lane, lw);
             for (int r = 0; r < PS; ++r) {
@@ -462,7 +729,9 @@ __device__ __forceinline__ void describe_body(const Geo *__restrict__ geo_p, con
             const int A = (PR + v) * PP + PR + a + (half ? 0 : -16);
             const uint32_t *wp = reinterpret_cast<const uint32_t *>(P + (A & ~3));
             const int sh = (A & 3) * 8;
+#ifdef DS_DENSE_PATCH
             const uint4 mk = *reinterpret_cast<const uint4 *>(k_ic_masks.m[lane]);
+#endif
             const uint32_t w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3], w4 = wp[4];
             const uint32_t b[4] = {__builtin_amdgcn_alignbit(w1, w0, sh) & mk.x, __builtin_amdgcn_alignbit(w2, w1, sh) & mk.y,
                                    __builtin_amdgcn_alignbit(w3, w2, sh) & mk.z, __builtin_amdgcn_alignbit(w4, w3, sh) & mk.w};
@@ -476,14 +745,27 @@ __device__ __forceinline__ void describe_body(const Geo *__restrict__ geo_p, con
             m01 = v * (int)s1;
         }
     }
-    if constexpr (MODE != 1) blur_rows(P, H, lane);  // overwrites the patch (see the slice layout above): everything that reads P comes before this line
+    // the row pass overwrites the patch (see the slice layout above): everything that reads P comes before these lines
+#ifndef DS_DENSE_ROWS
+    if constexpr (MODE != 1) {
+        if (centred) blur_rows_reach(s_slice[wv], row_items);
+        else blur_rows(P, H, lane);
+    }
+#else
+    if constexpr (MODE != 1) blur_rows(P, H, lane);
+#endif
+    // the first group's test pairs, asked for before the angle is worked out; every later group's while the group before it is evaluated
+    const float4 *pat = reinterpret_cast<const float4 *>(k_brief_pattern) + lane;
+#ifndef DS_DENSE_PATCH
+    float4 pt_next = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (MODE != 1) pt_next = pat[0];
+#endif
     float angle = given_angle;
     if constexpr (MODE != 2) {
         m10 = afv_wave_sum(m10);
         m01 = afv_wave_sum(m01);
         angle = fast_atan2_deg((float)m01, (float)m10);
     }
-    const float ptx = (float)cx * L.scale, pty = (float)cy * L.scale;
     if constexpr (MODE == 1) {  // keypoints only
         if (lane == 0) {
             afv_keypoint k;
@@ -504,20 +786,20 @@ __device__ __forceinline__ void describe_body(const Geo *__restrict__ geo_p, con
     float ca, sb;
     sincos_deg(angle, ca, sb);
     wave_sync();  // row-filtered plane complete
-    // BRIEF centre = cvRound(pt * (1/scale)) with pt = level coordinate * scale (orb.cpp computeOrbDescriptors); a given keypoint's
-    // centre IS that rounding already
-    const int bx = MODE == 2 ? cx : (int)rintf(ptx * L.inv_scale), by = MODE == 2 ? cy : (int)rintf(pty * L.inv_scale);
-    const int ox = bx - cx, oy = by - cy;  // 0 in practice; kept literal
     const int kox = ox - 0x4B400000, koy = oy - 0x4B400000;  // scalar: the mantissa offset of the rounding trick below and the (0) centre offset
     // a patch inside the level whose BRIEF centre is the patch centre (always, see above): LDS addresses straight from the float bits
-    const bool direct = interior && (ox | oy) == 0;  // wave-uniform
+    const bool direct = interior && centred;  // wave-uniform
     uint32_t k_addr = blur_addr_const((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)H, a);
     asm("" : "+s"(k_addr));  // one opaque scalar: the compiler would take it apart again and add its pieces per sample
     uint32_t words[8];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const int t = g * 64 + lane;
-        const float4 pt = reinterpret_cast<const float4 *>(k_brief_pattern)[t];
+#ifdef DS_DENSE_PATCH
+        const float4 pt = pat[g * 64];
+#else
+        const float4 pt = pt_next;
+        if (g + 1 < 4) pt_next = pat[(g + 1) * 64];
+#endif
         const float x0 = pt.x, y0 = pt.y, x1 = pt.z, y1 = pt.w;
         // (x ca - y sb, x sb + y ca) in PLAIN fp32, one rounding per operator (a - b = a + (-b), (-s) y = -(s y); -ffp-contract=off).
         // Round 5 held this as three packed instructions per point ((x, x) * (ca, sb) + (y, y) * (-sb, ca)); round 6 found that

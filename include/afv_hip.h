@@ -1000,6 +1000,15 @@ int afv_debug_pyramid_plan(const afv_orb_params *params, int width, int height, 
  * w, h per level.  tests/test_fast_ragged_cpu.py holds these decisions to rectangles it computes itself. */
 int afv_debug_fast_tiles(const afv_orb_params *params, int width, int height, int32_t *tiles, int tiles_cap, int32_t *level_wh, int *n_out);
 
+/* host-only (no device, no context): what the describe kernel stages and row-filters of a keypoint's 43 x 43 patch - the tables it was compiled
+ * with.  R[37 * 37]: 1 where a rotated BRIEF test can land, [iy + 18][ix + 18].  Per patch alignment a = 0..3 (first patch column & 3):
+ * items[a][192] = pair-row << 8 | group of four plane columns, in schedule order (wave step = index / 64, lane = index % 64);
+ * dwords[a][448] = patch row << 8 | dword of the LDS row, likewise; both padded with copies of their last entry.  counts[8]: items per
+ * alignment, then staged dwords per alignment.  layout[8]: row-pass steps, staging steps, byte offset of the patch in a wavefront's LDS slice,
+ * pitch of a patch row, bytes of a plane pair-row, slice bytes, 1 if the built kernel trims the row pass, 1 if it trims the staging.
+ * tests/test_describe_reach_cpu.py holds the tables to an angle sweep of the pattern. */
+int afv_debug_describe_reach(uint8_t *R, uint16_t *items, uint16_t *dwords, int32_t *counts, int32_t *layout);
+
 #ifdef __cplusplus
 }
 #endif
