@@ -11,6 +11,7 @@ Layout:
   frame.py       the device-resident Frame (reference: Frame.{h,cc} as far as the front end reads it)
   points.py      the device-resident map-point store (reference: MapPoint.{h,cc} as far as the projection searches read it)
   database.py    KeyFrameDatabase mirror over the keyframe table (reference: KeyFrameDatabase.{h,cc}, LoopClosing.cc:137-157)
+  sim3.py        Sim3Solver mirror: all RANSAC hypotheses of a loop check in one device call (reference: Sim3Solver.{h,cc})
   synth.py       bit-reproducible synthetic inputs
 """
 from . import _lib, synth  # noqa: F401
@@ -21,6 +22,7 @@ from .frame import Frame  # noqa: F401
 from .points import MapPoints  # noqa: F401
 from . import akaze, table  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
+from .sim3 import Sim3Solver  # noqa: F401
 from .akaze import AkazeContext  # noqa: F401
 from .matcher import (FeatureMatcher, FeatureView, FrameGridView, ProjectionQueries, ComputeDistinctiveDescriptors,  # noqa: F401
                       DescriptorDistance_orb32, DescriptorDistance_sift128)

@@ -143,6 +143,14 @@ class TriPointsJob(C.Structure):
                                           "mb1", "mb2", "mbf1", "ratio_factor", "max_size1")])
 
 
+class Sim3Job(C.Structure):
+    """afv_sim3_job: one (current keyframe, candidate) pair of afv_table_sim3_hypotheses"""
+    _fields_ = ([("struct_size", C.c_uint32), ("fix_scale", C.c_int32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)] +
+                [(k, C.c_float * n) for k, n in (("Rcw1", 9), ("tcw1", 3), ("Rcw2", 9), ("tcw2", 3))] +
+                [(k, C.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2")])
+
+
+SIM3_MAX_CANDIDATES, SIM3_MAX_HYPOTHESES, SIM3_MAX_MASK_WORDS = 64, 1024, 256
 TRI_MAX_PAIRS = 64
 TRI_STATUS = ("no_match", "accepted", "low_parallax", "w_zero", "z1", "z2", "reproj1", "reproj2", "zero_dist", "scale_ratio", "not_finite")
 TRI_ROUTE = ("triangulated", "unproject_a", "unproject_b")
@@ -274,6 +282,8 @@ SYMBOLS = {
     "afv_table_triangulate": (_i, [_vp, _vp, _vp, C.POINTER(TriPointsJob), _i, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "afv_table_create_new_points": (_i, [_vp, C.c_int32, _vp, _i, C.POINTER(TableTriJob), C.POINTER(TriPointsJob), _vp, _vp, _vp, C.c_int32,
                                          _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "afv_table_sim3_hypotheses": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Sim3Job), _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _vp, _vp]),
     "afv_vocab_set_weights": (_i, [_vp, _vp, _vp, _vp]),
     "afv_bow_vector": (_i, [_vp, _vp, _vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_frame_get_bowvec": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),

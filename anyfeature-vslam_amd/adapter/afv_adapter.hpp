@@ -1216,4 +1216,140 @@ class NewMapPoints {
     int cap;
 };
 
+// ---- Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc) as LoopClosing::ComputeSim3 uses it (src/LoopClosing.cc:247-416): Batch makes
+// ONE afv_table_sim3_hypotheses call for all candidates of a loop check - every solver's constructor and every RANSAC hypothesis run on
+// the device (include/afv_hip.h, "Sim3Solver": quirks Q1-Q3, deviations S1-S6) - and returns one solver per candidate.  iterate / find are
+// host code over the per-hypothesis counts, transforms and inlier words: hypothesis h depends on (seed, h) alone, so the reference's
+// sequential rule (running best, return on > minInliers) is a scan.  T12 is 16 floats row-major (cv::Mat 4 x 4 CV_32F in the reference).
+class Sim3Solver {
+  public:
+    struct Camera {  // one keyframe of a job: Rcw row-major, tcw, the intrinsics
+        float Rcw[9], tcw[3], fx, fy, cx, cy;
+    };
+    // cur: the slot of the current keyframe (mN1 = n1 features), cands: the candidates' slots; mp1[n1]: the point id per feature of the
+    // current keyframe (GetMapPointMatches, -1 = none); mp2 / idx2: per candidate n1 entries, vpMatched12 as point ids and
+    // GetIndexInKeyFrame of those points in their candidate; idx1: the same for mp1 in the current keyframe (empty: the feature itself);
+    // candidate c draws from seed + c
+    static std::vector<Sim3Solver> Batch(afv_ctx *ctx, afv_table *table, int cap, DeviceMapPoints &points, int32_t cur, const Camera &cam_cur,
+                                         const std::vector<int32_t> &cands, const std::vector<Camera> &cam_cands, int n1,
+                                         const std::vector<int32_t> &mp1, const std::vector<std::vector<int32_t>> &mp2,
+                                         const std::vector<std::vector<int32_t>> &idx2, bool fix_scale, uint64_t seed = 0,
+                                         const std::vector<int32_t> &idx1 = {}, int nhyp = 300) {
+        const size_t nc = cands.size(), cells = nc * (size_t)cap;
+        const int words = (cap + 31) / 32;
+        std::vector<afv_sim3_job> jobs(nc);
+        std::vector<int32_t> slot_a(nc, cur), r1(cells, -1), r2(cells, -1), k1(cells, -1), k2(cells, -1);
+        for (size_t c = 0; c < nc; ++c) {
+            afv_sim3_job &j = jobs[c];
+            std::memset(&j, 0, sizeof(j));
+            j.struct_size = (uint32_t)sizeof(afv_sim3_job);
+            j.fix_scale = fix_scale ? 1 : 0;
+            const uint64_t s = seed + c;
+            j.seed_lo = (uint32_t)s; j.seed_hi = (uint32_t)(s >> 32);
+            std::memcpy(j.Rcw1, cam_cur.Rcw, sizeof(j.Rcw1)); std::memcpy(j.tcw1, cam_cur.tcw, sizeof(j.tcw1));
+            std::memcpy(j.Rcw2, cam_cands[c].Rcw, sizeof(j.Rcw2)); std::memcpy(j.tcw2, cam_cands[c].tcw, sizeof(j.tcw2));
+            j.fx1 = cam_cur.fx; j.fy1 = cam_cur.fy; j.cx1 = cam_cur.cx; j.cy1 = cam_cur.cy;
+            j.fx2 = cam_cands[c].fx; j.fy2 = cam_cands[c].fy; j.cx2 = cam_cands[c].cx; j.cy2 = cam_cands[c].cy;
+            for (int i = 0; i < n1 && i < cap; ++i) {
+                const size_t o = c * (size_t)cap + (size_t)i;
+                r1[o] = mp1[(size_t)i]; r2[o] = mp2[c][(size_t)i]; k2[o] = idx2[c][(size_t)i];
+                k1[o] = idx1.empty() ? i : idx1[(size_t)i];
+            }
+        }
+        std::vector<int32_t> n(nc), index1(cells), count(nc * (size_t)nhyp);
+        std::vector<uint8_t> degenerate(nc * (size_t)nhyp);
+        std::vector<float> sim3(nc * (size_t)nhyp * 13);
+        std::vector<uint32_t> inliers(nc * (size_t)nhyp * (size_t)words);
+        const int rc = afv_table_sim3_hypotheses(table, points.handle(), slot_a.data(), cands.data(), jobs.data(), (int)nc, r1.data(), r2.data(),
+                                                 k1.data(), k2.data(), nhyp, words, n.data(), index1.data(), count.data(), degenerate.data(),
+                                                 sim3.data(), inliers.data(), nullptr, nullptr, nullptr);
+        if (rc != AFV_OK) fatal("afv_table_sim3_hypotheses", rc, ctx);
+        std::vector<Sim3Solver> out;
+        for (size_t c = 0; c < nc; ++c) {
+            Sim3Solver s;
+            s.N = n[c]; s.mN1 = n1; s.nhyp = nhyp; s.words = words;
+            s.index1.assign(index1.begin() + (long)(c * (size_t)cap), index1.begin() + (long)(c * (size_t)cap) + s.N);
+            s.count.assign(count.begin() + (long)(c * (size_t)nhyp), count.begin() + (long)((c + 1) * (size_t)nhyp));
+            s.degenerate.assign(degenerate.begin() + (long)(c * (size_t)nhyp), degenerate.begin() + (long)((c + 1) * (size_t)nhyp));
+            s.sim3.assign(sim3.begin() + (long)(c * (size_t)nhyp * 13), sim3.begin() + (long)((c + 1) * (size_t)nhyp * 13));
+            s.inliers.assign(inliers.begin() + (long)(c * (size_t)nhyp * (size_t)words), inliers.begin() + (long)((c + 1) * (size_t)nhyp * (size_t)words));
+            s.SetRansacParameters(0.99, 6, std::min(300, nhyp));  // :109, within what the device evaluated
+            out.push_back(std::move(s));
+        }
+        return out;
+    }
+
+    // :112-136 (Q3).  false (nothing changes): maxIterations beyond the evaluated hypotheses, or minInliers < 3
+    bool SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        if (maxIterations > nhyp || minInliers < 3) return false;
+        mRansacProb = probability;
+        mRansacMinInliers = minInliers;
+        const float epsilon = (float)minInliers / (float)N;
+        double v = 1.0;
+        if (minInliers != N) v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
+        // a double outside int's range is undefined in the reference: here it saturates and a NaN reads maxIterations
+        int nIterations = maxIterations;
+        if (v == v) nIterations = v >= 2147483647.0 ? 2147483647 : (v <= -2147483648.0 ? (-2147483647 - 1) : (int)v);
+        mRansacMaxIts = std::max(1, std::min(nIterations, maxIterations));
+        mnIterations = 0;
+        return true;
+    }
+
+    // :138-204.  T12: 16 floats when the return value is true
+    bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, float *T12) {
+        bNoMore = false;
+        vbInliers.assign((size_t)mN1, false);
+        nInliers = 0;
+        if (N < mRansacMinInliers) {
+            bNoMore = true;
+            return false;
+        }
+        int nCurrentIterations = 0;
+        while (mnIterations < mRansacMaxIts && nCurrentIterations < nIterations) {
+            nCurrentIterations++;
+            const int h = mnIterations++;
+            const int c = count[(size_t)h];  // a degenerate hypothesis counts 0 and still advances mnIterations
+            if (c >= mnBestInliers) {
+                mnBestInliers = c;
+                best = h;
+                if (c > mRansacMinInliers) {
+                    nInliers = c;
+                    const uint32_t *w = inliers.data() + (size_t)h * (size_t)words;
+                    for (int i = 0; i < N; ++i)
+                        if ((w[i >> 5] >> (i & 31)) & 1u) vbInliers[(size_t)index1[(size_t)i]] = true;
+                    const float *r = sim3.data() + (size_t)h * 13;
+                    for (int a = 0; a < 3; ++a) {
+                        for (int b = 0; b < 3; ++b) T12[4 * a + b] = r[12] * r[3 * a + b];  // mat3f sR = s12i * R12i
+                        T12[4 * a + 3] = r[9 + a];
+                    }
+                    T12[12] = T12[13] = T12[14] = 0.0f;
+                    T12[15] = 1.0f;
+                    return true;
+                }
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) bNoMore = true;
+        return false;
+    }
+
+    bool find(std::vector<bool> &vbInliers12, int &nInliers, float *T12) {  // :206-210
+        bool flag;
+        return iterate(mRansacMaxIts, flag, vbInliers12, nInliers, T12);
+    }
+
+    // the best hypothesis so far (best < 0: none yet)
+    const float *GetEstimatedRotation() const { return best < 0 ? nullptr : sim3.data() + (size_t)best * 13; }
+    const float *GetEstimatedTranslation() const { return best < 0 ? nullptr : sim3.data() + (size_t)best * 13 + 9; }
+    float GetEstimatedScale() const { return best < 0 ? 0.0f : sim3[(size_t)best * 13 + 12]; }
+
+    int N = 0, mN1 = 0, nhyp = 0, words = 0;
+    int mnIterations = 0, mnBestInliers = 0, best = -1;
+    int mRansacMinInliers = 6, mRansacMaxIts = 300;
+    double mRansacProb = 0.99;
+    std::vector<int32_t> index1, count;   // mvnIndices1; inliers per hypothesis
+    std::vector<uint8_t> degenerate;      // S5 flags per hypothesis
+    std::vector<float> sim3;              // [nhyp][13]: R12 row-major, t12, s12
+    std::vector<uint32_t> inliers;        // [nhyp][words]
+};
+
 }  // namespace afv

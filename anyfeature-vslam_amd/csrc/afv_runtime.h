@@ -196,6 +196,34 @@ struct DevNewPtsArgs {       // a kernel argument of both launches of every neig
 extern "C" void afv_launch_newpts_judge(const DevNewPtsArgs *args, int k, hipStream_t stream);
 extern "C" void afv_launch_newpts_store(const DevNewPtsArgs *args, int k, hipStream_t stream);
 
+// ---- k_sim3.hip: Sim3Solver's constructor and all its RANSAC hypotheses (host side: afv_sim3.hip) ----
+#define AFV_SIM3_T 256       // lanes per workgroup of both launches
+struct DevSim3Cand {         // one candidate: the caller's record and where the sigma2 planes of the two slots start
+    float R1[9], t1[3], R2[9], t2[3];
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    unsigned long long seed;
+    int fix_scale, n1;
+    const float *sigma2_1, *sigma2_2;
+};
+struct DevSim3Args {         // a kernel argument of both launches
+    const DevSim3Cand *cands;
+    const int *mp1, *mp2, *idx1, *idx2;  // [nc][cap]; idx1 null: i1
+    int nc, cap, nhyp, mask_words;
+    const float *pos[3];     // the store: XYZ planes and flags over `pcap` ids
+    const uint8_t *flags;
+    int pcap;
+    int *n, *index1;         // [nc], [nc][cap]
+    float *x1, *x2;          // [nc][cap][3] mvX3Dc1 / mvX3Dc2
+    float *im1, *im2;        // [nc][cap][2] mvP1im1 / mvP2im2
+    float *max_err;          // [nc][cap][2]
+    int *count;              // [nc][nhyp]
+    uint8_t *degenerate;     // [nc][nhyp]
+    float *sim3;             // [nc][nhyp][13]
+    uint32_t *inliers;       // [nc][nhyp][mask_words]
+};
+extern "C" void afv_launch_sim3_gather(const DevSim3Args *args, hipStream_t stream);
+extern "C" void afv_launch_sim3_hypotheses(const DevSim3Args *args, hipStream_t stream);
+
 // ---- k_poseopt.hip: Optimizer::PoseOptimization on a resident frame (host side: afv_poseopt.hip) ----
 struct DevPoseOut {          // what the workgroup of a job leaves
     float R[9], t[3];

@@ -826,6 +826,65 @@ int afv_table_create_new_points(afv_table *t, int32_t cur, const int32_t *neighb
                                 int32_t *match12, uint8_t *status, uint8_t *route, float *x3d, int32_t *new_id, int32_t *n_new,
                                 int32_t *n_done);
 
+/* ---- Sim3Solver: all RANSAC hypotheses of a loop check at once (src/Sim3Solver.cc:38-411, as LoopClosing::ComputeSim3 uses it,
+ * src/LoopClosing.cc:247-416).  Per candidate keyframe the constructor (the filter over vpMatched12, X3Dc1 / X3Dc2, their images, the two
+ * error bounds) and EVERY hypothesis h < nhyp (three draws, Horn's closed form on them, T12 and T21, CheckInliers over all N
+ * correspondences) run on the device: two launches and ONE wait per call whatever the number of candidates (csrc/k_sim3.hip:
+ * k_sim3_gather, one workgroup per candidate; k_sim3_hypotheses, one wavefront per (candidate, hypothesis)).  Hypothesis h depends on
+ * (seed, h) alone, so the sequential rule of Sim3Solver::iterate (running best, return on > minInliers) is a scan over count[h] that the
+ * host does exactly (afv::Sim3Solver of the adapter, Sim3Solver of the Python package).
+ * The normative semantics are tests/_sim3_ref.py; the device is held to it bit for bit - parity with a build of the reference is
+ * unpinned.  Float arithmetic, one rounding per operator, a three-term sum (a row of a 3 x 3 product, a dot product) as a0 + (a1 + a2),
+ * scalar expressions left to right as written; double where the reference accumulates in double: cv::Mat::dot (nom, err1, err2), den.
+ * Quirks restated as written:
+ *   Q1  mvnMaxError1/2 are vector<size_t>: the bound is (size_t)(9.210 * sigmaSquare), truncated, and err < bound compares in float
+ *   Q2  the best hypothesis is updated on mnInliersi >= mnBestInliers, iterate returns on mnInliersi > mRansacMinInliers (strict)
+ *   Q3  SetRansacParameters: epsilon in float, ceil(log(1 - p) / log(1 - pow(epsilon, 3))) in double, max(1, min(nIterations,
+ *       maxIterations)); host mathematics only
+ * Deliberate deviations:
+ *   S1  the reference assigns N(0..2,3) from row 3, which was never written (:254-256); here N is Horn's symmetric matrix:
+ *       N(3,0..2) = N(0..2,3) as computed at :242, :247, :252
+ *   S2  the eigenvector of the largest eigenvalue comes from a cyclic Jacobi on the symmetric 4 x 4 in double: pairs (0,1) (0,2) (0,3)
+ *       (1,2) (1,3) (2,3); only + - * / and sqrt; at most 12 sweeps, a pair is skipped when a_pq == 0 or |a_pp| + |a_pq| == |a_pp| and
+ *       |a_qq| + |a_pq| == |a_qq|, a sweep that rotates nothing ends it; ties on the maximum go to the lowest index.  It replaces
+ *       Eigen::EigenSolver
+ *   S3  R12 is built directly from the normalised quaternion, in double, then rounded to float; it replaces atan2 + cv::Rodrigues
+ *   S4  draws come from the counter-based generator of the vocabulary trainer: sm = splitmix64, key_h = sm(sm(seed) ^ (h + 1)), draw
+ *       d in {0, 1, 2} = sm(key_h + (d + 1) * 0xD1342543DE82EF95) % (N - d), applied to vAvailableIndices with the reference's
+ *       swap-with-back removal (:166-173)
+ *   S5  a hypothesis is degenerate if den (when the scale is estimated), s12i, R12 or t12 is not finite, or den == 0: it counts 0
+ *       inliers, is flagged, and its sim3 record and inlier words read 0.  A correspondence whose error is not finite is not an inlier
+ *       (the comparisons as written).  A sigma2 that is negative or not finite gives bound 0
+ *   S6  N < 3 evaluates no hypothesis: all counts 0, no flag (callers reach bNoMore first: min_inliers >= 3 is required)
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(afv_sim3_job) */
+    int32_t fix_scale;                       /* mbFixScale: 0 / 1 */
+    uint32_t seed_lo, seed_hi;               /* the 64-bit seed of S4 */
+    float Rcw1[9], tcw1[3], Rcw2[9], tcw2[3]; /* row-major; 1 = the current keyframe, 2 = the candidate */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+} afv_sim3_job;
+#define AFV_SIM3_MAX_CANDIDATES 64
+#define AFV_SIM3_MAX_HYPOTHESES 1024
+#define AFV_SIM3_MAX_MASK_WORDS 256 /* mask_words 0 .. 256: twice what the largest table (cap 4096) needs */
+/* nc 1 .. AFV_SIM3_MAX_CANDIDATES candidates: slot_a[c] holds keyframe 1 (mN1 = its feature count n1), slot_b[c] keyframe 2.  Host rows
+ * of `cap` (the table's) ints per candidate, of which entries i1 < n1 are read: mp1 = the map-point id of feature i1 of keyframe 1
+ * (vpKeyFrameMP1), mp2 = vpMatched12[i1], -1 = none; idx1 / idx2 = GetIndexInKeyFrame of the two points in their keyframes (idx1 NULL:
+ * i1 itself).  A correspondence survives when mp2 >= 0, mp1 >= 0, neither point is bad in the store (an id that was never set counts as
+ * bad), idx1 >= 0 and idx2 >= 0; the survivors keep the order of i1.  Outputs (host): n[nc] = N; index1[nc][cap] = mvnIndices1 (-1 from
+ * N on); count / degenerate [nc][nhyp]; sim3[nc][nhyp][13] = R12 row-major, t12, s12 (T12 = [s12 * R12 | t12]); inliers
+ * [nc][nhyp][mask_words], bit k of the row = correspondence k, unused bits 0; optional x3dc1 / x3dc2 [nc][cap][3] (mvX3Dc1/2) and
+ * max_err[nc][cap][2] (the two Q1 bounds as floats), 0 from N on.
+ * Refused before any launch, nothing written: AFV_EINVAL for NULL t / points / slot_a / slot_b / jobs / mp1 / mp2 / idx2 / n / index1 /
+ * count / degenerate / sim3 / inliers, nc, nhyp or mask_words out of range, an unknown struct_size, a fix_scale other than 0 / 1, a slot out of
+ * range or one holding features without geometry, a store of another context, an id outside [-1, capacity), an idx outside [-1, n_slot),
+ * mask_words * 32 below the largest number of entries with mp1, mp2, idx1, idx2 >= 0 of a candidate.  The store's descriptor kind and
+ * width do not matter: descriptors are not read. */
+int afv_table_sim3_hypotheses(afv_table *t, afv_points *points, const int32_t *slot_a, const int32_t *slot_b, const afv_sim3_job *jobs, int nc,
+                              const int32_t *mp1, const int32_t *mp2, const int32_t *idx1, const int32_t *idx2, int nhyp, int mask_words,
+                              int32_t *n, int32_t *index1, int32_t *count, uint8_t *degenerate, float *sim3, uint32_t *inliers, float *x3dc1,
+                              float *x3dc2, float *max_err);
+
 /* engine of the ordered phase of the projection searches / SearchForInitialization (identical results):
  *   1: one fixed point over all live queries of a job on a 1024-thread workgroup (round 5)   0: the ordered walk of rounds 1-4 on one
  *   wavefront   2 (default): 1 whenever the job's tables fit the workgroup's LDS, else 0   3: as 1, but ranking and ordered phase as two
