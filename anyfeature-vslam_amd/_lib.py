@@ -324,6 +324,7 @@ SYMBOLS = {
     "afv_profile_read": (_i, [_vp, _vp, _vp, _vp]),
     "afv_set_split_threshold": (_i, [_vp, _i]),
     "afv_set_split_chunks": (_i, [_vp, _i]),
+    "afv_set_split_schedule": (_i, [_vp, _i]),
     "afv_set_match_engine": (_i, [_vp, _i]),
     "afv_set_small_batch_path": (_i, [_vp, _i, _i]),
     "afv_set_match_resolve": (_i, [_vp, _i]),

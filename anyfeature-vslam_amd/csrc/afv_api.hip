@@ -210,6 +210,12 @@ extern "C" int afv_set_split_chunks(afv_ctx *c, int chunks) {
     return AFV_OK;
 }
 
+extern "C" int afv_set_split_schedule(afv_ctx *c, int mode) {
+    if (!c || (mode != 0 && mode != 1)) return AFV_EINVAL;
+    c->split_schedule = mode;
+    return AFV_OK;
+}
+
 extern "C" int afv_profile_enable(afv_ctx *c, int enable) {
     if (!c) return AFV_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
@@ -375,10 +381,17 @@ int afv_match_pairs_core(afv_ctx *c, const uint8_t *d_desc, const float *d_ang, 
         HIPCHK(c, hipMalloc(&c->d_topk, need));
         c->topk_bytes = need;
     }
-    if (npairs >= c->split_min_frames) {
-        // grid.y carries the pair index (<= 65535 per launch) and the two streams overlap the latency-bound ordered
-        // resolve of one chunk with the VALU-bound top-k of the other (more, smaller chunks were measured and are slower: 256 frames,
-        // 4 / 6 / 8 chunks: -4 / -9 / -13 %)
+    // Schedule 1 keeps a call of up to 4096 pairs on the caller's stream.  Split over the two streams, the two top-k launches run side by
+    // side at half speed each and so do the two resolves: nothing is hidden, and the fork and the join each leave the chip idle for 10 to
+    // 20 us (kernel trace: profiles/r09/overlap_parent.txt).  Unsplit, the step of bench.py is 0.4 % (512 frames) to 7.6 % (64 frames)
+    // shorter, 0.3 % at 1024 frames, 0.8 % on frames that really overlap (DESIGN_LOG, round 9); a call of 10 000 pairs, where two
+    // hand-offs are nothing beside 3 ms of kernels, was no faster unsplit (3.10 against 3.07 ms, inside its spread) and keeps the split.  All top-k launches on one stream
+    // with the resolves behind events on the other - so that a resolve runs beside the next top-k - was measured too: 2.8 % slower on
+    // unrelated frames, 4 to 6 % on overlapping ones (the lone last resolve and the event hops cost more than the overlap wins).
+    const bool split = npairs >= c->split_min_frames && (c->split_schedule == 0 || npairs > 4096);
+    if (split) {
+        // grid.y carries the pair index (<= 65535 per launch); chunk k, top-k and resolve, on stream k % 2 (more, smaller chunks were
+        // measured and are slower: 256 frames, 4 / 6 / 8 chunks: -4 / -9 / -13 %)
         HIPCHK(c, hipEventRecord(c->ev_fork, s));
         HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
         const int K = std::max(2, (npairs + 32767) / 32768 * 2);

@@ -402,26 +402,31 @@ extern "C" int afv_get_geometry(const afv_ctx *c, afv_geometry *g) {
 // kernels of one contiguous frame range [f0, f0 + nf) on stream s
 // clear_status: this range is the whole call, *d_status is cleared ahead of its kernels (by the one-launch pyramid when there is one)
 // d_desc == nullptr: keypoints only (afv_orb_detect); pyramid_only: nothing behind the pyramid (afv_orb_compute describes given keypoints on it)
+// pyramid_done: an earlier pyramid_only call on this stream has built the pyramid of these frames and cleared their candidate counts, and
+// the caller has cleared d_hq_n[f0] (enqueue_extract, schedule 1): only the kernels behind the pyramid
 static void enqueue_range(afv_ctx *c, const FrameSrc &src, int f0, int nf, afv_keypoint *d_kps, uint8_t *d_desc, int cap, int *d_n,
-                          int *d_status, hipStream_t s, bool clear_status = false, const DescribeMirror *mirror = nullptr, bool pyramid_only = false) {
+                          int *d_status, hipStream_t s, bool clear_status = false, const DescribeMirror *mirror = nullptr, bool pyramid_only = false,
+                          bool pyramid_done = false) {
     const Geo &g = c->geo;
     {   // work lists are indexed with afv_udiv (exact below AFV_MAX_WORK items): longer ranges go out in pieces
         const int per = std::max(std::max(g.total_tiles, afv_describe_blocks_per_frame(&g)), 1);
         const int max_nf = std::max(1, (AFV_MAX_WORK - 8) / per);
         if (nf > max_nf) {
             if (clear_status && d_status) (void)hipMemsetAsync(d_status, 0, sizeof(int), s);
-            for (int b = 0; b < nf; b += max_nf) enqueue_range(c, src, f0 + b, std::min(max_nf, nf - b), d_kps, d_desc, cap, d_n, d_status, s, false, mirror, pyramid_only);
+            for (int b = 0; b < nf; b += max_nf)
+                enqueue_range(c, src, f0 + b, std::min(max_nf, nf - b), d_kps, d_desc, cap, d_n, d_status, s, false, mirror, pyramid_only, pyramid_done);
             return;
         }
     }
     int *cnt0 = c->d_cand_count + (size_t)f0 * AFV_MAX_LEVELS;
-    if (g.nlevels < 2) {  // no pyramid launch to carry the clears
+    if (g.nlevels < 2 && !pyramid_done) {  // no pyramid launch to carry the clears
         (void)hipMemsetAsync(cnt0, 0, (size_t)nf * AFV_MAX_LEVELS * sizeof(int), s);
         (void)hipMemsetAsync(c->d_hq_n + f0, 0, sizeof(int), s);
     }
     const bool small = small_batch_path(c, nf);
     if (clear_status && d_status && !(small && c->pf_ok)) (void)hipMemsetAsync(d_status, 0, sizeof(int), s);
-    if (small && c->pf_ok) {
+    if (pyramid_done) {
+    } else if (small && c->pf_ok) {
         StageTimer t_(c, AFV_STAGE_PYRAMID, s, nf);
         PyrFuseArgs A = c->pf;
         A.zero_counts = cnt0;
@@ -467,16 +472,51 @@ static int enqueue_extract(afv_ctx *c, const FrameSrc &src, int nframes, afv_key
                            int *d_n, int *d_status, hipStream_t s) {
     if (nframes >= c->split_min_frames) {
         if (d_status) HIPCHK(c, hipMemsetAsync(d_status, 0, sizeof(int), s));
-        // two halves on two streams: the select / describe tail of one half overlaps the FAST kernel of the other
+        // Two streams.  What the split buys and what it does not (kernel traces, profiles/r09): two launches that share the chip run at
+        // about half speed each, whatever they are - a FAST launch beside its twin, or beside the other stream's Harris / select launches,
+        // which then wait for the workgroup slots FAST holds (a turnstile that let one FAST launch run at a time took its same-name
+        // overlap from 1.58 to 0 ms per step and stretched k_harris from 0.27 to 0.74 ms: the step was 1.1 % slower).  The split wins where
+        // a kernel alone leaves the chip part empty: the ramp and tail of every launch, the short launches of the small pyramid levels and
+        // the latency-bound select / retain kernels.  It loses at every hand-off between the streams, 10 to 20 us of idle chip each.
         HIPCHK(c, hipEventRecord(c->ev_fork, s));
         HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
         // automatic: chunks of ~85 frames (measured optimum at 640x480: large enough to fill the chip, small enough that the
-        // latency-bound kernels of one chunk hide behind the VALU-bound ones of the next), and an EVEN number of them: an odd
-        // last chunk runs with nothing beside it (256 frames: 2 chunks 1.55 ms, 3 chunks 1.61; 384: 4 chunks 2.25, 5 chunks 2.33)
+        // latency-bound kernels of one chunk run beside other kernels of the other stream), and an EVEN number of them: an odd
+        // last chunk runs with nothing beside it (256 frames: 2 chunks 1.55 ms, 3 chunks 1.61; 384: 4 chunks 2.25, 5 chunks 2.33);
+        // re-measured under schedule 1 (512 frames: 4 / 6 / 8 chunks 2.301 / 2.294 / 2.346 ms per step; 1024: 8 / 12 / 16 chunks
+        // 4.511 / 4.536 / 4.617; 384: 2 / 4 / 6 chunks 1.747 / 1.741 / 1.767): the rule stays
         const int K = c->split_chunks ? c->split_chunks : std::min(64, 2 * std::max(1, (int)((float)nframes / 170.0f + 0.45f)));
-        for (int k = 0; k < K; ++k) {  // chunk k on stream k % 2
-            const int b = (int)((long)nframes * k / K), e = (int)((long)nframes * (k + 1) / K);
-            if (e > b) enqueue_range(c, src, b, e - b, d_kps, d_desc, cap, d_n, d_status, (k & 1) ? c->stream2 : s);
+        if (c->split_schedule == 0) {
+            for (int k = 0; k < K; ++k) {  // chunk k on stream k % 2
+                const int b = (int)((long)nframes * k / K), e = (int)((long)nframes * (k + 1) / K);
+                if (e > b) enqueue_range(c, src, b, e - b, d_kps, d_desc, cap, d_n, d_status, (k & 1) ? c->stream2 : s);
+            }
+        } else {
+            // Schedule 1: frames [0, h) on the caller's stream, [h, nframes) on the second, each as its share of the K chunks, and
+            //  - the pyramid of a stream's whole range first, 7 launches instead of 7 per chunk (the launches of the small levels are
+            //    mostly ramp and tail: 42 launches took 0.30 ms of a 512-frame step, the same levels of the whole batch take 0.24 alone);
+            //  - the caller's stream carries `lead` frames more, so that it ends last: it runs straight on into whatever the caller has
+            //    enqueued behind this call (bench.py: the pair matcher) instead of waiting one hand-off for the second stream, and the
+            //    second stream's late start behind the fork is paid for.  28 frames of 640 x 480 (about 55 us of this pipeline; scaled by
+            //    the pixel count), at most a tenth of the batch: measured optimum of the second stream's share at 64 .. 256 frames 0.45,
+            //    at 512 frames 0.47 (0.49: +0.9 %, 0.45: +0.7 %).
+            const int Ks = (K + 1) / 2, K2 = K / 2;
+            const double px = std::max(1.0, (double)c->geo.width * (double)c->geo.height);
+            const int lead = std::min(nframes / 10, std::max(1, (int)(28.0 * 640.0 * 480.0 / px + 0.5)));
+            const int h = std::min(nframes, (int)(((long)nframes * Ks + K - 1) / K) + (lead + 1) / 2);
+            enqueue_range(c, src, 0, h, d_kps, d_desc, cap, d_n, d_status, s, false, nullptr, true);
+            HIPCHK(c, hipMemsetAsync(c->d_hq_n, 0, (size_t)h * sizeof(int), s));  // every chunk owns the counter of its first frame
+            if (nframes > h) {
+                enqueue_range(c, src, h, nframes - h, d_kps, d_desc, cap, d_n, d_status, c->stream2, false, nullptr, true);
+                HIPCHK(c, hipMemsetAsync(c->d_hq_n + h, 0, (size_t)(nframes - h) * sizeof(int), c->stream2));
+            }
+            for (int k = 0; k < Ks; ++k) {  // host order: the streams' chunks in turn
+                const int b = (int)((long)h * k / Ks), e = (int)((long)h * (k + 1) / Ks);
+                if (e > b) enqueue_range(c, src, b, e - b, d_kps, d_desc, cap, d_n, d_status, s, false, nullptr, false, true);
+                if (k >= K2) continue;
+                const int b2 = h + (int)((long)(nframes - h) * k / K2), e2 = h + (int)((long)(nframes - h) * (k + 1) / K2);
+                if (e2 > b2) enqueue_range(c, src, b2, e2 - b2, d_kps, d_desc, cap, d_n, d_status, c->stream2, false, nullptr, false, true);
+            }
         }
         HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
         HIPCHK(c, hipStreamWaitEvent(s, c->ev_join, 0));

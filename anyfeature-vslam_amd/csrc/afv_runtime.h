@@ -335,7 +335,7 @@ struct afv_points {
 struct afv_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;  // second lane for split batches (latency-bound kernels overlap VALU-bound ones)
+    hipStream_t stream2 = nullptr;  // second lane for split batches (fills the ramps, tails and latency-bound kernels of the first)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipStream_t stream_copy = nullptr;                         // copy lane of the host-buffer batch pipeline (created on first use)
     std::vector<hipEvent_t> pipe_ev;                           // 3 events per chunk in flight
@@ -353,7 +353,9 @@ struct afv_ctx {
     int proj_fuse = 1;             // 1: single-job searches rank and resolve in one launch (afv_set_projection_fuse)
     std::vector<afv_frame *> frames;  // frames alive on this context (destroyed with it)
     std::vector<afv_points *> points; // ... and its map-point stores (afv_points.hip)
-    int split_chunks = 0;          // ... into this many chunks (alternating streams); 0 = about 85 frames each; afv_set_split_chunks
+    int split_chunks = 0;          // ... into this many chunks; 0 = about 85 frames each; afv_set_split_chunks
+    int split_schedule = 1;        // 1: a lane per half of the batch, its pyramid first, the caller's lane ends last; the pair matcher unsplit
+                                   // 0: chunks alternating over the lanes, the matcher split too; afv_set_split_schedule
     // small-batch ("latency") path: kernels shaped for one or a few frames; afv_set_small_batch_path
     int small_mode = 1;            // 0 = never, 1 = batches of at most small_max_frames, 2 = always
     int small_max_frames = 4;

@@ -227,6 +227,12 @@ class Context:
     def set_split_chunks(self, chunks):
         self.check(self.lib.afv_set_split_chunks(self.handle, int(chunks)))
 
+    def set_split_schedule(self, mode):
+        """how a split batch is laid over the two streams: 1 = a contiguous part per stream, its whole pyramid first, the caller's stream a few
+        frames longer so that it ends last, pair-matcher calls unsplit (default); 0 = chunks alternating over the streams, the matcher split
+        too (the earlier schedule, for A/B runs); identical results"""
+        self.check(self.lib.afv_set_split_schedule(self.handle, int(mode)))
+
     @property
     def stream(self):
         """the context's own hipStream_t (what a NULL `stream` argument selects)"""

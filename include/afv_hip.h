@@ -1000,6 +1000,13 @@ int afv_profile_read(afv_ctx *ctx, int32_t *launches /*[afv_num_stages()]*/, flo
 int afv_set_split_threshold(afv_ctx *ctx, int min_frames);
 int afv_set_split_chunks(afv_ctx *ctx, int chunks); /* ... into this many chunks alternating over the two streams (2..64; 0 = automatic,
                                                       * chunks of about 85 frames: the default) */
+/* How the chunks of a split call meet on the two streams; identical results either way.
+ *   1 (default): extraction - the first part of the batch on the caller's stream, the rest on the second; each stream builds the
+ *      pyramid of its whole part first (one launch per level), then runs its share of the chunks; the caller's stream carries slightly
+ *      more frames, so that it ends last and runs on into the caller's next call without waiting for a hand-off.  Pair matcher - a call
+ *      of up to 4096 pairs stays on the caller's stream, one top-k and one resolve launch (larger calls are split as under 0).
+ *   0: chunk k, pyramid included, on stream k % 2, the pair matcher split the same way (the schedule of earlier releases, kept for A/B runs) */
+int afv_set_split_schedule(afv_ctx *ctx, int mode);
 /* afv_match_l2_pairs_device processes its jobs in launches of at most `pairs` jobs (default 2048; the key scratch of a launch is
  * pairs x cap x 32 bytes and is reused by the next launch on the same stream) */
 int afv_set_l2_chunk_pairs(afv_ctx *ctx, int pairs);
