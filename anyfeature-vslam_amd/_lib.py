@@ -151,6 +151,28 @@ class Sim3Job(C.Structure):
 
 
 SIM3_MAX_CANDIDATES, SIM3_MAX_HYPOTHESES, SIM3_MAX_MASK_WORDS = 64, 1024, 256
+
+
+class InitJob(C.Structure):
+    """afv_init_job: the constants of one afv_frame_initializer call"""
+    _fields_ = ([("struct_size", C.c_uint32), ("iterations", C.c_int32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)] +
+                [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "sigma")])
+
+
+INIT_MAX_ITERATIONS, INIT_MAX_MOTIONS, INIT_MAX_MASK_WORDS = 1024, 8, 256
+INIT_ROUTE_H, INIT_ROUTE_F = 0, 1
+INIT_REASON = ("ok", "too_few_matches", "d_ratio", "ambiguous", "parallax", "min_triangulated", "min_good")
+
+
+class InitTrace(C.Structure):
+    """afv_init_trace: what afv_frame_initializer decided on the way"""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("sh", C.c_float), ("sf", C.c_float), ("rh", C.c_float),
+                ("best_h", C.c_int32), ("best_f", C.c_int32), ("h21", C.c_float * 9), ("f21", C.c_float * 9), ("route", C.c_int32),
+                ("n_inliers", C.c_int32), ("n_motion", C.c_int32), ("best_motion", C.c_int32), ("reason", C.c_int32),
+                ("n_good", C.c_int32 * INIT_MAX_MOTIONS), ("cos_parallax", C.c_float * INIT_MAX_MOTIONS),
+                ("R", (C.c_float * 9) * INIT_MAX_MOTIONS), ("t", (C.c_float * 3) * INIT_MAX_MOTIONS), ("T1", C.c_float * 9), ("T2", C.c_float * 9)]
+
+
 TRI_MAX_PAIRS = 64
 TRI_STATUS = ("no_match", "accepted", "low_parallax", "w_zero", "z1", "z2", "reproj1", "reproj2", "zero_dist", "scale_ratio", "not_finite")
 TRI_ROUTE = ("triangulated", "unproject_a", "unproject_b")
@@ -284,6 +306,8 @@ SYMBOLS = {
                                          _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_table_sim3_hypotheses": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Sim3Job), _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp]),
+    "afv_frame_initializer": (_i, [_vp, _vp, C.POINTER(InitJob), _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp,
+                                   C.POINTER(InitTrace), _vp, _vp, _vp, _vp, _i]),
     "afv_vocab_set_weights": (_i, [_vp, _vp, _vp, _vp]),
     "afv_bow_vector": (_i, [_vp, _vp, _vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_frame_get_bowvec": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),

@@ -27,6 +27,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <algorithm>
+#include <array>
 #include <exception>
 #include <functional>
 #include <map>
@@ -1350,6 +1351,54 @@ class Sim3Solver {
     std::vector<uint8_t> degenerate;      // S5 flags per hypothesis
     std::vector<float> sim3;              // [nhyp][13]: R12 row-major, t12, s12
     std::vector<uint32_t> inliers;        // [nhyp][words]
+};
+
+// ---- Initializer (include/Initializer.h, src/Initializer.cc) as Tracking::MonocularInitialization uses it (src/Tracking.cc:455, :487):
+// built on the reference frame, asked once per current frame with the matches of SearchForInitialization.  Initialize makes ONE
+// afv_frame_initializer call - the H and F RANSAC over all iterations, the selection, the motion hypotheses and CheckRT run on the device
+// (include/afv_hip.h, "Initializer": the quirks, deviations I1-I11) - and returns what the reference returns.  The reference's constructor
+// reads K from the frame; a DeviceFrame does not hold K, so it is handed over.  R21 is 9 floats row-major, t21 3 floats (mat3f / vec3f in
+// the reference), a point of vP3D 3 floats.
+class Initializer {
+  public:
+    Initializer(DeviceFrame &ReferenceFrame, float fx, float fy, float cx, float cy, float sigma = 1.0f, int iterations = 200, uint64_t seed = 0)
+        : ref(ReferenceFrame) {
+        std::memset(&job, 0, sizeof(job));
+        job.struct_size = (uint32_t)sizeof(afv_init_job);
+        job.iterations = iterations;
+        job.seed_lo = (uint32_t)seed; job.seed_hi = (uint32_t)(seed >> 32);
+        job.fx = fx; job.fy = fy; job.cx = cx; job.cy = cy; job.sigma = sigma;
+        std::memset(&trace, 0, sizeof(trace));
+    }
+
+    // :41-114.  vMatches12: one entry per feature of the reference frame (the current frame's feature | -1).  vP3D / vbTriangulated get one
+    // entry per feature of the reference frame; on false they read 0 / false (the reference leaves them untouched)
+    bool Initialize(DeviceFrame &CurrentFrame, const std::vector<int> &vMatches12, float (&R21)[9], float (&t21)[3],
+                    std::vector<std::array<float, 3>> &vP3D, std::vector<bool> &vbTriangulated) {
+        const size_t n1 = vMatches12.size();
+        std::vector<int32_t> m(vMatches12.begin(), vMatches12.end());
+        std::vector<float> p3d(3 * std::max<size_t>(n1, 1));
+        std::vector<uint8_t> tri(std::max<size_t>(n1, 1));
+        int32_t ok = 0;
+        trace.struct_size = (uint32_t)sizeof(afv_init_trace);
+        const int rc = afv_frame_initializer(ref.handle(), CurrentFrame.handle(), &job, m.data(), &ok, &route, R21, t21, p3d.data(), tri.data(),
+                                             &trace, nullptr, nullptr, nullptr, nullptr, 0);
+        if (rc != AFV_OK) fatal("afv_frame_initializer", rc, nullptr);
+        vP3D.resize(n1);
+        vbTriangulated.assign(n1, false);
+        for (size_t i = 0; i < n1; ++i) {
+            vP3D[i] = {p3d[3 * i], p3d[3 * i + 1], p3d[3 * i + 2]};
+            vbTriangulated[i] = tri[i] != 0;
+        }
+        return ok != 0;
+    }
+
+    afv_init_job job;      // iterations, seed, K, sigma: change between calls at will
+    afv_init_trace trace;  // what the last Initialize decided on the way (cosines, not degrees: I6)
+    int32_t route = AFV_INIT_ROUTE_F;
+
+  private:
+    DeviceFrame &ref;
 };
 
 }  // namespace afv

@@ -224,6 +224,35 @@ struct DevSim3Args {         // a kernel argument of both launches
 extern "C" void afv_launch_sim3_gather(const DevSim3Args *args, hipStream_t stream);
 extern "C" void afv_launch_sim3_hypotheses(const DevSim3Args *args, hipStream_t stream);
 
+// ---- k_init.hip: Initializer::Initialize between two resident frames (host side: afv_init.hip) ----
+#define AFV_INIT_PREP_T 256  // lanes of k_init_prepare (I5: the width of Normalize's partial sums)
+#define AFV_INIT_REC_T 512   // lanes of k_init_reconstruct: 8 wavefronts over the 8 motion hypotheses of H or the 4 of F
+struct DevInitArgs {         // a kernel argument of the three launches
+    const float *x1, *y1, *x2, *y2;  // mvKeysUn of the two frames, read in place
+    int n1, n2;
+    const int *matches12;    // [n1]
+    int iterations, mask_words;      // mask_words: what the host's count of the matches needs, at least 1
+    unsigned long long seed;
+    float fx, fy, cx, cy, sigma;
+    int *n;                  // N
+    int *pairs;              // [n1][2] (i1, i2) in ascending i1
+    float *norm;             // [2][4] meanX, meanY, sX, sY of frame 1, frame 2
+    int *sets;               // [iterations][8]
+    float *score;            // [2][iterations]
+    float *model;            // [2][iterations][9]
+    uint8_t *degenerate;     // [2][iterations]
+    uint32_t *inliers;       // [2][iterations][mask_words]
+    float *cosv;             // [8][n1] CheckRT's cosines by match
+    float *p3dk;             // [8][n1][3] its points by match
+    uint8_t *status;         // [8][n1] by match: bit 0 pushed (counted in nGood), bit 1 isGood
+    afv_init_trace *trace;
+    int *answer;             // ok, route
+    float *Rt;               // R21[9], t21[3]
+    float *p3d;              // [n1][3]
+    uint8_t *triangulated;   // [n1]
+};
+extern "C" void afv_launch_init(const DevInitArgs *args, hipStream_t stream);
+
 // ---- k_poseopt.hip: Optimizer::PoseOptimization on a resident frame (host side: afv_poseopt.hip) ----
 struct DevPoseOut {          // what the workgroup of a job leaves
     float R[9], t[3];

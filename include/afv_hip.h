@@ -885,6 +885,84 @@ int afv_table_sim3_hypotheses(afv_table *t, afv_points *points, const int32_t *s
                               int32_t *n, int32_t *index1, int32_t *count, uint8_t *degenerate, float *sim3, uint32_t *inliers, float *x3dc1,
                               float *x3dc2, float *max_err);
 
+/* ---- Initializer: monocular start-up between two resident frames (src/Initializer.cc:41-908, as Tracking::MonocularInitialization calls
+ * it, src/Tracking.cc:487).  One synchronous call does what Initializer::Initialize does, from matches12 (what
+ * afv_frame_match_initialization answers) to (R21, t21, vP3D, vbTriangulated): one upload, three launches on the context's stream, one
+ * wait (csrc/k_init.hip: k_init_prepare - ordered compaction of the matches, Normalize of both frames over ALL their keypoints, the
+ * 8-sets of every iteration; k_init_hypotheses - one wavefront per (model, iteration): ComputeH21 / ComputeF21, de-normalisation,
+ * CheckHomography / CheckFundamental over all N matches; k_init_reconstruct - selection, RH, the 8 motion hypotheses of ReconstructH or
+ * the 4 of ReconstructF, CheckRT with one or two wavefronts per motion hypothesis, the accept / reject rules).  Only the mvKeysUn planes of the
+ * two frames are read: frames of every descriptor kind and width are accepted.
+ * The normative semantics are tests/_init_ref.py; the device is held to it bit for bit - parity with a build of the reference is
+ * unpinned (it uses Eigen::JacobiSVD<float> and its own random generator).  Float arithmetic, one rounding per operator, a three-term
+ * sum as a0 + (a1 + a2), other scalar expressions left to right as written, A * B * C = (A * B) * C, det3 / inv3 by cofactors.
+ * Quirks restated as written: CheckFundamental gates on 3.841 and scores with 5.991; CheckRT counts in nGood (and writes p3d for) points
+ * that fail cosParallax < minCos while isGood stays false; ReconstructF's else-if chain tests only the first hypothesis equal to
+ * maxGood; RH is NaN when both scores are 0 and goes to ReconstructF; ReconstructF counts inliers in a float, ReconstructH in an int.
+ * Deliberate deviations:
+ *   I1  the DLT null vector: M = A^T A in double (running sums over the rows), a cyclic Jacobi on the symmetric 9 x 9 in double, pairs
+ *       (0,1) (0,2) .. (7,8), + - * / sqrt only, at most 30 sweeps, the skip and stop rules and the rotation of S2; the column of V of the
+ *       smallest diagonal entry (ties: lowest index), rounded to float.  It replaces Eigen::JacobiSVD
+ *   I2  svd3 (the rank-2 step, DecomposeE, ReconstructH): V from the same Jacobi on the 3 x 3 A^T A, columns ordered by descending
+ *       eigenvalue (for i in 0, 1: for k in i + 1 .. 2: swap when d_i < d_k); b_k = A v_k, w_k = |b_k|, u_0 = b_0 / w_0, u_1 = b_1 / w_1,
+ *       u_2 = u_0 x u_1, v_2 negated when b_2 . u_2 < 0; all in double, then rounded to float
+ *   I3  ReconstructH negates A = K^-1 H21 K when det3(A) < 0: the sign of H21 reaches no output (that of F21 does not either: I2)
+ *   I4  draws: key_h = sm(sm(seed) ^ (h + 1)), draw d in 0..7 = sm(key_h + (d + 1) * 0xD1342543DE82EF95) % (N - d), applied to
+ *       availableIndices with the reference's swap-with-back (:83-89); H and F share the sets
+ *   I5  fixed-shape sums.  Normalize: 256 partial sums (partial t adds elements t, t + 256, .. in ascending order), then p[t] += p[t + s]
+ *       for s = 128 .. 1.  The scores: a match contributes e = c1 + c2 (c = th - chiSquare where the gate passes, else 0), 64 partial
+ *       sums over the matches l, l + 64, .., the same halving tree from s = 32
+ *   I6  no acosf: parallax > / >= minParallax is cos < / <= float(cos(1 degree)) on the min(50, n - 1)-th smallest cosine; nGood == 0
+ *       reads cosine 1, ReconstructH's initial bestParallax = -1 reads cosine 2.  The trace carries cosines
+ *   I7  N < 8: nothing is evaluated, ok = 0, reason AFV_INIT_TOO_FEW_MATCHES, every per-hypothesis output reads 0
+ *   I8  a hypothesis is degenerate when the second-smallest diagonal entry of the converged 9 x 9 is <= 1e-12 times the largest (repeated
+ *       or collinear points), or an entry of H21, H12 or F21 is not finite: it scores 0, is flagged, its model record and inlier words
+ *       read 0.  A match whose chiSquare is not finite fails that gate and contributes 0
+ *   I9  no hypothesis of a model scores above 0: the model is all zeros with no inliers, its winning index is -1
+ *   I10 CheckRT skips a point with x3Dh(3) == 0 or a cosParallax that is not finite like a point that is not finite
+ *   I11 on ok = 0, R21, t21, p3d and triangulated read 0; on ok = 1 the p3d rows CheckRT did not write read 0
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(afv_init_job) */
+    int32_t iterations;                      /* maxIterations, 1 .. AFV_INIT_MAX_ITERATIONS */
+    uint32_t seed_lo, seed_hi;               /* the 64-bit seed of I4 */
+    float fx, fy, cx, cy;                    /* K of the reference frame */
+    float sigma;                             /* sigmaInitializer */
+} afv_init_job;
+#define AFV_INIT_MAX_ITERATIONS 1024
+#define AFV_INIT_MAX_MOTIONS 8
+#define AFV_INIT_MAX_MASK_WORDS 256 /* mask_words 0 .. 256: the largest frame (8192 features) needs 256 */
+enum { AFV_INIT_ROUTE_H = 0, AFV_INIT_ROUTE_F = 1 };
+enum { AFV_INIT_OK = 0, AFV_INIT_TOO_FEW_MATCHES, AFV_INIT_D_RATIO, AFV_INIT_AMBIGUOUS, AFV_INIT_PARALLAX, AFV_INIT_MIN_TRIANGULATED,
+       AFV_INIT_MIN_GOOD };
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(afv_init_trace), set by the caller */
+    int32_t n;                               /* N, the number of matches */
+    float sh, sf, rh;                        /* SH, SF, RH = SH / (SH + SF) */
+    int32_t best_h, best_f;                  /* the winning iteration of each model, -1 = none (I9) */
+    float h21[9], f21[9];                    /* the winning models, row-major */
+    int32_t route;                           /* AFV_INIT_ROUTE_H / _F: which reconstruction ran */
+    int32_t n_inliers;                       /* inliers of that model */
+    int32_t n_motion;                        /* motion hypotheses built: 8, 4, or 0 (N < 8, dRatio) */
+    int32_t best_motion;                     /* the accepted one, -1 = none */
+    int32_t reason;                          /* AFV_INIT_OK or why the answer is false */
+    int32_t n_good[AFV_INIT_MAX_MOTIONS];    /* CheckRT's nGood */
+    float cos_parallax[AFV_INIT_MAX_MOTIONS]; /* the selected cosine (I6) */
+    float R[AFV_INIT_MAX_MOTIONS][9], t[AFV_INIT_MAX_MOTIONS][3];
+    float T1[9], T2[9];                      /* Normalize's T of both frames */
+} afv_init_trace;
+/* f1 = the reference frame (N1 = its feature count), f2 = the current frame (N2); matches12[N1] = feature of f2 | -1.  Outputs (host):
+ * *ok, *route, R21[9] row-major, t21[3], p3d[N1][3], triangulated[N1]; optional: trace, hyp_score[2][iterations] (0 = H, 1 = F),
+ * hyp_model[2][iterations][9], hyp_degenerate[2][iterations], hyp_inliers[2][iterations][mask_words] (bit k of a row = match k in
+ * ascending i1, unused bits 0).
+ * Refused before any launch, nothing written: AFV_EINVAL for NULL f1 / f2 / job / ok / route / R21 / t21, NULL matches12 / p3d /
+ * triangulated when N1 > 0, frames of different contexts or without features (a distorted frame without afv_frame_set_undistorted),
+ * iterations out of range, an unknown struct_size (job or trace), a matches12[i] outside [-1, N2), sigma, fx or fy not finite or
+ * <= 0, cx or cy not finite, mask_words outside 0 .. AFV_INIT_MAX_MASK_WORDS, mask_words * 32 < N when hyp_inliers is given. */
+int afv_frame_initializer(afv_frame *f1, afv_frame *f2, const afv_init_job *job, const int32_t *matches12, int32_t *ok, int32_t *route,
+                          float *R21, float *t21, float *p3d, uint8_t *triangulated, afv_init_trace *trace, float *hyp_score,
+                          float *hyp_model, uint8_t *hyp_degenerate, uint32_t *hyp_inliers, int mask_words);
+
 /* engine of the ordered phase of the projection searches / SearchForInitialization (identical results):
  *   1: one fixed point over all live queries of a job on a 1024-thread workgroup (round 5)   0: the ordered walk of rounds 1-4 on one
  *   wavefront   2 (default): 1 whenever the job's tables fit the workgroup's LDS, else 0   3: as 1, but ranking and ordered phase as two
