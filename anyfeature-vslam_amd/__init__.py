@@ -12,6 +12,7 @@ Layout:
   points.py      the device-resident map-point store (reference: MapPoint.{h,cc} as far as the projection searches read it)
   database.py    KeyFrameDatabase mirror over the keyframe table (reference: KeyFrameDatabase.{h,cc}, LoopClosing.cc:137-157)
   sim3.py        Sim3Solver mirror: all RANSAC hypotheses of a loop check in one device call (reference: Sim3Solver.{h,cc})
+  pnp.py         PnPsolver mirror: all EPnP RANSAC hypotheses of a relocalisation in one device call (reference: PnPsolver.{h,cc})
   initializer.py Initializer mirror: H and F RANSAC and the reconstruction in one device call (reference: Initializer.{h,cc})
   synth.py       bit-reproducible synthetic inputs
 """
@@ -25,6 +26,7 @@ from . import akaze, table  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
 from .sim3 import Sim3Solver  # noqa: F401
 from .initializer import Initializer  # noqa: F401
+from .pnp import PnPsolver  # noqa: F401
 from .akaze import AkazeContext  # noqa: F401
 from .matcher import (FeatureMatcher, FeatureView, FrameGridView, ProjectionQueries, ComputeDistinctiveDescriptors,  # noqa: F401
                       DescriptorDistance_orb32, DescriptorDistance_sift128)

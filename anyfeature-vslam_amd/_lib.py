@@ -153,6 +153,15 @@ class Sim3Job(C.Structure):
 SIM3_MAX_CANDIDATES, SIM3_MAX_HYPOTHESES, SIM3_MAX_MASK_WORDS = 64, 1024, 256
 
 
+class PnpJob(C.Structure):
+    """afv_pnp_job: one candidate of afv_frame_pnp_hypotheses"""
+    _fields_ = [("struct_size", C.c_uint32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("min_inliers", C.c_int32),
+                ("epsilon", C.c_float), ("th2", C.c_float)]
+
+
+PNP_MAX_CANDIDATES, PNP_MAX_HYPOTHESES, PNP_MAX_MASK_WORDS = 64, 1024, 256
+
+
 class InitJob(C.Structure):
     """afv_init_job: the constants of one afv_frame_initializer call"""
     _fields_ = ([("struct_size", C.c_uint32), ("iterations", C.c_int32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32)] +
@@ -308,6 +317,7 @@ SYMBOLS = {
                                        _vp, _vp, _vp]),
     "afv_frame_initializer": (_i, [_vp, _vp, C.POINTER(InitJob), _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp,
                                    C.POINTER(InitTrace), _vp, _vp, _vp, _vp, _i]),
+    "afv_frame_pnp_hypotheses": (_i, [_vp, _vp, C.POINTER(PnpJob), _i, _vp, _i, _i] + [_vp] * 13),
     "afv_vocab_set_weights": (_i, [_vp, _vp, _vp, _vp]),
     "afv_bow_vector": (_i, [_vp, _vp, _vp, _i, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_frame_get_bowvec": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int32)]),

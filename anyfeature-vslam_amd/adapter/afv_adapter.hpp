@@ -1353,6 +1353,153 @@ class Sim3Solver {
     std::vector<uint32_t> inliers;        // [nhyp][words]
 };
 
+// ---- PnPsolver (include/PnPsolver.h, src/PnPsolver.cc) as Tracking::Relocalization uses it (src/Tracking.cc:1190-1216): Batch makes ONE
+// afv_frame_pnp_hypotheses call for all candidates of a relocalisation - every solver's constructor, every EPnP RANSAC hypothesis and the
+// Refine of every record run on the device (include/afv_hip.h, "PnPsolver": quirks Q1-Q6, deviations E1-E10) - and returns one solver per
+// candidate.  iterate / find are host code over the per-hypothesis counts, poses and inlier words: hypothesis h depends on (seed, h) alone
+// and Refine reads only the best set, which changes only at a record, so the reference's sequential rule is a scan.  Tcw is 16 floats
+// row-major (cv::Mat 4 x 4 CV_32F in the reference).
+class PnPsolver {
+  public:
+    // F: the current frame with its features and a pose (the intrinsics are the frame's); pts[c]: vvpMapPointMatches of candidate c as
+    // point ids, one per feature of F, -1 = none; minInliers / epsilon / th2: what SetRansacParameters will be given; candidate c draws
+    // from seed + c
+    static std::vector<PnPsolver> Batch(afv_ctx *ctx, DeviceFrame &F, int nf, DeviceMapPoints &points, const std::vector<std::vector<int32_t>> &pts,
+                                        uint64_t seed = 0, int nhyp = 300, int minInliers = 10, float epsilon = 0.5f, float th2 = 5.991f) {
+        const size_t nc = pts.size(), cells = nc * (size_t)nf, hyps = nc * (size_t)nhyp;
+        const int words = (nf + 31) / 32;
+        std::vector<afv_pnp_job> jobs(nc);
+        std::vector<int32_t> rows(cells, -1);
+        for (size_t c = 0; c < nc; ++c) {
+            afv_pnp_job &j = jobs[c];
+            std::memset(&j, 0, sizeof(j));
+            j.struct_size = (uint32_t)sizeof(afv_pnp_job);
+            const uint64_t s = seed + c;
+            j.seed_lo = (uint32_t)s; j.seed_hi = (uint32_t)(s >> 32);
+            j.min_inliers = minInliers; j.epsilon = epsilon; j.th2 = th2;
+            for (int i = 0; i < nf; ++i) rows[c * (size_t)nf + (size_t)i] = pts[c][(size_t)i];
+        }
+        std::vector<int32_t> n(nc), nmin(nc), index(cells), count(hyps), rcount(hyps);
+        std::vector<uint8_t> degenerate(hyps), refined(hyps);
+        std::vector<float> pose(hyps * 12), rpose(hyps * 12);
+        std::vector<uint32_t> inliers(hyps * (size_t)words), rinliers(hyps * (size_t)words);
+        const int rc = afv_frame_pnp_hypotheses(F.handle(), points.handle(), jobs.data(), (int)nc, rows.data(), nhyp, words, n.data(), nmin.data(),
+                                                index.data(), count.data(), degenerate.data(), pose.data(), inliers.data(), refined.data(),
+                                                rcount.data(), rpose.data(), rinliers.data(), nullptr, nullptr);
+        if (rc != AFV_OK) fatal("afv_frame_pnp_hypotheses", rc, ctx);
+        std::vector<PnPsolver> out;
+        for (size_t c = 0; c < nc; ++c) {
+            PnPsolver s;
+            s.N = n[c]; s.nf = nf; s.nhyp = nhyp; s.words = words; s.device_min_inliers = nmin[c];
+            s.given_min = minInliers; s.given_eps = epsilon; s.given_th2 = th2;
+            const long h0 = (long)(c * (size_t)nhyp), h1 = (long)((c + 1) * (size_t)nhyp);
+            s.index.assign(index.begin() + (long)(c * (size_t)nf), index.begin() + (long)(c * (size_t)nf) + s.N);
+            s.count.assign(count.begin() + h0, count.begin() + h1);
+            s.degenerate.assign(degenerate.begin() + h0, degenerate.begin() + h1);
+            s.refined.assign(refined.begin() + h0, refined.begin() + h1);
+            s.refined_count.assign(rcount.begin() + h0, rcount.begin() + h1);
+            s.pose.assign(pose.begin() + h0 * 12, pose.begin() + h1 * 12);
+            s.refined_pose.assign(rpose.begin() + h0 * 12, rpose.begin() + h1 * 12);
+            s.inliers.assign(inliers.begin() + h0 * words, inliers.begin() + h1 * words);
+            s.refined_inliers.assign(rinliers.begin() + h0 * words, rinliers.begin() + h1 * words);
+            if (!s.SetRansacParameters(0.99, minInliers, std::min(300, nhyp), 4, epsilon, th2))
+                fatal("PnPsolver::Batch: the device's mRansacMinInliers is not the host's", AFV_EINVAL, ctx);
+            out.push_back(std::move(s));
+        }
+        return out;
+    }
+
+    // :121-157 (Q2): host mathematics only.  false (nothing changes): minInliers, epsilon or th2 differ from what the device call was
+    // given, minSet != 4, or maxIterations beyond the evaluated hypotheses
+    bool SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4f,
+                             float th2 = 5.991f) {
+        if (minInliers != given_min || epsilon != given_eps || th2 != given_th2 || minSet != 4 || maxIterations > nhyp) return false;
+        const float prod = (float)N * epsilon;  // :134, the product in float, truncated
+        int nMinInliers = !(prod < 2147483648.0f) ? 2147483647 : (int)prod;
+        nMinInliers = std::max(std::max(nMinInliers, minInliers), minSet);
+        if (nMinInliers != device_min_inliers) return false;
+        mRansacProb = probability;
+        mRansacMinInliers = nMinInliers;
+        mRansacEpsilon = epsilon;
+        if (mRansacEpsilon < (float)mRansacMinInliers / N) mRansacEpsilon = (float)mRansacMinInliers / N;
+        double v = 1.0;
+        if (mRansacMinInliers != N) v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)mRansacEpsilon, 3.0)));
+        // a double outside int's range is undefined in the reference: here it saturates and a NaN reads maxIterations
+        nIterationsWanted = maxIterations;
+        if (v == v) nIterationsWanted = v >= 2147483647.0 ? 2147483647 : (v <= -2147483648.0 ? (-2147483647 - 1) : (int)v);
+        mRansacMaxIts = std::max(1, std::min(nIterationsWanted, maxIterations));
+        return true;
+    }
+
+    // :165-258.  Tcw: 16 floats when the return value is true.  A scan that would visit a hypothesis the device did not evaluate is fatal
+    bool iterate(int nIterations, bool &bNoMore, std::vector<bool> &vbInliers, int &nInliers, float *Tcw) {
+        bNoMore = false;
+        vbInliers.assign((size_t)nf, false);
+        nInliers = 0;
+        if (N < mRansacMinInliers) {
+            bNoMore = true;
+            return false;
+        }
+        int nCurrentIterations = 0;
+        while (mnIterations < mRansacMaxIts || nCurrentIterations < nIterations) {  // Q1
+            if (mnIterations >= nhyp) fatal("PnPsolver::iterate: a hypothesis the device did not evaluate", AFV_EINVAL, nullptr);
+            nCurrentIterations++;
+            const int h = mnIterations++;
+            const int c = count[(size_t)h];  // a degenerate hypothesis counts 0 and still advances mnIterations
+            if (c >= mRansacMinInliers) {
+                if (c > mnBestInliers) {  // a record
+                    mnBestInliers = c;
+                    best = h;
+                }
+                // Q4: Refine on the best set so far; the device evaluated it at the record
+                if (refined[(size_t)best] == 1 && refined_count[(size_t)best] > mRansacMinInliers) {
+                    answer(refined_pose.data() + (size_t)best * 12, refined_inliers.data() + (size_t)best * (size_t)words, vbInliers, Tcw);
+                    nInliers = refined_count[(size_t)best];
+                    return true;
+                }
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) {
+            bNoMore = true;
+            if (mnBestInliers >= mRansacMinInliers) {  // Q3: the unrefined best
+                answer(pose.data() + (size_t)best * 12, inliers.data() + (size_t)best * (size_t)words, vbInliers, Tcw);
+                nInliers = mnBestInliers;
+                return true;
+            }
+        }
+        return false;
+    }
+
+    bool find(std::vector<bool> &vbInliers, int &nInliers, float *Tcw) {  // :159-163
+        bool flag;
+        return iterate(mRansacMaxIts, flag, vbInliers, nInliers, Tcw);
+    }
+
+    int N = 0, nf = 0, nhyp = 0, words = 0, device_min_inliers = 0;
+    int mnIterations = 0, mnBestInliers = 0, best = -1;
+    int mRansacMinInliers = 8, mRansacMaxIts = 300, nIterationsWanted = 0;
+    double mRansacProb = 0.99;
+    float mRansacEpsilon = 0.4f;
+    std::vector<int32_t> index, count, refined_count;  // mvKeyPointIndices; inliers per hypothesis; of its refinement
+    std::vector<uint8_t> degenerate, refined;          // E8 flags; 0 no record, 1 refined, 2 record whose refinement is degenerate
+    std::vector<float> pose, refined_pose;             // [nhyp][12]: Rcw row-major, tcw
+    std::vector<uint32_t> inliers, refined_inliers;    // [nhyp][words]
+
+  private:
+    void answer(const float *p, const uint32_t *w, std::vector<bool> &vbInliers, float *Tcw) const {
+        for (int i = 0; i < N; ++i)
+            if ((w[i >> 5] >> (i & 31)) & 1u) vbInliers[(size_t)index[(size_t)i]] = true;
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 3; ++b) Tcw[4 * a + b] = p[3 * a + b];
+            Tcw[4 * a + 3] = p[9 + a];
+        }
+        Tcw[12] = Tcw[13] = Tcw[14] = 0.0f;
+        Tcw[15] = 1.0f;
+    }
+    int given_min = 0;
+    float given_eps = 0.0f, given_th2 = 0.0f;
+};
+
 // ---- Initializer (include/Initializer.h, src/Initializer.cc) as Tracking::MonocularInitialization uses it (src/Tracking.cc:455, :487):
 // built on the reference frame, asked once per current frame with the matches of SearchForInitialization.  Initialize makes ONE
 // afv_frame_initializer call - the H and F RANSAC over all iterations, the selection, the motion hypotheses and CheckRT run on the device

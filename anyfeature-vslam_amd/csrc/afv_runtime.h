@@ -253,6 +253,36 @@ struct DevInitArgs {         // a kernel argument of the three launches
 };
 extern "C" void afv_launch_init(const DevInitArgs *args, hipStream_t stream);
 
+// ---- k_pnp.hip: PnPsolver's constructor, all its EPnP RANSAC hypotheses and the refinement of every record (host side: afv_pnp.hip) ----
+#define AFV_PNP_T 256        // lanes per workgroup of k_pnp_gather
+struct DevPnpCand {          // one candidate: the caller's record
+    unsigned long long seed;
+    int min_inliers;
+    float epsilon, th2;
+    int pad;
+};
+struct DevPnpArgs {          // a kernel argument of the three launches
+    const DevPnpCand *cands;
+    const int *pts;          // [nc][nf] point id | -1
+    int nc, nf, nhyp, mask_words;
+    const float *x, *y, *sigma2;  // the frame: mvKeysUn and the sigma2 plane over nf features, read in place
+    float fx, fy, cx, cy;
+    const float *pos[3];     // the store: XYZ planes and flags over `pcap` ids
+    const uint8_t *flags;
+    int pcap;
+    int *n, *min_inliers, *index;  // [nc], [nc], [nc][nf]
+    float *p2d, *p3dw, *max_err;   // [nc][nf][2], [nc][nf][3], [nc][nf]
+    int *count;              // [nc][nhyp]
+    uint8_t *degenerate;     // [nc][nhyp]
+    float *pose;             // [nc][nhyp][12]
+    uint32_t *inliers;       // [nc][nhyp][mask_words]
+    uint8_t *refined;        // [nc][nhyp]
+    int *refined_count;
+    float *refined_pose;
+    uint32_t *refined_inliers;
+};
+extern "C" void afv_launch_pnp(const DevPnpArgs *args, hipStream_t stream);
+
 // ---- k_poseopt.hip: Optimizer::PoseOptimization on a resident frame (host side: afv_poseopt.hip) ----
 struct DevPoseOut {          // what the workgroup of a job leaves
     float R[9], t[3];

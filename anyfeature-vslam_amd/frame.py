@@ -388,6 +388,12 @@ class Frame:
                             lam=np.array(r.lambda_, np.float64)))
         return out
 
+    def PnPsolverBatch(self, points, pts_rows, **kw):
+        """PnPsolver.batch on this frame (the relocalisation loop, Tracking.cc:1190-1216: one solver per candidate keyframe, one device
+        call for all of them); a successful iterate gives the initial pose and the pts of a PoseOptimizationBatch job"""
+        from .pnp import PnPsolver
+        return PnPsolver.batch(self, points, pts_rows, **kw)
+
     def PoseOptimization(self, points, pts, set_pose=True):
         """Optimizer::PoseOptimization(&frame) (Optimizer.cc:245-448): pts[i] = the id of the map point of feature i | -1.  Returns
         (nGood, mvbOutlier [N] bool, Tcw 4 x 4).  set_pose: pFrame->SetPose(Tcw) (:445) - the optimised pose goes to set_pose with

@@ -963,6 +963,78 @@ int afv_frame_initializer(afv_frame *f1, afv_frame *f2, const afv_init_job *job,
                           float *R21, float *t21, float *p3d, uint8_t *triangulated, afv_init_trace *trace, float *hyp_score,
                           float *hyp_model, uint8_t *hyp_degenerate, uint32_t *hyp_inliers, int mask_words);
 
+/* ---- PnPsolver: all EPnP RANSAC hypotheses of a relocalisation at once (src/PnPsolver.cc:67-950, as Tracking::Relocalization uses it,
+ * src/Tracking.cc:1190-1216).  Per candidate keyframe the constructor (the filter over vpMapPointMatches, mvP2D, mvP3Dw, mvMaxError,
+ * mRansacMinInliers), EVERY hypothesis h < nhyp (four draws, EPnP on them, CheckInliers over all N correspondences) and the Refine of
+ * every RECORD run on the device: one upload, three launches and ONE wait per call whatever the number of candidates (csrc/k_pnp.hip:
+ * k_pnp_gather, one workgroup per candidate; k_pnp_hypotheses and k_pnp_refine, one wavefront per (candidate, hypothesis)).
+ * Hypothesis h depends on (seed, h) alone.  Refine reads only mvbBestInliers, which changes only at a record: h is a record when
+ * count[h] >= min_inliers and count[h] > count[g] for every g < h.  A Refine called at a later hypothesis that is no record repeats the
+ * last record's computation, so the device evaluates it once per record and PnPsolver::iterate is a scan over count[] that the host does
+ * exactly (afv::PnPsolver of the adapter, PnPsolver of the Python package): at a hypothesis with count >= min_inliers it answers the refined pose of the current record
+ * when that record's refined count is > min_inliers.
+ * It reads the frame's mvKeysUn and sigma2 planes, XYZ and the flags of the store and the intrinsics given with afv_frame_set_pose.
+ * The normative semantics are tests/_pnp_ref.py; the device is held to it bit for bit - parity with a build of the reference is
+ * unpinned (it links OpenCV's legacy cvSVD / cvSolve / cvInvert).  EPnP runs in double, one rounding per operator, scalar expressions
+ * left to right as written.
+ * Quirks restated as written:
+ *   Q1  the `||` of iterate's loop condition: a call runs until mnIterations >= mRansacMaxIts AND its own count >= nIterations (host)
+ *   Q2  pow(epsilon, 3) with a minimal set of 4 (host)
+ *   Q3  the best is updated on >, the early answer is given on refined count > min_inliers, the final answer on best >= min_inliers: it
+ *       is the UNREFINED best pose (host)
+ *   Q4  Refine runs at every qualifying hypothesis, on the best set so far, not on the current one
+ *   Q5  CheckInliers: Xc, Yc, invZc are floats of double expressions, ue / ve double, distX / distY / error2 float, error2 < mvMaxError[i]
+ *   Q6  solve_for_sign looks at the first selected correspondence only
+ * Deliberate deviations:
+ *   E1  eigenvectors of M^T M: the cyclic Jacobi of S2 / I1 on the symmetric 12 x 12 in double, pairs (0,1) (0,2) .. (10,11), + - * /
+ *       sqrt only, the same skip and stop rules, at most 30 sweeps (the scenes of tests/_pnp_scenes.py need at most 10); the columns
+ *       ordered by descending diagonal entry, ties to the lowest index; ut row k = column k; signs as the Jacobi leaves them
+ *   E2  PCA of the points: the same Jacobi on the 3 x 3, descending order
+ *   E3  cvInvert(CC, CV_SVD): the inverse by cofactors in double (the layout of the Initializer's inv3)
+ *   E4  the three cvSolve(CV_SVD) least-squares systems go through the file's own qr_solve (:860-950), restated as written
+ *   E5  estimate_R_and_t's SVD of ABt: the I2 construction in double: V from the Jacobi on A^T A, u_k = A v_k / |A v_k| for k = 0, 1,
+ *       u_2 = u_0 x u_1, v_2 negated when (A v_2) . u_2 < 0; R = U V^T, then the reference's det < 0 fix
+ *   E6  draws: key_h = sm(sm(seed) ^ (h + 1)), draw d in 0..3 = sm(key_h + (d + 1) * 0xD1342543DE82EF95) % (N - d), applied to
+ *       vAvailableIndices with the reference's swap-with-back (:188-201)
+ *   E7  every sum over the selected correspondences (centroid, PW0^T PW0, M^T M, pc0 / pw0, ABt, the reprojection error) has a fixed
+ *       shape: 64 partial sums (partial l starts at 0 and adds the selected elements l, l + 64, .. in ascending order), then
+ *       p[l] += p[l + s] for s = 32 .. 1
+ *   E8  a hypothesis or a refinement is degenerate when qr_solve meets eta == 0 (the reference returns with X unwritten), a betas[0] it
+ *       divides by is 0, or an entry of R or t of the chosen approximation is not finite: it counts 0 inliers, is flagged, its pose and
+ *       words read 0.  A reprojection error that is not finite loses the comparison of the three approximations; a correspondence whose
+ *       error2 is not finite is not an inlier.  A coplanar or collinear 4-set has no rule of its own (the reference has no rank test):
+ *       CC is singular or nearly so and the pose is what the arithmetic gives, or not finite and then degenerate by this clause
+ *       (the first two clauses are tested at the functions that raise them only: no 4-set of finite points is known that reaches them
+ *       through EPnP - control points that coincide exactly make the barycentric coordinates NaN first, which is the third clause)
+ *   E9  N < 4 evaluates nothing: all counts 0, no flag
+ *   E10 what is not written reads 0; the refined rows of a hypothesis that is not a record read 0 with refined = 0
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(afv_pnp_job) */
+    uint32_t seed_lo, seed_hi;               /* the 64-bit seed of E6 */
+    int32_t min_inliers;                     /* minInliers of SetRansacParameters, >= 4 */
+    float epsilon, th2;                      /* epsilon and th2 of SetRansacParameters */
+} afv_pnp_job;
+#define AFV_PNP_MAX_CANDIDATES 64
+#define AFV_PNP_MAX_HYPOTHESES 1024
+#define AFV_PNP_MAX_MASK_WORDS 256 /* mask_words 0 .. 256: the largest frame (8192 features) needs 256 */
+/* nc 1 .. AFV_PNP_MAX_CANDIDATES candidates of the frame f (NF = its feature count): pts[nc][NF] = the map-point id matched to feature
+ * i for candidate c (what afv_table_match_bow_frame answers, mapped to point ids), -1 = none.  A feature is kept when its id is >= 0,
+ * was set in the store and is not bad (an id that was never set counts as bad); the survivors keep the feature order.  Outputs (host):
+ * n[nc] = N; min_inliers[nc] = mRansacMinInliers = max(int(N * epsilon), job.min_inliers, 4), the product in float; index[nc][NF] =
+ * mvKeyPointIndices (-1 from N on); count / degenerate [nc][nhyp]; pose[nc][nhyp][12] = Rcw row-major, tcw, converted to float; inliers
+ * [nc][nhyp][mask_words], bit k of the row = correspondence k, unused bits 0; refined[nc][nhyp]: 0 = h is no record, 1 = refined, 2 =
+ * a record whose refinement is degenerate; refined_count / refined_pose / refined_inliers as count / pose / inliers; optional max_err
+ * [nc][NF] (mvMaxError = sigma2 * th2 in float) and p3dw[nc][NF][3] (mvP3Dw), 0 from N on.
+ * Refused before any launch, nothing written: AFV_EINVAL for a NULL argument other than max_err / p3dw, a frame without features or
+ * without a pose (afv_frame_set_pose: the intrinsics are the frame's), a store of another context, an id outside [-1, capacity), nc,
+ * nhyp or mask_words out of range, mask_words * 32 below the largest number of ids >= 0 in a row, an unknown struct_size, min_inliers
+ * < 4, epsilon or th2 not finite or <= 0.  The descriptor kind and width of frame and store do not matter: descriptors are not read. */
+int afv_frame_pnp_hypotheses(afv_frame *f, afv_points *points, const afv_pnp_job *jobs, int nc, const int32_t *pts, int nhyp, int mask_words,
+                             int32_t *n, int32_t *min_inliers, int32_t *index, int32_t *count, uint8_t *degenerate, float *pose,
+                             uint32_t *inliers, uint8_t *refined, int32_t *refined_count, float *refined_pose, uint32_t *refined_inliers,
+                             float *max_err, float *p3dw);
+
 /* engine of the ordered phase of the projection searches / SearchForInitialization (identical results):
  *   1: one fixed point over all live queries of a job on a 1024-thread workgroup (round 5)   0: the ordered walk of rounds 1-4 on one
  *   wavefront   2 (default): 1 whenever the job's tables fit the workgroup's LDS, else 0   3: as 1, but ranking and ordered phase as two
