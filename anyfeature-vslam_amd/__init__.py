@@ -11,7 +11,8 @@ Layout:
   frame.py       the device-resident Frame (reference: Frame.{h,cc} as far as the front end reads it)
   points.py      the device-resident map-point store (reference: MapPoint.{h,cc} as far as the projection searches read it)
   database.py    KeyFrameDatabase mirror over the keyframe table (reference: KeyFrameDatabase.{h,cc}, LoopClosing.cc:137-157)
-  sim3.py        Sim3Solver mirror: all RANSAC hypotheses of a loop check in one device call (reference: Sim3Solver.{h,cc})
+  sim3.py        Sim3Solver mirror: all RANSAC hypotheses of a loop check in one device call (reference: Sim3Solver.{h,cc});
+                 OptimizeSim3 / OptimizeSim3Batch: Optimizer::OptimizeSim3 for every candidate in one device call
   pnp.py         PnPsolver mirror: all EPnP RANSAC hypotheses of a relocalisation in one device call (reference: PnPsolver.{h,cc})
   initializer.py Initializer mirror: H and F RANSAC and the reconstruction in one device call (reference: Initializer.{h,cc})
   synth.py       bit-reproducible synthetic inputs
@@ -24,7 +25,7 @@ from .frame import Frame  # noqa: F401
 from .points import MapPoints  # noqa: F401
 from . import akaze, table  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
-from .sim3 import Sim3Solver  # noqa: F401
+from .sim3 import OptimizeSim3, OptimizeSim3Batch, Sim3Solver  # noqa: F401
 from .initializer import Initializer  # noqa: F401
 from .pnp import PnPsolver  # noqa: F401
 from .akaze import AkazeContext  # noqa: F401

@@ -153,6 +153,24 @@ class Sim3Job(C.Structure):
 SIM3_MAX_CANDIDATES, SIM3_MAX_HYPOTHESES, SIM3_MAX_MASK_WORDS = 64, 1024, 256
 
 
+class Sim3OptJob(C.Structure):
+    """afv_sim3opt_job: one (current keyframe, candidate) pair of afv_table_optimize_sim3"""
+    _fields_ = ([("struct_size", C.c_uint32), ("fix_scale", C.c_int32), ("th2", C.c_float)] +
+                [(k, C.c_float * n) for k, n in (("Rcw1", 9), ("tcw1", 3), ("Rcw2", 9), ("tcw2", 3))] +
+                [(k, C.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2", "cy2")] +
+                [("R12", C.c_float * 9), ("t12", C.c_float * 3), ("s12", C.c_float)])
+
+
+class Sim3OptResult(C.Structure):
+    """afv_sim3opt_result: what Optimizer::OptimizeSim3 answers for one job, and the trace of its two optimize() calls"""
+    _fields_ = [("n_in", C.c_int32), ("n_corr", C.c_int32), ("n_bad", C.c_int32), ("more_iterations", C.c_int32), ("early", C.c_int32),
+                ("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("reserved", C.c_int32),
+                ("R12", C.c_double * 9), ("t12", C.c_double * 3), ("s12", C.c_double), ("chi2", C.c_double * 2), ("lam", C.c_double * 2)]
+
+
+SIM3OPT_NO_MATCH, SIM3OPT_NOT_EDGE, SIM3OPT_KEPT, SIM3OPT_REMOVED_FIRST, SIM3OPT_REMOVED_SECOND = 0, 1, 2, 3, 4
+
+
 class PnpJob(C.Structure):
     """afv_pnp_job: one candidate of afv_frame_pnp_hypotheses"""
     _fields_ = [("struct_size", C.c_uint32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("min_inliers", C.c_int32),
@@ -315,6 +333,8 @@ SYMBOLS = {
                                          _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "afv_table_sim3_hypotheses": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Sim3Job), _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp]),
+    "afv_table_optimize_sim3": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Sim3OptJob), _i, _vp, _vp, _vp, C.POINTER(Sim3OptResult), _vp]),
+    "afv_table_set_inf": (_i, [_vp, _i, _vp]),
     "afv_frame_initializer": (_i, [_vp, _vp, C.POINTER(InitJob), _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp,
                                    C.POINTER(InitTrace), _vp, _vp, _vp, _vp, _i]),
     "afv_frame_pnp_hypotheses": (_i, [_vp, _vp, C.POINTER(PnpJob), _i, _vp, _i, _i] + [_vp] * 13),

@@ -1353,6 +1353,78 @@ class Sim3Solver {
     std::vector<uint32_t> inliers;        // [nhyp][words]
 };
 
+// ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:1033-1226) as LoopClosing::ComputeSim3 calls it once a solver found a transform
+// (src/LoopClosing.cc:342): OptimizeSim3Batch makes ONE afv_table_optimize_sim3 call for all candidates - the edge sets, both optimize()
+// calls and both classifications of every job run on the device, one wavefront per job (include/afv_hip.h, "OptimizeSim3": deviations
+// O1-O7).  The slots hold the keyframes' mvKeysUn (afv_table_set_geometry) and GetKeyPt2DInf (afv_table_set_inf, or a promoted frame).
+struct Sim3d {  // g2o::Sim3 without the quaternion: R row-major, t, s
+    double R[9], t[3], s;
+};
+struct OptimizeSim3Answer {
+    int nInliers;               // what the reference returns
+    Sim3d g2oS12;               // after the call (the start itself when the call answered 0 for want of correspondences)
+    afv_sim3opt_result trace;   // counts, iterations, trials, chi2 and lambda of both optimize() calls
+};
+// cur / cands / cam_cur / cam_cands / n1 / mp1 / idx2: as Sim3Solver::Batch takes them; vpMatches1[c]: the matches of candidate c as point
+// ids (-1 = none), n1 entries - on return -1 where the reference wrote NULL; start[c]: g2oS12 going in, rounded to float (what
+// Sim3Solver::GetEstimated* return)
+inline std::vector<OptimizeSim3Answer> OptimizeSim3Batch(afv_ctx *ctx, afv_table *table, int cap, DeviceMapPoints &points, int32_t cur,
+                                                         const Sim3Solver::Camera &cam_cur, const std::vector<int32_t> &cands,
+                                                         const std::vector<Sim3Solver::Camera> &cam_cands, int n1, const std::vector<int32_t> &mp1,
+                                                         std::vector<std::vector<int32_t>> &vpMatches1, const std::vector<std::vector<int32_t>> &idx2,
+                                                         const std::vector<Sim3d> &start, float th2, bool bFixScale) {
+    const size_t nc = cands.size(), cells = nc * (size_t)cap;
+    std::vector<afv_sim3opt_job> jobs(nc);
+    std::vector<int32_t> slot_a(nc, cur), r1(cells, -1), r2(cells, -1), k2(cells, -1);
+    for (size_t c = 0; c < nc; ++c) {
+        afv_sim3opt_job &j = jobs[c];
+        std::memset(&j, 0, sizeof(j));
+        j.struct_size = (uint32_t)sizeof(afv_sim3opt_job);
+        j.fix_scale = bFixScale ? 1 : 0;
+        j.th2 = th2;
+        std::memcpy(j.Rcw1, cam_cur.Rcw, sizeof(j.Rcw1)); std::memcpy(j.tcw1, cam_cur.tcw, sizeof(j.tcw1));
+        std::memcpy(j.Rcw2, cam_cands[c].Rcw, sizeof(j.Rcw2)); std::memcpy(j.tcw2, cam_cands[c].tcw, sizeof(j.tcw2));
+        j.fx1 = cam_cur.fx; j.fy1 = cam_cur.fy; j.cx1 = cam_cur.cx; j.cy1 = cam_cur.cy;
+        j.fx2 = cam_cands[c].fx; j.fy2 = cam_cands[c].fy; j.cx2 = cam_cands[c].cx; j.cy2 = cam_cands[c].cy;
+        for (int k = 0; k < 9; ++k) j.R12[k] = (float)start[c].R[k];
+        for (int k = 0; k < 3; ++k) j.t12[k] = (float)start[c].t[k];
+        j.s12 = (float)start[c].s;
+        for (int i = 0; i < n1 && i < cap; ++i) {
+            const size_t o = c * (size_t)cap + (size_t)i;
+            r1[o] = mp1[(size_t)i]; r2[o] = vpMatches1[c][(size_t)i]; k2[o] = idx2[c][(size_t)i];
+        }
+    }
+    std::vector<afv_sim3opt_result> res(nc);
+    std::vector<uint8_t> state(cells);
+    const int rc = afv_table_optimize_sim3(table, points.handle(), slot_a.data(), cands.data(), jobs.data(), (int)nc, r1.data(), r2.data(), k2.data(),
+                                           res.data(), state.data());
+    if (rc != AFV_OK) fatal("afv_table_optimize_sim3", rc, ctx);
+    std::vector<OptimizeSim3Answer> out(nc);
+    for (size_t c = 0; c < nc; ++c) {
+        out[c].nInliers = res[c].n_in;
+        std::memcpy(out[c].g2oS12.R, res[c].R12, sizeof(res[c].R12));
+        std::memcpy(out[c].g2oS12.t, res[c].t12, sizeof(res[c].t12));
+        out[c].g2oS12.s = res[c].s12;
+        out[c].trace = res[c];
+        for (int i = 0; i < n1 && i < cap; ++i) {
+            const uint8_t st = state[c * (size_t)cap + (size_t)i];
+            if (st == AFV_SIM3OPT_REMOVED_FIRST || st == AFV_SIM3OPT_REMOVED_SECOND) vpMatches1[c][(size_t)i] = -1;
+        }
+    }
+    return out;
+}
+// the reference's call shape for one candidate: vpMatches1 and g2oS12 are updated in place, nIn is returned
+inline int OptimizeSim3(afv_ctx *ctx, afv_table *table, int cap, DeviceMapPoints &points, int32_t cur, const Sim3Solver::Camera &cam_cur, int32_t cand,
+                        const Sim3Solver::Camera &cam_cand, int n1, const std::vector<int32_t> &mp1, std::vector<int32_t> &vpMatches1,
+                        const std::vector<int32_t> &idx2, Sim3d &g2oS12, float th2, bool bFixScale) {
+    std::vector<std::vector<int32_t>> m{vpMatches1};
+    const std::vector<OptimizeSim3Answer> a =
+        OptimizeSim3Batch(ctx, table, cap, points, cur, cam_cur, {cand}, {cam_cand}, n1, mp1, m, {idx2}, {g2oS12}, th2, bFixScale);
+    vpMatches1 = m[0];
+    g2oS12 = a[0].g2oS12;
+    return a[0].nInliers;
+}
+
 // ---- PnPsolver (include/PnPsolver.h, src/PnPsolver.cc) as Tracking::Relocalization uses it (src/Tracking.cc:1190-1216): Batch makes ONE
 // afv_frame_pnp_hypotheses call for all candidates of a relocalisation - every solver's constructor, every EPnP RANSAC hypothesis and the
 // Refine of every record run on the device (include/afv_hip.h, "PnPsolver": quirks Q1-Q6, deviations E1-E10) - and returns one solver per

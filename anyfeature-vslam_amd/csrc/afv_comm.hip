@@ -49,7 +49,7 @@ static std::vector<afv_comm *> g_comms;
 static void table_free(afv_table *t) {
     if (!t) return;
     if (t->c) (void)hipSetDevice(t->c->device);
-    void *ptrs[] = {t->d_desc, t->d_angle, t->d_n, t->d_idx, t->d_geo, t->d_scale, t->d_valid, t->d_pairs, t->d_out, t->d_nm, t->d_bow_word, t->d_bow_value, t->d_bow_n};
+    void *ptrs[] = {t->d_desc, t->d_angle, t->d_n, t->d_idx, t->d_geo, t->d_scale, t->d_inf, t->d_valid, t->d_pairs, t->d_out, t->d_nm, t->d_bow_word, t->d_bow_value, t->d_bow_n};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (t->h_pin) (void)hipHostFree(t->h_pin);
@@ -92,6 +92,7 @@ static int table_create(afv_ctx *c, int nsets, int cap, int desc_bytes, afv_tabl
         t->has_fv.assign((size_t)nsets, 0);
         t->has_geo.assign((size_t)nsets, 0);
         t->has_scale.assign((size_t)nsets, 0);
+        t->has_inf.assign((size_t)nsets, 0);
         t->h_bow_n.assign((size_t)nsets, 0);
         t->has_bow.assign((size_t)nsets, 0);
         t->fv_body_on_device.assign((size_t)nsets, 0);
@@ -158,6 +159,7 @@ extern "C" int afv_table_set(afv_table *t, int set, const uint8_t *desc32, const
     t->fv_body_on_device[set] = 0;
     t->has_geo[set] = 0;
     t->has_scale[set] = 0;
+    t->has_inf[set] = 0;
     t->has_bow[set] = 0;
     t->h_bow_n[set] = 0;
     if (t->d_bow_n) HIPCHK(c, hipMemsetAsync(t->d_bow_n + set, 0, sizeof(int32_t), c->stream));
@@ -213,6 +215,21 @@ extern "C" int afv_table_set_u_right(afv_table *t, int set, const float *u_right
     const int n = t->h_n[set];
     if (n > 0) HIPCHK(c, hipMemcpy(t->d_geo + 3 * plane + (size_t)set * t->cap, u_right, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     return AFV_OK;
+}
+
+// GetKeyPt2DInf of a slot: what OptimizeSim3 reads next to the geometry (afv_table_optimize_sim3)
+extern "C" int afv_table_set_inf(afv_table *t, int set, const float *inf) {
+    if (!t || set < 0 || set >= t->nsets || !inf) return AFV_EINVAL;
+    if (!t->d_geo || !t->has_geo[set]) return AFV_EINVAL;  // after afv_table_set_geometry of the same slot
+    afv_ctx *c = t->c;
+    return guarded(c, [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        if (!t->d_inf) HIPCHK(c, hipMalloc(&t->d_inf, (size_t)t->nsets * t->cap * sizeof(float)));
+        const int n = t->h_n[set];
+        t->has_inf[set] = 1;
+        if (n > 0) HIPCHK(c, hipMemcpy(t->d_inf + (size_t)set * t->cap, inf, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        return AFV_OK;
+    });
 }
 
 // keyPtsSize, mvDepth and the distorted mvKeys of a slot: what CreateNewMapPoints reads next to the geometry (afv_table_triangulate)
@@ -330,7 +347,7 @@ extern "C" int afv_table_sync_counts(afv_table *t) {  // after a broadcast / ext
 }
 
 // ---- replica image: everything a replica needs besides the device planes (host-side FeatureVector structure + per-set flags).
-// Layout (int32): [nsets] then per set {has_fv, has_geo | has_scale << 1, has_bow, bow_n, nnodes, node_id[nnodes], seg_ptr[nnodes + 1] (absent when nnodes == 0)}.
+// Layout (int32): [nsets] then per set {has_fv, has_geo | has_scale << 1 | has_inf << 2, has_bow, bow_n, nnodes, node_id[nnodes], seg_ptr[nnodes + 1] (absent when nnodes == 0)}.
 // The feature indices themselves travel with the d_idx plane, the BowVector entries with the BowVector planes. ----
 static void table_pack_meta(const afv_table *t, std::vector<int32_t> &blob) {
     blob.clear();
@@ -338,7 +355,7 @@ static void table_pack_meta(const afv_table *t, std::vector<int32_t> &blob) {
     for (int s = 0; s < t->nsets; ++s) {
         const HostFeatVec &f = t->fv[s];
         blob.push_back(t->has_fv[s]);
-        blob.push_back(t->has_geo[s] | (t->has_scale[s] << 1));  // bit 1: the scale planes (afv_table_set_scale)
+        blob.push_back(t->has_geo[s] | (t->has_scale[s] << 1) | (t->has_inf[s] << 2));  // bit 1: the scale planes (afv_table_set_scale), bit 2: the information plane (afv_table_set_inf)
         blob.push_back(t->has_bow[s]);
         blob.push_back(t->h_bow_n[s]);
         blob.push_back((int32_t)f.node_id.size());
@@ -359,6 +376,7 @@ static int table_unpack_meta(afv_table *t, const int32_t *blob, size_t len) {
         pos += 5;
         if (bow_n < 0 || bow_n > t->cap || ((has_bow || bow_n) && !t->d_bow_word)) return AFV_EINVAL;
         if ((has_geo & 2) && !t->d_scale) return AFV_EINVAL;
+        if ((has_geo & 4) && !t->d_inf) return AFV_EINVAL;
         if (nnodes < 0 || pos + (size_t)nnodes + (nnodes ? (size_t)nnodes + 1 : 0) > len) return AFV_EINVAL;
         HostFeatVec f;
         f.node_id.assign(blob + pos, blob + pos + nnodes);
@@ -379,6 +397,7 @@ static int table_unpack_meta(afv_table *t, const int32_t *blob, size_t len) {
         t->has_fv[s] = has_fv != 0;
         t->has_geo[s] = (has_geo & 1) != 0;
         t->has_scale[s] = (has_geo & 2) != 0;
+        t->has_inf[s] = (has_geo & 4) != 0;
         t->has_bow[s] = has_bow != 0;
         t->h_bow_n[s] = bow_n;
     }
@@ -399,6 +418,7 @@ extern "C" int afv_table_clone(const afv_table *src, afv_table *dst) {
         if (src->d_idx && !dst->d_idx) HIPCHK(c, hipMalloc(&dst->d_idx, plane * sizeof(int32_t)));
         if (src->d_geo && !dst->d_geo) HIPCHK(c, hipMalloc(&dst->d_geo, 4 * plane * sizeof(float)));
         if (src->d_scale && !dst->d_scale) HIPCHK(c, hipMalloc(&dst->d_scale, 4 * plane * sizeof(float)));
+        if (src->d_inf && !dst->d_inf) HIPCHK(c, hipMalloc(&dst->d_inf, plane * sizeof(float)));
         if (src->d_valid && !dst->d_valid) HIPCHK(c, hipMalloc(&dst->d_valid, plane));
         if (src->d_bow_word) {
             const int rcb = table_ensure_bow(dst);
@@ -415,11 +435,12 @@ extern "C" int afv_table_clone(const afv_table *src, afv_table *dst) {
         if (src->d_idx) HIPCHK(c, afv_copy_dd(c, dst->d_idx, src->d_idx, plane * sizeof(int32_t)));
         if (src->d_geo) HIPCHK(c, afv_copy_dd(c, dst->d_geo, src->d_geo, 4 * plane * sizeof(float)));
         if (src->d_scale) HIPCHK(c, afv_copy_dd(c, dst->d_scale, src->d_scale, 4 * plane * sizeof(float)));
+        if (src->d_inf) HIPCHK(c, afv_copy_dd(c, dst->d_inf, src->d_inf, plane * sizeof(float)));
         if (src->d_valid) HIPCHK(c, afv_copy_dd(c, dst->d_valid, src->d_valid, plane));
         else if (dst->d_valid) HIPCHK(c, afv_fill(c, dst->d_valid, 1, plane));
         for (int s = 0; s < dst->nsets; ++s) {  // nothing of the destination's previous content survives
             dst->fv[s] = HostFeatVec();
-            dst->has_fv[s] = dst->has_geo[s] = dst->has_scale[s] = dst->has_bow[s] = 0;
+            dst->has_fv[s] = dst->has_geo[s] = dst->has_scale[s] = dst->has_inf[s] = dst->has_bow[s] = 0;
             dst->h_bow_n[s] = 0;
             dst->fv_body_on_device[s] = 0;
         }
@@ -747,6 +768,10 @@ extern "C" int afv_table_set_from_frame(afv_table *t, int slot, afv_frame *f) {
         }
         t->has_geo[slot] = 1;
         t->has_scale[slot] = 1;
+        // ... and its keyPtsInf, the information plane (what PoseOptimization reads on the frame, OptimizeSim3 on the keyframe)
+        if (!t->d_inf) HIPCHK(c, hipMalloc(&t->d_inf, plane * sizeof(float)));
+        if (f->n) HIPCHK(c, hipMemcpyAsync(t->d_inf + (size_t)slot * t->cap, f->d_inf, (size_t)f->n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        t->has_inf[slot] = 1;
         // the BowVector comes along like the FeatureVector (a frame without one leaves the slot without one)
         t->has_bow[slot] = 0;
         t->h_bow_n[slot] = 0;
@@ -961,7 +986,7 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         // plane moves, so that a table of another shape or row width on any rank is refused everywhere instead of mismatching the
         // lengths of the broadcasts below
         // (the kind travels next to the width: 64-byte binary rows and rows of 16 floats have the same pitch and the same byte size)
-        int32_t flags[9] = {t->d_idx != nullptr, (t->d_geo != nullptr) | ((t->d_scale != nullptr) << 1) /* bit 1: the scale planes */, t->d_valid != nullptr, (int32_t)blob.size(), t->nsets, t->cap, t->desc_bytes, t->float_dim,
+        int32_t flags[9] = {t->d_idx != nullptr, (t->d_geo != nullptr) | ((t->d_scale != nullptr) << 1) | ((t->d_inf != nullptr) << 2) /* bit 1: the scale planes, bit 2: the information plane */, t->d_valid != nullptr, (int32_t)blob.size(), t->nsets, t->cap, t->desc_bytes, t->float_dim,
                             t->d_bow_word != nullptr};
         int32_t *d_flags = nullptr;
         HIPCHK(c, hipMalloc(&d_flags, sizeof(flags) + (size_t)(m->nranks + 1) * sizeof(int32_t)));
@@ -997,6 +1022,7 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         if (flags[0] && !t->d_idx) HIPCHK(c, hipMalloc(&t->d_idx, plane * sizeof(int32_t)));
         if ((flags[1] & 1) && !t->d_geo) HIPCHK(c, hipMalloc(&t->d_geo, 4 * plane * sizeof(float)));
         if ((flags[1] & 2) && !t->d_scale) HIPCHK(c, hipMalloc(&t->d_scale, 4 * plane * sizeof(float)));
+        if ((flags[1] & 4) && !t->d_inf) HIPCHK(c, hipMalloc(&t->d_inf, plane * sizeof(float)));
         if (flags[2] && !t->d_valid) HIPCHK(c, hipMalloc(&t->d_valid, plane));
         if (flags[8]) {
             const int rcb = table_ensure_bow(t);
@@ -1013,6 +1039,7 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         if (!rc && flags[0]) rc = afv_comm_broadcast(m, t->d_idx, plane * sizeof(int32_t), root, c->stream);
         if (!rc && (flags[1] & 1)) rc = afv_comm_broadcast(m, t->d_geo, 4 * plane * sizeof(float), root, c->stream);
         if (!rc && (flags[1] & 2)) rc = afv_comm_broadcast(m, t->d_scale, 4 * plane * sizeof(float), root, c->stream);
+        if (!rc && (flags[1] & 4)) rc = afv_comm_broadcast(m, t->d_inf, plane * sizeof(float), root, c->stream);
         if (!rc && flags[2]) rc = afv_comm_broadcast(m, t->d_valid, plane, root, c->stream);
         if (!rc && flags[8]) rc = afv_comm_broadcast(m, t->d_bow_word, plane * sizeof(int32_t), root, c->stream);
         if (!rc && flags[8]) rc = afv_comm_broadcast(m, t->d_bow_value, plane * sizeof(double), root, c->stream);
@@ -1029,7 +1056,7 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         // receivers: nothing of the previous content survives; counts first, then the FeatureVectors against them
         for (int s = 0; s < t->nsets; ++s) {
             t->fv[s] = HostFeatVec();
-            t->has_fv[s] = t->has_geo[s] = t->has_scale[s] = t->has_bow[s] = 0;
+            t->has_fv[s] = t->has_geo[s] = t->has_scale[s] = t->has_inf[s] = t->has_bow[s] = 0;
             t->h_bow_n[s] = 0;
         }
         if (!flags[8] && t->d_bow_n) HIPCHK(c, afv_fill(c, t->d_bow_n, 0, (size_t)t->nsets * sizeof(int32_t)));

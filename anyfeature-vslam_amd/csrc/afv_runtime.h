@@ -224,6 +224,36 @@ struct DevSim3Args {         // a kernel argument of both launches
 extern "C" void afv_launch_sim3_gather(const DevSim3Args *args, hipStream_t stream);
 extern "C" void afv_launch_sim3_hypotheses(const DevSim3Args *args, hipStream_t stream);
 
+// ---- k_sim3opt.hip: Optimizer::OptimizeSim3 for every candidate of a loop check (host side: afv_sim3opt.hip) ----
+#define AFV_SIM3OPT_T 256    // lanes per workgroup of the gather; the solve runs one wavefront per job
+struct DevSim3OptJob {       // one job: the caller's record and where the planes of the two slots start
+    float R1[9], t1[3], R2[9], t2[3];
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    float R12[9], t12[3], s12, th2;
+    int fix_scale, n1;
+    const float *x1, *y1, *inf1, *x2, *y2, *inf2;
+};
+struct DevSim3OptEdge {      // one correspondence as the gather leaves it
+    float p1[3], p2[3];      // P3D1c, P3D2c
+    float obs1[2], obs2[2];
+    float inf1, inf2;
+};
+struct DevSim3OptArgs {      // a kernel argument of both launches
+    const DevSim3OptJob *jobs;
+    const int *mp1, *mp2, *idx2;  // [nc][cap]
+    int nc, cap;
+    const float *pos[3];     // the store: XYZ planes and flags over `pcap` ids
+    const uint8_t *flags;
+    int pcap;
+    int *n, *index1;         // [nc], [nc][cap]: the edges' features in ascending order
+    DevSim3OptEdge *edges;   // [nc][cap]
+    uint8_t *active;         // [nc][cap] by edge: 1 while the edge is in the graph
+    afv_sim3opt_result *results;  // [nc]
+    uint8_t *state;          // [nc][cap] by feature
+};
+extern "C" void afv_launch_sim3opt_gather(const DevSim3OptArgs *args, hipStream_t stream);
+extern "C" void afv_launch_sim3opt_solve(const DevSim3OptArgs *args, hipStream_t stream);
+
 // ---- k_init.hip: Initializer::Initialize between two resident frames (host side: afv_init.hip) ----
 #define AFV_INIT_PREP_T 256  // lanes of k_init_prepare (I5: the width of Normalize's partial sums)
 #define AFV_INIT_REC_T 512   // lanes of k_init_reconstruct: 8 wavefronts over the 8 motion hypotheses of H or the 4 of F
@@ -700,6 +730,8 @@ struct afv_table {
     std::vector<HostFeatVec> fv;
     std::vector<uint8_t> has_fv, has_geo;  // per set: afv_table_set_featvec / afv_table_set_geometry called since the last afv_table_set
     std::vector<uint8_t> has_scale;        // per set: afv_table_set_scale called (or a frame promoted) since the last afv_table_set
+    float *d_inf = nullptr;     // [nsets][cap] GetKeyPt2DInf (afv_table_set_inf / a promoted frame's keyPtsInf), lazily allocated
+    std::vector<uint8_t> has_inf;          // per set: the information plane was stored since the last afv_table_set
     std::vector<uint8_t> fv_body_on_device;  // per set: the FeatureVector body came from a frame (afv_table_set_from_frame): no host copy yet
     // BowVector planes (afv_table_set_bowvec / afv_table_set_from_frame), lazily allocated together
     int32_t *d_bow_word = nullptr;  // [nsets][cap] word ids ascending

@@ -85,6 +85,13 @@ __device__ __forceinline__ unsigned afv_wave_min_u32(unsigned v) {
     return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// a double of lane `src` (wave-uniform, usually a compile-time constant) for every lane, through scalar registers: two v_readlane, no
+// LDS crossbar.  What one lane computed is handed to all of them this way (k_sim3opt.hip: the perturbed estimates of a linearisation).
+__device__ __forceinline__ double afv_wave_read_f64(double v, int src) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src), hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
+    return __hiloint2double(hi, lo);
+}
+
 // ---------------- the rotation histogram of FeatureMatcher.cc ----------------
 // the bin of a match (FeatureMatcher.cc:1587-1599), rotFactor = 1/30 (:1579-1585)
 __device__ __forceinline__ int afv_rotation_bin(float a1, float a2) {

@@ -6,6 +6,10 @@ candidate, csrc/k_sim3.hip) and returns one Sim3Solver per candidate.  iterate /
 transforms and inlier words: hypothesis h depends on (seed, h) alone, so the reference's sequential rule (running best, return on
 > minInliers) is a scan.  The normative semantics, the quirks Q1-Q3 and the deviations S1-S6 are tests/_sim3_ref.py's and
 include/afv_hip.h's ("Sim3Solver").
+
+OptimizeSim3 / OptimizeSim3Batch are Optimizer::OptimizeSim3 (src/Optimizer.cc:1033-1226) as LoopClosing::ComputeSim3 calls it after a
+solver found a transform (src/LoopClosing.cc:342): ONE device call (afv_table_optimize_sim3, csrc/k_sim3opt.hip) refines the Sim3 of every
+candidate.  Normative semantics and the deviations O1-O7: tests/_sim3opt_ref.py and include/afv_hip.h ("OptimizeSim3").
 """
 import ctypes as C
 import math
@@ -13,7 +17,7 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import Sim3Job, ptr
+from ._lib import Sim3Job, Sim3OptJob, Sim3OptResult, ptr
 
 
 def _rows(a, nc, cap, what, broadcast=False):
@@ -174,3 +178,71 @@ class Sim3Solver:
 
     def GetEstimatedScale(self):
         return None if self.best is None else float(self.sim3[self.best][12])
+
+
+def sim3opt_jobs(cam_cur, cams_cand, S12s, th2, fix_scale):
+    """afv_sim3opt_job records from camera dicts {Rcw, tcw, fx, fy, cx, cy} and starts (R12, t12, s12): 1 = the current keyframe, 2 = candidate c"""
+    jobs = (Sim3OptJob * len(cams_cand))()
+    for c, (cam2, S12) in enumerate(zip(cams_cand, S12s)):
+        j = jobs[c]
+        j.struct_size = C.sizeof(Sim3OptJob)
+        j.fix_scale = 1 if fix_scale else 0
+        j.th2 = float(np.float32(th2))
+        for side, cam in (("1", cam_cur), ("2", cam2)):
+            for name, cnt in (("Rcw", 9), ("tcw", 3)):
+                v = np.asarray(cam[name], np.float32).reshape(cnt)
+                dst = getattr(j, name + side)
+                for k in range(cnt):
+                    dst[k] = float(v[k])
+            for key in ("fx", "fy", "cx", "cy"):
+                setattr(j, key + side, float(np.float32(cam[key])))
+        R12, t12 = np.asarray(S12[0], np.float32).reshape(9), np.asarray(S12[1], np.float32).reshape(3)
+        for k in range(9):
+            j.R12[k] = float(R12[k])
+        for k in range(3):
+            j.t12[k] = float(t12[k])
+        j.s12 = float(np.float32(S12[2]))
+    return jobs
+
+
+def optimize_sim3(table, points, slot_a, slot_b, jobs, mp1, mp2, idx2):
+    """afv_table_optimize_sim3 as it is: rows [nc, cap] in; (results: a ctypes array of Sim3OptResult, state [nc, cap] uint8) out"""
+    sa, sb = (np.ascontiguousarray(v, np.int32).reshape(-1) for v in (slot_a, slot_b))
+    nc, cap = len(sa), table.cap
+    if len(sb) != nc or len(jobs) != nc:
+        raise ValueError("OptimizeSim3: %d candidates need %d slots and jobs" % (nc, nc))
+    mp1, mp2, idx2 = _rows(mp1, nc, cap, "mp1", True), _rows(mp2, nc, cap, "mp2"), _rows(idx2, nc, cap, "idx2")
+    results = (Sim3OptResult * nc)()
+    state = np.zeros((nc, cap), np.uint8)
+    table.ctx.check(table.lib.afv_table_optimize_sim3(table.handle, points.handle, ptr(sa), ptr(sb), jobs, nc, ptr(mp1), ptr(mp2), ptr(idx2), results,
+                                                      ptr(state)), "afv_table_optimize_sim3")
+    return results, state
+
+
+def OptimizeSim3Batch(table, points, cur, cands, mp1, mp2, idx2, cams, S12s, th2=10, fix_scale=False):
+    """Optimizer::OptimizeSim3 for every candidate of a loop check in one device call.  table / points / cur / cands / mp1 / mp2 / idx2 / cams:
+    as Sim3Solver.batch takes them (the slots also need their information plane: DescriptorTable.set_inf or a promoted frame); S12s: per
+    candidate (R12 [3, 3], t12 [3], s12), what the solver's GetEstimatedRotation / Translation / Scale return; th2, fix_scale: the
+    reference's arguments.  Returns per candidate (nInliers, mp2_out, (R12 [3, 3], t12 [3], s12)) with mp2_out = vpMatches1 after the call
+    (-1 where the reference writes NULL) and the Sim3 in double (the start itself when the call answers 0 for want of correspondences)."""
+    cands = [int(s) for s in cands]
+    nc = len(cands)
+    if len(S12s) != nc:
+        raise ValueError("OptimizeSim3Batch: one start per candidate is expected")
+    jobs = sim3opt_jobs(cams[int(cur)], [cams[s] for s in cands], S12s, th2, fix_scale)
+    results, state = optimize_sim3(table, points, [int(cur)] * nc, cands, jobs, mp1, mp2, idx2)
+    mp2 = np.asarray(mp2, np.int32)
+    out = []
+    for c in range(nc):
+        r = results[c]
+        row = mp2[c].copy()
+        st = state[c, :len(row)]
+        row[(st == _lib.SIM3OPT_REMOVED_FIRST) | (st == _lib.SIM3OPT_REMOVED_SECOND)] = -1
+        out.append((int(r.n_in), row, (np.array(r.R12[:], np.float64).reshape(3, 3), np.array(r.t12[:], np.float64), float(r.s12))))
+    return out
+
+
+def OptimizeSim3(table, points, cur, cand, mp1, mp2, idx2, cams, S12, th2=10, fix_scale=False):
+    """one candidate: mp2 / idx2 [n1].  Returns (nInliers, mp2_out, (R12, t12, s12))"""
+    return OptimizeSim3Batch(table, points, cur, [cand], mp1, np.asarray(mp2, np.int32)[None], np.asarray(idx2, np.int32)[None], cams, [S12], th2,
+                             fix_scale)[0]

@@ -155,6 +155,11 @@ class DescriptorTable:
             u = np.ascontiguousarray(u_right, np.float32)
             self.ctx.check(self.lib.afv_table_set_u_right(self.handle, int(slot), ptr(u)), "afv_table_set_u_right")
 
+    def set_inf(self, slot, inf):
+        """KeyFrame::GetKeyPt2DInf of a slot (the information of feature i is inf[i] * I), after set_geometry: what OptimizeSim3 reads"""
+        v = np.ascontiguousarray(inf, np.float32)
+        self.ctx.check(self.lib.afv_table_set_inf(self.handle, int(slot), ptr(v)), "afv_table_set_inf")
+
     def set_scale(self, slot, size, depth=None, x_dist=None, y_dist=None):
         """KeyFrame::GetKeyPtSize, mvDepth and the distorted mvKeys of a slot, after set_geometry: what triangulate reads next to the
         geometry.  depth None: -1 everywhere (monocular); x_dist / y_dist None (both or neither): the undistorted points"""

@@ -885,6 +885,68 @@ int afv_table_sim3_hypotheses(afv_table *t, afv_points *points, const int32_t *s
                               int32_t *n, int32_t *index1, int32_t *count, uint8_t *degenerate, float *sim3, uint32_t *inliers, float *x3dc1,
                               float *x3dc2, float *max_err);
 
+/* ---- OptimizeSim3: the Sim3 of every loop candidate refined in one call (Optimizer::OptimizeSim3, src/Optimizer.cc:1033-1226, as
+ * LoopClosing::ComputeSim3 calls it at src/LoopClosing.cc:342).  Everything the routine reads is resident: mvKeysUn of the two keyframes
+ * (the table's geometry planes), GetKeyPt2DInf (the table's information plane, afv_table_set_inf), XYZ and isBad of the points (the
+ * store).  One upload, two launches, one wait per call whatever the number of candidates (csrc/k_sim3opt.hip: k_sim3opt_gather, one
+ * workgroup per job: the edge set; k_sim3opt_solve, ONE WAVEFRONT per job: both optimize() calls and both classifications, the estimate,
+ * H, b and lambda lane-uniform in registers, the lanes striding over the correspondences, no barrier, no LDS).
+ * The normative semantics are tests/_sim3opt_ref.py (double, one rounding per operator, every operator order fixed there); the device
+ * is held to it bit for bit.  g2o is not shipped by the reference, so what it runs is restated after upstream g2o as bundled with
+ * ORB-SLAM2 - parity with a real g2o is UNPINNED.
+ * The edge set (:1084-1163): feature i of keyframe 1 is a correspondence when mp2[i] >= 0, mp1[i] >= 0, both ids are set in the store
+ * and not bad, and idx2[i] >= 0.  A match that fails the filter stays in vpMatches1: it is no edge, and it is not removed.
+ * Deliberate deviations from upstream (the numbering of tests/_sim3opt_ref.py):
+ *   O1  both classifications are made at the accepted estimate (P1 of PoseOptimization)
+ *   O2  a chi2 that is not finite is an outlier (P2)
+ *   O3  the state is R (3 x 3), t and s in double; a step is R <- dR R, t <- ds (dR t) + dt, s <- ds s; no quaternion, the caller's R12
+ *       is taken as given (P3)
+ *   O4  no library sin / cos / exp: sin(th)/th, (1 - cos th)/th^2, (th - sin th)/th^3 are PoseOptimization's 16-term Horner polynomials in
+ *       th^2 (sin th = th * A, cos th = 1 - th^2 * B); exp(sigma) = 2^k * P(r), k = floor(sigma * log2(e) + 0.5), r = (sigma - k * ln2_hi)
+ *       - k * ln2_lo, P the Taylor polynomial of degree 13 by Horner; measured against math.exp over |sigma| <= 64: at most 1 ulp.  A step
+ *       with th^2 > pi^2, or a sigma that is not finite or beyond 64 in magnitude, is a failed trial
+ *   O5  every sum over the correspondences (28 + 7 + 1 per linearisation, 1 per trial): 64 partial sums, partial l adds the terms of
+ *       the correspondences l, l + 64, ... (positions in the edge list) in ascending order, a correspondence contributing e12's term +
+ *       e21's term, a removed one nothing; then p[l] += p[l + s], s = 32 .. 1
+ *   O6  the 7 x 7 solve is an unpivoted L L^T in a fixed order; a pivot that is not positive and finite is a failed trial.  With
+ *       fix_scale the numeric Jacobian's scale column is exactly zero, so row 6 holds lambda alone and the scale's bits never change
+ *   O7  a problem without (remaining) edges evaluates nothing: optimize() leaves the estimate and reports 0 iterations
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(afv_sim3opt_job) */
+    int32_t fix_scale;                       /* bFixScale: 0 / 1 */
+    float th2;                               /* th2; the Huber delta is sqrtf(th2) */
+    float Rcw1[9], tcw1[3], Rcw2[9], tcw2[3]; /* row-major; 1 = the current keyframe, 2 = the candidate */
+    float fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2;
+    float R12[9], t12[3], s12;               /* g2oS12 as Sim3Solver::GetEstimatedRotation / Translation / Scale return it */
+} afv_sim3opt_job;
+typedef struct {
+    int32_t n_in;                            /* what OptimizeSim3 returns */
+    int32_t n_corr, n_bad, more_iterations;  /* nCorrespondences, nBad of the first check, nMoreIterations (10 / 5) */
+    int32_t early;                           /* 1: nCorrespondences - nBad < 10, the call answered 0 and R12 / t12 / s12 are the job's */
+    int32_t iterations[2], trials[2];        /* per optimize() call */
+    int32_t reserved;
+    double R12[9], t12[3], s12;              /* g2oS12 after the call */
+    double chi2[2], lambda[2];               /* the robust chi2 and lambda each optimize() call ended with */
+} afv_sim3opt_result;
+/* state[nc][cap], one byte per feature of keyframe 1 (0 from n1 on) */
+#define AFV_SIM3OPT_NO_MATCH 0       /* mp2 < 0 */
+#define AFV_SIM3OPT_NOT_EDGE 1       /* a match that fails the filter: kept in vpMatches1 */
+#define AFV_SIM3OPT_KEPT 2           /* an edge whose match stays (an inlier unless the call answered 0 early) */
+#define AFV_SIM3OPT_REMOVED_FIRST 3  /* removed by the check after optimize(5) */
+#define AFV_SIM3OPT_REMOVED_SECOND 4 /* removed by the check after optimize(nMoreIterations) */
+/* nc 1 .. AFV_SIM3_MAX_CANDIDATES jobs; slots, mp1 / mp2 / idx2 rows of `cap` ints as afv_table_sim3_hypotheses takes them (no idx1:
+ * the observation of keyframe 1 is feature i itself, :1127).  Outputs (host): results[nc], state[nc][cap].
+ * Refused before any launch, nothing written: AFV_EINVAL for a NULL argument, nc out of range, an unknown struct_size, a fix_scale other
+ * than 0 / 1, a slot out of range, one holding features without geometry or without the information plane (afv_table_set_inf), a store
+ * of another context, an id outside [-1, capacity), an idx2 outside [-1, n_slot_b).  Descriptors are not read. */
+int afv_table_optimize_sim3(afv_table *t, afv_points *points, const int32_t *slot_a, const int32_t *slot_b, const afv_sim3opt_job *jobs, int nc,
+                            const int32_t *mp1, const int32_t *mp2, const int32_t *idx2, afv_sim3opt_result *results, uint8_t *state);
+/* GetKeyPt2DInf of a slot's features (inf[n]: the information of feature i is inf[i] * I), after afv_table_set_geometry of the same slot.
+ * afv_table_set_from_frame brings the frame's keyPtsInf, afv_table_clone and afv_table_broadcast carry the plane, afv_table_set forgets
+ * it.  Only afv_table_optimize_sim3 reads it. */
+int afv_table_set_inf(afv_table *t, int set, const float *inf);
+
 /* ---- Initializer: monocular start-up between two resident frames (src/Initializer.cc:41-908, as Tracking::MonocularInitialization calls
  * it, src/Tracking.cc:487).  One synchronous call does what Initializer::Initialize does, from matches12 (what
  * afv_frame_match_initialization answers) to (R21, t21, vP3D, vbTriangulated): one upload, three launches on the context's stream, one
