@@ -13,6 +13,7 @@ Layout:
   database.py    KeyFrameDatabase mirror over the keyframe table (reference: KeyFrameDatabase.{h,cc}, LoopClosing.cc:137-157)
   sim3.py        Sim3Solver mirror: all RANSAC hypotheses of a loop check in one device call (reference: Sim3Solver.{h,cc});
                  OptimizeSim3 / OptimizeSim3Batch: Optimizer::OptimizeSim3 for every candidate in one device call
+  lba.py         LocalBundleAdjustment / BundleAdjustment over table slots and store ids (reference: Optimizer.cc:450-768, :61-243)
   pnp.py         PnPsolver mirror: all EPnP RANSAC hypotheses of a relocalisation in one device call (reference: PnPsolver.{h,cc})
   initializer.py Initializer mirror: H and F RANSAC and the reconstruction in one device call (reference: Initializer.{h,cc})
   synth.py       bit-reproducible synthetic inputs
@@ -26,6 +27,7 @@ from .points import MapPoints  # noqa: F401
 from . import akaze, table  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
 from .sim3 import OptimizeSim3, OptimizeSim3Batch, Sim3Solver  # noqa: F401
+from .lba import BundleAdjustment, LocalBundleAdjustment  # noqa: F401
 from .initializer import Initializer  # noqa: F401
 from .pnp import PnPsolver  # noqa: F401
 from .akaze import AkazeContext  # noqa: F401

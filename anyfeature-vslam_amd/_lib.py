@@ -171,6 +171,28 @@ class Sim3OptResult(C.Structure):
 SIM3OPT_NO_MATCH, SIM3OPT_NOT_EDGE, SIM3OPT_KEPT, SIM3OPT_REMOVED_FIRST, SIM3OPT_REMOVED_SECOND = 0, 1, 2, 3, 4
 
 
+class LbaCam(C.Structure):
+    """afv_lba_cam: pose and intrinsics of one keyframe of afv_table_bundle_adjust"""
+    _fields_ = ([("struct_size", C.c_uint32), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3)] +
+                [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "bf")])
+
+
+class LbaParams(C.Structure):
+    """afv_lba_params: the driver of afv_table_bundle_adjust (checks = 1: LocalBundleAdjustment, 0: BundleAdjustment)"""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32 * 2), ("robust", C.c_int32 * 2), ("checks", C.c_int32),
+                ("write_points", C.c_int32), ("trial_budget", C.c_int32)]
+
+
+class LbaResult(C.Structure):
+    """afv_lba_result: the trace of the two optimize() calls and the counts of the two checks"""
+    _fields_ = [("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("n_edges", C.c_int32), ("n_removed_first", C.c_int32),
+                ("n_erase", C.c_int32), ("stopped", C.c_int32), ("chi2", C.c_double * 2), ("lam", C.c_double * 2)]
+
+
+LBA_MAX_FREE, LBA_MAX_KF, LBA_MAX_POINTS, LBA_MAX_EDGES = 64, 256, 32768, 262144
+LBA_EDGE_DROPPED, LBA_EDGE_KEPT, LBA_EDGE_REMOVED_KEPT, LBA_EDGE_ERASE = 0, 1, 2, 3
+
+
 class PnpJob(C.Structure):
     """afv_pnp_job: one candidate of afv_frame_pnp_hypotheses"""
     _fields_ = [("struct_size", C.c_uint32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("min_inliers", C.c_int32),
@@ -334,6 +356,8 @@ SYMBOLS = {
     "afv_table_sim3_hypotheses": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Sim3Job), _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                        _vp, _vp, _vp]),
     "afv_table_optimize_sim3": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Sim3OptJob), _i, _vp, _vp, _vp, C.POINTER(Sim3OptResult), _vp]),
+    "afv_table_bundle_adjust": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(LbaCam), _vp, _i, _vp, _vp, _vp, _i, C.POINTER(LbaParams), _vp,
+                                     C.POINTER(LbaResult), _vp, _vp, _vp]),
     "afv_table_set_inf": (_i, [_vp, _i, _vp]),
     "afv_frame_initializer": (_i, [_vp, _vp, C.POINTER(InitJob), _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp,
                                    C.POINTER(InitTrace), _vp, _vp, _vp, _vp, _i]),

@@ -1425,6 +1425,107 @@ inline int OptimizeSim3(afv_ctx *ctx, afv_table *table, int cap, DeviceMapPoints
     return a[0].nInliers;
 }
 
+// ---- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:450-768) and Optimizer::BundleAdjustment (:61-243): ONE afv_table_bundle_adjust
+// call over slots of the keyframe table and ids of the map-point store (include/afv_hip.h, "Bundle adjustment": quirk L-Q1, deviations
+// L1-L9).  The slots hold the keyframes' mvKeysUn, mvuRight and GetKeyPt2DInf.  What stays with the host's map after a call:
+// EraseMapPointMatch / EraseObservation for every pair of vToErase, SetPose from `poses`, UpdateNormalAndDepth of the moved points.
+struct BundleKeyFrame {  // a keyframe of the problem: its slot, whether its vertex is fixed (keyId == 0, lFixedCameras), GetPose(), intrinsics
+    int32_t slot;
+    bool fixed;
+    float Rcw[9], tcw[3], fx, fy, cx, cy, mbf;
+};
+struct BundleObservation {  // pMP->GetObservations(): point id, keyframe slot, feature index - in the reference's order
+    int32_t point, slot, idx;
+};
+struct Pose3d {  // g2o::SE3Quat without the quaternion: R row-major, t
+    double R[9], t[3];
+};
+struct BundleAnswer {
+    std::vector<std::pair<int32_t, Pose3d>> poses;          // (slot, pose) of every optimised keyframe, in the caller's order
+    std::vector<double> xyz;                                // [np][3]; the store holds the float cast when write_points
+    std::vector<std::pair<int32_t, int32_t>> vToErase;      // (slot, point id)
+    std::vector<uint8_t> edge_state;                        // AFV_LBA_EDGE_* per observation
+    afv_lba_result trace;
+};
+inline BundleAnswer BundleAdjust(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<BundleKeyFrame> &kfs,
+                                 const std::vector<int32_t> &point_ids, const std::vector<BundleObservation> &observations, int it0, int it1,
+                                 bool robust0, bool robust1, bool checks, bool write_points, const volatile int32_t *pbStopFlag) {
+    std::vector<size_t> order;  // free keyframes first, each group in the caller's order
+    for (size_t k = 0; k < kfs.size(); ++k)
+        if (!kfs[k].fixed) order.push_back(k);
+    const int n_free = (int)order.size();
+    for (size_t k = 0; k < kfs.size(); ++k)
+        if (kfs[k].fixed) order.push_back(k);
+    std::vector<int32_t> slots(std::max<size_t>(kfs.size(), 1), 0);
+    std::vector<afv_lba_cam> cams(std::max<size_t>(kfs.size(), 1));
+    std::map<int32_t, int32_t> where_k, where_p;
+    for (size_t i = 0; i < order.size(); ++i) {
+        const BundleKeyFrame &K = kfs[order[i]];
+        slots[i] = K.slot;
+        where_k[K.slot] = (int32_t)i;
+        afv_lba_cam &c = cams[i];
+        std::memset(&c, 0, sizeof(c));
+        c.struct_size = (uint32_t)sizeof(afv_lba_cam);
+        std::memcpy(c.Rcw, K.Rcw, sizeof(c.Rcw)); std::memcpy(c.tcw, K.tcw, sizeof(c.tcw));
+        c.fx = K.fx; c.fy = K.fy; c.cx = K.cx; c.cy = K.cy; c.bf = K.mbf;
+    }
+    for (size_t p = 0; p < point_ids.size(); ++p) where_p[point_ids[p]] = (int32_t)p;
+    // the edges grouped by point in the order of point_ids; the observations of a point keep their order
+    std::vector<size_t> eo(observations.size());
+    for (size_t e = 0; e < eo.size(); ++e) eo[e] = e;
+    std::vector<int32_t> pos_p(observations.size()), pos_k(observations.size());
+    for (size_t e = 0; e < observations.size(); ++e) {
+        const auto ip = where_p.find(observations[e].point);
+        const auto ik = where_k.find(observations[e].slot);
+        if (ip == where_p.end() || ik == where_k.end()) fatal("BundleAdjust: an observation names a point or keyframe outside the problem", AFV_EINVAL, ctx);
+        pos_p[e] = ip->second;
+        pos_k[e] = ik->second;
+    }
+    std::stable_sort(eo.begin(), eo.end(), [&](size_t a, size_t b) { return pos_p[a] < pos_p[b]; });
+    const size_t ne = observations.size(), np = point_ids.size();
+    std::vector<int32_t> op(std::max<size_t>(ne, 1), 0), ok(std::max<size_t>(ne, 1), 0), oi(std::max<size_t>(ne, 1), 0), ids(std::max<size_t>(np, 1), 0);
+    for (size_t e = 0; e < ne; ++e) { op[e] = pos_p[eo[e]]; ok[e] = pos_k[eo[e]]; oi[e] = observations[eo[e]].idx; }
+    std::copy(point_ids.begin(), point_ids.end(), ids.begin());
+    afv_lba_params prm;
+    std::memset(&prm, 0, sizeof(prm));
+    prm.struct_size = (uint32_t)sizeof(afv_lba_params);
+    prm.iterations[0] = it0; prm.iterations[1] = it1; prm.robust[0] = robust0 ? 1 : 0; prm.robust[1] = robust1 ? 1 : 0;
+    prm.checks = checks ? 1 : 0; prm.write_points = write_points ? 1 : 0;
+    BundleAnswer A;
+    std::memset(&A.trace, 0, sizeof(A.trace));
+    std::vector<double> kf((size_t)std::max(n_free, 1) * 12, 0.0);
+    std::vector<uint8_t> state(std::max<size_t>(ne, 1), 0);
+    A.xyz.assign(std::max<size_t>(np, 1) * 3, 0.0);
+    const int rc = afv_table_bundle_adjust(table, points.handle(), slots.data(), (int)kfs.size(), n_free, cams.data(), ids.data(), (int)np, op.data(),
+                                           ok.data(), oi.data(), (int)ne, &prm, pbStopFlag, &A.trace, kf.data(), A.xyz.data(), state.data());
+    if (rc != AFV_OK) fatal("afv_table_bundle_adjust", rc, ctx);
+    A.xyz.resize(np * 3);
+    A.edge_state.assign(ne, 0);
+    if (A.trace.stopped == 1) return A;  // the return at :645-647: nothing was written
+    for (int i = 0; i < n_free; ++i) {
+        Pose3d P;
+        std::memcpy(P.R, kf.data() + (size_t)i * 12, sizeof(P.R));
+        std::memcpy(P.t, kf.data() + (size_t)i * 12 + 9, sizeof(P.t));
+        A.poses.emplace_back(slots[(size_t)i], P);
+    }
+    for (size_t e = 0; e < ne; ++e) A.edge_state[eo[e]] = state[e];
+    for (size_t e = 0; e < ne; ++e)
+        if (A.edge_state[e] == AFV_LBA_EDGE_ERASE) A.vToErase.emplace_back(observations[e].slot, observations[e].point);
+    return A;
+}
+// the reference's call shapes.  kfs: lLocalKeyFrames then lFixedCameras (fixed = true for keyId == 0 and every fixed camera)
+inline BundleAnswer LocalBundleAdjustment(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<BundleKeyFrame> &kfs,
+                                          const std::vector<int32_t> &point_ids, const std::vector<BundleObservation> &observations,
+                                          const volatile int32_t *pbStopFlag = nullptr) {
+    return BundleAdjust(ctx, table, points, kfs, point_ids, observations, 5, 10, true, false, true, true, pbStopFlag);
+}
+// write_points = false is the nLoopKF != 0 path: the caller keeps xyz as mPosGBA and the poses as mTcwGBA, the store stays
+inline BundleAnswer BundleAdjustment(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<BundleKeyFrame> &kfs,
+                                     const std::vector<int32_t> &point_ids, const std::vector<BundleObservation> &observations, int nIterations = 5,
+                                     const volatile int32_t *pbStopFlag = nullptr, bool bRobust = true, bool write_points = true) {
+    return BundleAdjust(ctx, table, points, kfs, point_ids, observations, nIterations, 0, bRobust, false, false, write_points, pbStopFlag);
+}
+
 // ---- PnPsolver (include/PnPsolver.h, src/PnPsolver.cc) as Tracking::Relocalization uses it (src/Tracking.cc:1190-1216): Batch makes ONE
 // afv_frame_pnp_hypotheses call for all candidates of a relocalisation - every solver's constructor, every EPnP RANSAC hypothesis and the
 // Refine of every record run on the device (include/afv_hip.h, "PnPsolver": quirks Q1-Q6, deviations E1-E10) - and returns one solver per

@@ -254,6 +254,34 @@ struct DevSim3OptArgs {      // a kernel argument of both launches
 extern "C" void afv_launch_sim3opt_gather(const DevSim3OptArgs *args, hipStream_t stream);
 extern "C" void afv_launch_sim3opt_solve(const DevSim3OptArgs *args, hipStream_t stream);
 
+// ---- k_lba.hip: LocalBundleAdjustment / BundleAdjustment (host side: afv_lba.hip; the arithmetic: afv_lba_math.h) ----
+struct LbView;
+struct LbCam;
+struct DevLbaGather {        // k_lba_gather: what the call reads from the table and the store, and where it goes in the view
+    const float *geo, *inf;  // the table's planes: geo [4][nsets][cap], inf [nsets][cap]
+    size_t plane;            // nsets * cap
+    int cap;
+    const int *slots, *obs_idx, *point_ids;  // [nk], [ne], [np]
+    const float *cams;       // [nk][17]: Rcw, tcw, fx, fy, cx, cy, bf
+    const float *pos[3];     // the store
+    const uint8_t *flags;
+    double *obs;             // [5][ne]
+    uint8_t *stereo, *p_on;
+    LbCam *cam;
+};
+struct DevLbaFinish {        // k_lba_finish
+    double *kf_out, *xyz_out;
+    float *pos[3];
+    const int *point_ids;
+    int write_points;
+};
+extern "C" void afv_launch_lba_gather(const LbView *V, const DevLbaGather *G, hipStream_t stream);
+extern "C" void afv_launch_lba_round(const LbView *V, int max_it, int robust, hipStream_t stream);
+extern "C" void afv_launch_lba_iteration(const LbView *V, hipStream_t stream);  // linearise, build, begin
+extern "C" void afv_launch_lba_trial(const LbView *V, hipStream_t stream);      // invert, schur, solve, step, trial, judge
+extern "C" void afv_launch_lba_check(const LbView *V, int final_check, hipStream_t stream);
+extern "C" void afv_launch_lba_finish(const LbView *V, const DevLbaFinish *F, hipStream_t stream);
+
 // ---- k_init.hip: Initializer::Initialize between two resident frames (host side: afv_init.hip) ----
 #define AFV_INIT_PREP_T 256  // lanes of k_init_prepare (I5: the width of Normalize's partial sums)
 #define AFV_INIT_REC_T 512   // lanes of k_init_reconstruct: 8 wavefronts over the 8 motion hypotheses of H or the 4 of F

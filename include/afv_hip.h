@@ -947,6 +947,87 @@ int afv_table_optimize_sim3(afv_table *t, afv_points *points, const int32_t *slo
  * it.  Only afv_table_optimize_sim3 reads it. */
 int afv_table_set_inf(afv_table *t, int set, const float *inf);
 
+/* ---- Bundle adjustment: Optimizer::LocalBundleAdjustment (src/Optimizer.cc:450-768, as LocalMapping calls it after every keyframe) and
+ * Optimizer::BundleAdjustment (:61-243: the two-keyframe BA of the monocular start-up, global BA) over slots of the keyframe table and
+ * ids of the map-point store.  Everything the routines read is resident: mvKeysUn, mvuRight and GetKeyPt2DInf of every keyframe (the
+ * table's geometry, u_right and information planes), GetWorldPos and isBad of every point (the store).
+ * The normative semantics are tests/_lba_ref.py (double, one rounding per operator, every operator order fixed there); the device is held
+ * to it bit for bit.  g2o is not shipped by the reference, so what it runs (EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ with both
+ * Jacobians, BaseBinaryEdge::constructQuadraticForm, BlockSolver_6_3 with the points marginalised, OptimizationAlgorithmLevenberg) is
+ * restated after upstream g2o as bundled with ORB-SLAM2 - parity with a real g2o is UNPINNED.
+ * The first n_free keyframes are optimised, the others are fixed (the host puts keyId == 0 and lFixedCameras there).  Edge e joins point
+ * obs_point[e] (a position in point_ids) with feature obs_idx[e] of keyframe obs_kf[e] (a position in slots), in the order in which the
+ * reference adds edges (per point, per observation): obs_point is ascending.  A feature is a stereo edge when its u_right >= 0; its
+ * information is diag(inf, inf, 0.5f * (inf + inf)) (GetKeyPt3DInf), a mono edge's inf * I2.  A point id that is unset or bad in the
+ * store drops the point and its edges (:475-476).
+ * params.checks = 1: LocalBundleAdjustment - optimize(iterations[0]) under the kernel if robust[0], the first check (level 1 on chi2 >
+ * 5.991 / 7.815 || !isDepthPositive), optimize(iterations[1]) with robust[1], the final check that fills vToErase; the reference's values
+ * are iterations {5, 10}, robust {1, 0}.  checks = 0: BundleAdjustment - one optimize(iterations[0]) with robust[0], no check.
+ * Quirk kept (L-Q1): the final check visits the edges removed by the first check too, with the chi2 of the first check (upstream caches
+ * _error) and the depth test at the final estimate - an edge removed for depth alone can survive (AFV_LBA_EDGE_REMOVED_KEPT).
+ * The launches (csrc/k_lba.hip): one gather per call; per iteration k_lba_linearise (a lane per edge), k_lba_build (a wavefront per free
+ * keyframe, a lane per point), k_lba_begin; per trial k_lba_invert (a lane per point), k_lba_schur (a wavefront per block of the reduced
+ * system), k_lba_solve (one workgroup: dense L L^T of at most 384 x 384), k_lba_step, k_lba_trial, k_lba_judge, then ONE wait in which
+ * the host reads the status record (a few dozen bytes) and the stop flag - exactly where g2o's terminate() stands.  The accept / reject
+ * decision, lambda and ni are the device's; the host only follows them.  No spinning flag, no cooperative launch, no captured graph.
+ * Deliberate deviations from upstream (the numbering of tests/_lba_ref.py, where the full text is):
+ *   L1  both checks are made at the accepted estimate (P1 / O1)      L2  a chi2 that is not finite is an outlier
+ *   L3  the state is R, t in double, no quaternion                   L4  no libm (P4's Horner tables); a step beyond pi is a failed trial
+ *   L5  every sum has one fixed shape: per keyframe (Hpp, bp, the Schur sums of block row i) 64 strided partial sums over that keyframe's
+ *       edges in list order, then p[l] += p[l + s], s = 32 .. 1; per point (Hll, bl, the back substitution) its edges one after the
+ *       other; the chi2 and scale sums the same 64-partial tree over the edge list and over the unknowns (poses, then points)
+ *   L6  Hll^-1 by cofactors in a fixed order; a determinant that is 0 or not finite is a failed trial
+ *   L7  the reduced system is solved by a dense, unpivoted L L^T in the order of the free-keyframe list, element (i, j) subtracting its
+ *       products in ascending k (forward substitution ascending, back substitution descending); a pivot that is not positive and
+ *       finite is a failed trial.  A vertex without active edges stays in the system: its block holds lambda alone, its step is 0
+ *   L8  a problem without free keyframes, without points or without (active) edges evaluates nothing
+ *   L9  what is not written reads 0: xyz_out of a dropped point, the trace of a round that did not run
+ * The stop flag: stop_flag (a host variable, or NULL) is read before the call, before every iteration, after every trial and before the
+ * first check; params.trial_budget > 0 raises it deterministically from the moment that many trials have run.  Raised before the call
+ * with checks = 1: the return at :645-647 - results holds stopped = 1 and zeros, nothing else is written, the store is unchanged.
+ * Raised during the first optimize(): bDoMore = false - the first check and the second optimize() are skipped, the final check and
+ * the write-back run.
+ * What the host still does: EraseMapPointMatch / EraseObservation for every edge in state AFV_LBA_EDGE_ERASE, SetPose from kf_out, and
+ * UpdateNormalAndDepth of the moved points (afv_points_set with the new normal and distances) stay with the host's map.
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+#define AFV_LBA_MAX_FREE 64
+#define AFV_LBA_MAX_KF 256
+#define AFV_LBA_MAX_POINTS 32768
+#define AFV_LBA_MAX_EDGES 262144
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(afv_lba_cam) */
+    float Rcw[9], tcw[3];                    /* GetPose(), row-major */
+    float fx, fy, cx, cy, bf;                /* bf = mbf (read by stereo edges only) */
+} afv_lba_cam;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(afv_lba_params) */
+    int32_t iterations[2], robust[2];        /* per optimize() call */
+    int32_t checks;                          /* 1: LocalBundleAdjustment's two checks; 0: BundleAdjustment, one round */
+    int32_t write_points;                    /* 1: the store receives (float)xyz_out (SetWorldPos); 0: it stays (the nLoopKF != 0 path) */
+    int32_t trial_budget;                    /* 0: none; k: the stop flag reads raised once k trials have run */
+} afv_lba_params;
+typedef struct {
+    int32_t iterations[2], trials[2];        /* per optimize() call */
+    int32_t n_edges, n_removed_first, n_erase;
+    int32_t stopped;                         /* 0 no; 1 before the call; 2 in the first optimize(); 3 in the second */
+    double chi2[2], lambda[2];               /* the robust chi2 and lambda each optimize() call ended with */
+} afv_lba_result;
+#define AFV_LBA_EDGE_DROPPED 0       /* its point is unset or bad in the store */
+#define AFV_LBA_EDGE_KEPT 1
+#define AFV_LBA_EDGE_REMOVED_KEPT 2  /* removed by the first check, not in vToErase (L-Q1) */
+#define AFV_LBA_EDGE_ERASE 3         /* in vToErase */
+/* slots[nk], cams[nk], point_ids[np], obs_point / obs_kf / obs_idx[ne] (host).  Outputs (host): results[1], kf_out[n_free][12] (R
+ * row-major, t; double), xyz_out[np][3] (double; the store receives the float cast when write_points), edge_state[ne].
+ * Refused before any launch, outputs untouched: AFV_EINVAL for a NULL argument, an unknown struct_size, nk > AFV_LBA_MAX_KF, n_free >
+ * min(nk, AFV_LBA_MAX_FREE), np > AFV_LBA_MAX_POINTS, ne > AFV_LBA_MAX_EDGES or a negative count, iterations below 0, robust / checks /
+ * write_points other than 0 / 1, a negative trial_budget, a slot out of range or one holding features without geometry or without the
+ * information plane, a store of another context, a point id outside [0, capacity) or named twice, obs_point / obs_kf / obs_idx out of
+ * range, edges not grouped by point (obs_point descending somewhere), a point observed twice by one keyframe.  Descriptors are not read. */
+int afv_table_bundle_adjust(afv_table *t, afv_points *points, const int32_t *slots, int nk, int n_free, const afv_lba_cam *cams,
+                            const int32_t *point_ids, int np, const int32_t *obs_point, const int32_t *obs_kf, const int32_t *obs_idx, int ne,
+                            const afv_lba_params *params, const volatile int32_t *stop_flag, afv_lba_result *results, double *kf_out,
+                            double *xyz_out, uint8_t *edge_state);
+
 /* ---- Initializer: monocular start-up between two resident frames (src/Initializer.cc:41-908, as Tracking::MonocularInitialization calls
  * it, src/Tracking.cc:487).  One synchronous call does what Initializer::Initialize does, from matches12 (what
  * afv_frame_match_initialization answers) to (R21, t21, vP3D, vbTriangulated): one upload, three launches on the context's stream, one
