@@ -14,6 +14,8 @@ Layout:
   sim3.py        Sim3Solver mirror: all RANSAC hypotheses of a loop check in one device call (reference: Sim3Solver.{h,cc});
                  OptimizeSim3 / OptimizeSim3Batch: Optimizer::OptimizeSim3 for every candidate in one device call
   lba.py         LocalBundleAdjustment / BundleAdjustment over table slots and store ids (reference: Optimizer.cc:450-768, :61-243)
+  refresh.py     RefreshMapPoints: ComputeDistinctiveDescriptors and UpdateNormalAndDepth of resident map points from the observation list
+                 of the bundle adjustment (reference: MapPoint.cc:279-349, :372-418)
   pnp.py         PnPsolver mirror: all EPnP RANSAC hypotheses of a relocalisation in one device call (reference: PnPsolver.{h,cc})
   initializer.py Initializer mirror: H and F RANSAC and the reconstruction in one device call (reference: Initializer.{h,cc})
   synth.py       bit-reproducible synthetic inputs
@@ -31,5 +33,7 @@ from .lba import BundleAdjustment, LocalBundleAdjustment  # noqa: F401
 from .initializer import Initializer  # noqa: F401
 from .pnp import PnPsolver  # noqa: F401
 from .akaze import AkazeContext  # noqa: F401
-from .matcher import (FeatureMatcher, FeatureView, FrameGridView, ProjectionQueries, ComputeDistinctiveDescriptors,  # noqa: F401
+from .matcher import (FeatureMatcher, FeatureView, FrameGridView, ProjectionQueries,  # noqa: F401
                       DescriptorDistance_orb32, DescriptorDistance_sift128)
+# ComputeDistinctiveDescriptors(ctx, descriptor_sets) stays the form over host rows (matcher.py); with a table in front it is the resident one
+from .refresh import (ComputeDistinctiveDescriptors, RefreshAfterBundleAdjustment, RefreshMapPoints, UpdateNormalAndDepth)  # noqa: F401

@@ -193,6 +193,19 @@ LBA_MAX_FREE, LBA_MAX_KF, LBA_MAX_POINTS, LBA_MAX_EDGES = 64, 256, 32768, 262144
 LBA_EDGE_DROPPED, LBA_EDGE_KEPT, LBA_EDGE_REMOVED_KEPT, LBA_EDGE_ERASE = 0, 1, 2, 3
 
 
+class RefreshParams(C.Structure):
+    """afv_refresh_params: which parts afv_table_refresh_points runs"""
+    _fields_ = [("struct_size", C.c_uint32), ("descriptors", C.c_int32), ("normals", C.c_int32)]
+
+
+class RefreshOut(C.Structure):
+    """afv_refresh_out: the host outputs of afv_table_refresh_points, any of which may be NULL"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("status", C.c_void_p), ("best_obs", C.c_void_p), ("best_median", C.c_void_p)]
+
+
+REFRESH_DONE, REFRESH_SKIPPED, REFRESH_NO_OBSERVATIONS, REFRESH_NO_REF, REFRESH_BAD_DISTANCE = 0, 1, 2, 3, 4
+
+
 class PnpJob(C.Structure):
     """afv_pnp_job: one candidate of afv_frame_pnp_hypotheses"""
     _fields_ = [("struct_size", C.c_uint32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("min_inliers", C.c_int32),
@@ -358,6 +371,8 @@ SYMBOLS = {
     "afv_table_optimize_sim3": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Sim3OptJob), _i, _vp, _vp, _vp, C.POINTER(Sim3OptResult), _vp]),
     "afv_table_bundle_adjust": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(LbaCam), _vp, _i, _vp, _vp, _vp, _i, C.POINTER(LbaParams), _vp,
                                      C.POINTER(LbaResult), _vp, _vp, _vp]),
+    "afv_table_refresh_points": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(RefreshParams),
+                                      C.POINTER(RefreshOut)]),
     "afv_table_set_inf": (_i, [_vp, _i, _vp]),
     "afv_frame_initializer": (_i, [_vp, _vp, C.POINTER(InitJob), _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp,
                                    C.POINTER(InitTrace), _vp, _vp, _vp, _vp, _i]),

@@ -1428,7 +1428,8 @@ inline int OptimizeSim3(afv_ctx *ctx, afv_table *table, int cap, DeviceMapPoints
 // ---- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:450-768) and Optimizer::BundleAdjustment (:61-243): ONE afv_table_bundle_adjust
 // call over slots of the keyframe table and ids of the map-point store (include/afv_hip.h, "Bundle adjustment": quirk L-Q1, deviations
 // L1-L9).  The slots hold the keyframes' mvKeysUn, mvuRight and GetKeyPt2DInf.  What stays with the host's map after a call:
-// EraseMapPointMatch / EraseObservation for every pair of vToErase, SetPose from `poses`, UpdateNormalAndDepth of the moved points.
+// EraseMapPointMatch / EraseObservation for every pair of vToErase and SetPose from `poses`; UpdateNormalAndDepth of the moved points is
+// RefreshAfterBundleAdjustment below, on the device.
 struct BundleKeyFrame {  // a keyframe of the problem: its slot, whether its vertex is fixed (keyId == 0, lFixedCameras), GetPose(), intrinsics
     int32_t slot;
     bool fixed;
@@ -1524,6 +1525,108 @@ inline BundleAnswer BundleAdjustment(afv_ctx *ctx, afv_table *table, DeviceMapPo
                                      const std::vector<int32_t> &point_ids, const std::vector<BundleObservation> &observations, int nIterations = 5,
                                      const volatile int32_t *pbStopFlag = nullptr, bool bRobust = true, bool write_points = true) {
     return BundleAdjust(ctx, table, points, kfs, point_ids, observations, nIterations, 0, bRobust, false, false, write_points, pbStopFlag);
+}
+
+// ---- MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:279-349) and MapPoint::UpdateNormalAndDepth (:372-418) of resident points:
+// ONE afv_table_refresh_points call over the observation list of the bundle adjustment (include/afv_hip.h, "Refresh of resident map
+// points": deviations R1-R3).  What stays with the host's map after a call: refKeyframe / refIndex of every point, from best_obs.
+struct RefreshKeyFrame {  // a keyframe some observation names: its slot, GetCameraCenter(), maxKeyPtSize, isBad()
+    int32_t slot;
+    float centre[3], maxKeyPtSize;
+    bool bad;
+};
+struct RefreshAnswer {
+    std::vector<int32_t> status;       // AFV_REFRESH_* per point
+    std::vector<int32_t> best_obs;     // the index into `observations` of the winning row | -1
+    std::vector<int32_t> best_median;  // an int for binary tables, the bits of the float for float tables
+};
+// ref_slot[p]: the slot of mpRefKF of point_ids[p] | -1
+inline RefreshAnswer RefreshMapPoints(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<RefreshKeyFrame> &kfs,
+                                      const std::vector<int32_t> &point_ids, const std::vector<int32_t> &ref_slot,
+                                      const std::vector<BundleObservation> &observations, bool descriptors = true, bool normals = true) {
+    const size_t nk = kfs.size(), np = point_ids.size(), ne = observations.size();
+    if (ref_slot.size() != np) fatal("RefreshMapPoints: one ref keyframe per point is expected", AFV_EINVAL, ctx);
+    std::vector<int32_t> slots(std::max<size_t>(nk, 1), 0), ids(std::max<size_t>(np, 1), 0), ref(std::max<size_t>(np, 1), -1);
+    std::vector<float> centres(std::max<size_t>(nk, 1) * 3, 0.0f), max_size(std::max<size_t>(nk, 1), 1.0f);
+    std::vector<uint8_t> bad(std::max<size_t>(nk, 1), 0);
+    std::map<int32_t, int32_t> where_k, where_p;
+    for (size_t k = 0; k < nk; ++k) {
+        slots[k] = kfs[k].slot;
+        where_k[kfs[k].slot] = (int32_t)k;
+        std::memcpy(&centres[3 * k], kfs[k].centre, sizeof(kfs[k].centre));
+        max_size[k] = kfs[k].maxKeyPtSize;
+        bad[k] = kfs[k].bad ? 1 : 0;
+    }
+    for (size_t p = 0; p < np; ++p) {
+        ids[p] = point_ids[p];
+        where_p[point_ids[p]] = (int32_t)p;
+        const auto ik = where_k.find(ref_slot[p]);
+        ref[p] = ik == where_k.end() ? -1 : ik->second;
+    }
+    // the observations grouped by point in the order of point_ids; the observations of a point keep their order
+    std::vector<size_t> eo(ne);
+    for (size_t e = 0; e < ne; ++e) eo[e] = e;
+    std::vector<int32_t> pos_p(ne), pos_k(ne);
+    for (size_t e = 0; e < ne; ++e) {
+        const auto ip = where_p.find(observations[e].point);
+        const auto ik = where_k.find(observations[e].slot);
+        if (ip == where_p.end() || ik == where_k.end()) fatal("RefreshMapPoints: an observation names a point or keyframe outside the call", AFV_EINVAL, ctx);
+        pos_p[e] = ip->second;
+        pos_k[e] = ik->second;
+    }
+    std::stable_sort(eo.begin(), eo.end(), [&](size_t a, size_t b) { return pos_p[a] < pos_p[b]; });
+    std::vector<int32_t> op(std::max<size_t>(ne, 1), 0), ok(std::max<size_t>(ne, 1), 0), oi(std::max<size_t>(ne, 1), 0);
+    for (size_t e = 0; e < ne; ++e) { op[e] = pos_p[eo[e]]; ok[e] = pos_k[eo[e]]; oi[e] = observations[eo[e]].idx; }
+    RefreshAnswer A;
+    A.status.assign(std::max<size_t>(np, 1), 0);
+    A.best_obs.assign(std::max<size_t>(np, 1), -1);
+    A.best_median.assign(std::max<size_t>(np, 1), 0);
+    afv_refresh_params prm;
+    std::memset(&prm, 0, sizeof(prm));
+    prm.struct_size = (uint32_t)sizeof(prm);
+    prm.descriptors = descriptors ? 1 : 0;
+    prm.normals = normals ? 1 : 0;
+    afv_refresh_out out;
+    std::memset(&out, 0, sizeof(out));
+    out.struct_size = (uint32_t)sizeof(out);
+    out.status = A.status.data(); out.best_obs = A.best_obs.data(); out.best_median = A.best_median.data();
+    const int rc = afv_table_refresh_points(table, points.handle(), slots.data(), (int)nk, centres.data(), max_size.data(), bad.data(), ids.data(), (int)np,
+                                            ref.data(), op.data(), ok.data(), oi.data(), (int)ne, &prm, &out);
+    if (rc != AFV_OK) fatal("afv_table_refresh_points", rc, ctx);
+    A.status.resize(np); A.best_obs.resize(np); A.best_median.resize(np);
+    for (int32_t &b : A.best_obs)
+        if (b >= 0) b = (int32_t)eo[(size_t)b];
+    return A;
+}
+// GetCameraCenter() after KeyFrame::SetPose (src/KeyFrame.cc:81-84): twc = -Rwc * tcw in float, a0 + (a1 + a2)
+inline void CameraCentre(const float *Rcw, const float *tcw, float *centre) {
+    for (int k = 0; k < 3; ++k) centre[k] = -Rcw[k] * tcw[0] + (-Rcw[3 + k] * tcw[1] + -Rcw[6 + k] * tcw[2]);
+}
+// What Optimizer::LocalBundleAdjustment / BundleAdjustment do after the write-back (Optimizer.cc:753-767, :207-234): `answer` is what
+// afv::LocalBundleAdjustment returned for `kfs`; an optimised keyframe's centre is formed from the float cast of its new pose
+// (Converter::toMatrix4f, then SetPose), a fixed one's from the pose it was given.  maxKeyPtSize[k] / bad[k] belong to kfs[k] (bad may be
+// empty).  The normal part alone unless descriptors is set.
+inline RefreshAnswer RefreshAfterBundleAdjustment(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<BundleKeyFrame> &kfs,
+                                                  const BundleAnswer &answer, const std::vector<float> &maxKeyPtSize, const std::vector<uint8_t> &bad,
+                                                  const std::vector<int32_t> &point_ids, const std::vector<int32_t> &ref_slot,
+                                                  const std::vector<BundleObservation> &observations, bool descriptors = false) {
+    if (maxKeyPtSize.size() != kfs.size()) fatal("RefreshAfterBundleAdjustment: one maxKeyPtSize per keyframe is expected", AFV_EINVAL, ctx);
+    std::vector<RefreshKeyFrame> rk(kfs.size());
+    for (size_t k = 0; k < kfs.size(); ++k) {
+        float R[9], t[3];
+        std::memcpy(R, kfs[k].Rcw, sizeof(R));
+        std::memcpy(t, kfs[k].tcw, sizeof(t));
+        for (const auto &moved : answer.poses)
+            if (moved.first == kfs[k].slot) {
+                for (int q = 0; q < 9; ++q) R[q] = (float)moved.second.R[q];
+                for (int q = 0; q < 3; ++q) t[q] = (float)moved.second.t[q];
+            }
+        rk[k].slot = kfs[k].slot;
+        CameraCentre(R, t, rk[k].centre);
+        rk[k].maxKeyPtSize = maxKeyPtSize[k];
+        rk[k].bad = k < bad.size() && bad[k] != 0;
+    }
+    return RefreshMapPoints(ctx, table, points, rk, point_ids, ref_slot, observations, descriptors, true);
 }
 
 // ---- PnPsolver (include/PnPsolver.h, src/PnPsolver.cc) as Tracking::Relocalization uses it (src/Tracking.cc:1190-1216): Batch makes ONE

@@ -282,6 +282,26 @@ extern "C" void afv_launch_lba_trial(const LbView *V, hipStream_t stream);      
 extern "C" void afv_launch_lba_check(const LbView *V, int final_check, hipStream_t stream);
 extern "C" void afv_launch_lba_finish(const LbView *V, const DevLbaFinish *F, hipStream_t stream);
 
+// ---- k_refresh.hip: ComputeDistinctiveDescriptors / UpdateNormalAndDepth of resident map points (host side: afv_refresh.hip) ----
+struct DevRefresh {          // a kernel argument of both launches
+    DevPointPlanes P;        // the store, written in place
+    const uint8_t *desc;     // the table's rows [nsets][cap][4 * words]
+    const float *sigma2;     // the table's sigma2 plane [nsets][cap]
+    const float *size;       // the table's keyPtsSize plane [nsets][cap] (normals only)
+    int cap, desc_bytes, float_dim;
+    const int *slots;        // [nk]
+    const float *centres, *max_size;  // [nk][3], [nk]
+    const uint8_t *kf_bad;   // [nk]
+    const int *point_ids, *ref_kf, *pt_ptr;  // [np], [np], [np + 1]
+    const int *obs_kf, *obs_idx;      // [ne]
+    int np;
+    int *c_row, *c_obs;      // [ne] scratch: table row and observation of the c-th good observation of a point, at pt_ptr[p] + c
+    int *status, *best_obs, *best_median;  // [np]
+    int desc_writes_status;  // the descriptor launch is the only one
+};
+extern "C" void afv_launch_refresh_desc(const DevRefresh *A, hipStream_t stream);
+extern "C" void afv_launch_refresh_normals(const DevRefresh *A, hipStream_t stream);
+
 // ---- k_init.hip: Initializer::Initialize between two resident frames (host side: afv_init.hip) ----
 #define AFV_INIT_PREP_T 256  // lanes of k_init_prepare (I5: the width of Normalize's partial sums)
 #define AFV_INIT_REC_T 512   // lanes of k_init_reconstruct: 8 wavefronts over the 8 motion hypotheses of H or the 4 of F

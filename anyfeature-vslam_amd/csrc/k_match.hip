@@ -20,6 +20,7 @@
 #include "afv_runtime.h"  // the launchers below are declared there: a signature that drifts is a compile error, not a silent ABI mismatch
 #include "afv_jobs.h"
 #include "k_tri_row.h"
+#include "k_median.h"
 
 
 #include <type_traits>
@@ -1298,7 +1299,7 @@ extern "C" void afv_launch_match_topk(const uint8_t *desc, const int *nset, int 
 // Per map point: the N x N Hamming distances of its N observed descriptors, per row the median = the floor(0.5 (N - 1))-th smallest
 // entry (the row sorted, MapPoint.cc:329-331; the self-distance 0 is part of the row), the row with the least median wins, first one on
 // ties (strict <, :333).  One wavefront per map point, lane = row (rows in chunks of 64); nothing is sorted or stored: the m-th smallest of a
-// row of integers in [0, 8 * bytes] is found by bisection on the VALUE - count(d < mid) against m - recomputing the row's distances in each
+// row of integers in [0, 8 * bytes] is found by bisection on the VALUE (afv_bisect_mth, k_median.h) - recomputing the row's distances in each
 // of the <= 10 steps (N = 20 observations: 10 x 20 x 8 xor + popcount per lane; the other rows' descriptors are the same address in all lanes).
 template <int W>
 __global__ __launch_bounds__(256) void k_distinctive(const uint32_t *__restrict__ desc, const int *__restrict__ set_ptr, int nsets, int max_dist,
@@ -1320,24 +1321,18 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint32_t *__restrict_
         uint32_t q[W];
 #pragma unroll
         for (int w = 0; w < W; ++w) q[w] = desc[(size_t)(b + min(i, n - 1)) * W + w];
-        // smallest v with count(d <= v) > m  <=>  the m-th smallest (0-based) value
-        int lo = 0, hi = max_dist;  // answer in [lo, hi]
-        while (__any(lo < hi)) {
-            const int mid = (lo + hi) >> 1;
+        const unsigned lo = afv_bisect_mth(0u, (unsigned)max_dist, m, [&](unsigned mid) {
             int cnt = 0;  // #{j : d(i, j) <= mid}
             for (int j = 0; j < n; ++j) {
                 const uint32_t *r = desc + (size_t)(b + j) * W;
                 int d = 0;
 #pragma unroll
                 for (int w = 0; w < W; ++w) d += __popc(q[w] ^ r[w]);
-                cnt += d <= mid;
+                cnt += (unsigned)d <= mid;
             }
-            if (lo < hi) {
-                if (cnt > m) hi = mid;
-                else lo = mid + 1;
-            }
-        }
-        if (i < n) best = min(best, ((unsigned)lo << 16) | (unsigned)i);
+            return cnt;
+        });
+        if (i < n) best = min(best, (lo << 16) | (unsigned)i);
     }
     // wave minimum of (median, row): the least median, the first row on ties
     const unsigned g = afv_wave_min_u32(best);
@@ -1374,30 +1369,24 @@ __global__ __launch_bounds__(256) void k_distinctive_f32(const float *__restrict
         const float *q = desc + (size_t)(b + min(i, n - 1)) * dim;
         if (cached)
             for (int j = 0; j < n; ++j) s_d[wv][j][lane] = __float_as_uint(l2sqr(q, desc + (size_t)(b + j) * dim, dim));  // (the diagonal: 0)
-        unsigned lo = 0u, hi = 0x7f800000u;  // smallest key v with #{j : key(d(i, j)) <= v} > m  <=>  the m-th smallest (0-based) distance
-        while (__any(lo < hi)) {
-            const unsigned mid = lo + ((hi - lo) >> 1);
+        const unsigned lo = afv_bisect_mth(0u, 0x7f800000u, m, [&](unsigned mid) {
             int cnt = 0;
             if (cached)
                 for (int j = 0; j < n; ++j) cnt += s_d[wv][j][lane] <= mid;
             else
                 for (int j = 0; j < n; ++j) cnt += __float_as_uint(l2sqr(q, desc + (size_t)(b + j) * dim, dim)) <= mid;
-            if (lo < hi) {
-                if (cnt > m) hi = mid;
-                else lo = mid + 1u;
-            }
-        }
+            return cnt;
+        });
         if (i < n && lo < best_med) {  // strict: the first row keeps a tie (rows ascend with i0 inside a lane)
             best_med = lo;
             best_row = (unsigned)i;
         }
     }
     // the least median over the lanes, then the first row that has it
-    const unsigned gm = afv_wave_min_u32(best_med);
-    const unsigned gr = afv_wave_min_u32(best_med == gm ? best_row : 0xffffffffu);
+    const AfvBestRow g = afv_wave_best_row(best_med, best_row);
     if (lane == 0) {
-        best_idx[s] = (int)gr;
-        best_median[s] = __uint_as_float(gm);
+        best_idx[s] = (int)g.row;
+        best_median[s] = __uint_as_float(g.median);
     }
 }
 extern "C" void afv_launch_distinctive_f32(const float *desc, int dim, const int *set_ptr, int nsets, int *best_idx, float *best_median, hipStream_t stream) {

@@ -2,8 +2,8 @@
 and ids of the map-point store: afv_table_bundle_adjust (csrc/k_lba.hip).  Normative semantics, the quirk L-Q1 and the deviations L1-L9:
 tests/_lba_ref.py and include/afv_hip.h ("Bundle adjustment").
 
-What stays with the host's map after a call: EraseMapPointMatch / EraseObservation for every pair in to_erase, SetPose from the returned
-poses, UpdateNormalAndDepth of the moved points (MapPoints.set with the new normal and distances).
+What stays with the host's map after a call: EraseMapPointMatch / EraseObservation for every pair in to_erase and SetPose from the
+returned poses.  UpdateNormalAndDepth of the moved points is refresh.RefreshAfterBundleAdjustment, on the device, over the same observations.
 """
 import ctypes as C
 

@@ -987,8 +987,9 @@ int afv_table_set_inf(afv_table *t, int set, const float *inf);
  * with checks = 1: the return at :645-647 - results holds stopped = 1 and zeros, nothing else is written, the store is unchanged.
  * Raised during the first optimize(): bDoMore = false - the first check and the second optimize() are skipped, the final check and
  * the write-back run.
- * What the host still does: EraseMapPointMatch / EraseObservation for every edge in state AFV_LBA_EDGE_ERASE, SetPose from kf_out, and
- * UpdateNormalAndDepth of the moved points (afv_points_set with the new normal and distances) stay with the host's map.
+ * What the host still does: EraseMapPointMatch / EraseObservation for every edge in state AFV_LBA_EDGE_ERASE and SetPose from kf_out stay
+ * with the host's map.  UpdateNormalAndDepth of the moved points no longer does: afv_table_refresh_points (below) takes the same
+ * observation arrays and refreshes the store on the device.
  * New symbols and records only: AFV_ABI_VERSION stays 6. */
 #define AFV_LBA_MAX_FREE 64
 #define AFV_LBA_MAX_KF 256
@@ -1027,6 +1028,64 @@ int afv_table_bundle_adjust(afv_table *t, afv_points *points, const int32_t *slo
                             const int32_t *point_ids, int np, const int32_t *obs_point, const int32_t *obs_kf, const int32_t *obs_idx, int ne,
                             const afv_lba_params *params, const volatile int32_t *stop_flag, afv_lba_result *results, double *kf_out,
                             double *xyz_out, uint8_t *edge_state);
+
+/* ---- Refresh of resident map points from their observations: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:279-349) and
+ * MapPoint::UpdateNormalAndDepth (:372-418) for a batch of points, every row and every plane read where it is resident (the keyframe
+ * table, the store).  The reference calls the two after BundleAdjustment (Optimizer.cc:234), LocalBundleAdjustment (:766) and
+ * OptimizeEssentialGraph (:1029), at the end of SearchInNeighbors (LocalMapping.cc:547-548), in CorrectLoop (LoopClosing.cc:515) and
+ * when an observation is added, erased or replaced (MapPoint.cc:120 / :172 / :249).
+ * The observation arrays have the format and order of afv_table_bundle_adjust: grouped by point, obs_point ascending (a position in
+ * point_ids), obs_kf a position in slots, and inside a point the order of the reference's map<KeyframeId, Obs>.  centres[k] is
+ * GetCameraCenter() of keyframe k as the host computes it (the rule of afv_frame_set_pose for Ow), max_size[k] its maxKeyPtSize,
+ * kf_bad[k] (NULL: none) its isBad(), ref_kf[p] the position of mpRefKF of point p in slots.
+ * The normative semantics are tests/_refresh_ref.py (float, one rounding per operator); the device is held to it bit for bit.
+ * A point that is unset or bad in the store is skipped by both parts, and so is a point without observations.
+ * params.descriptors = 1: the observations of keyframes that are not kf_bad, in list order, are the N rows; per row the median =
+ *   the floor(0.5 (N - 1))-th smallest of its N distances (its own 0 included); the least median wins, the first row on a tie; the
+ *   distance is Hamming over desc_bytes (pad bytes are not counted) or, for float tables, cv::norm(NORM_L2SQR) as a float.  The winning
+ *   row is copied into the store device to device (the semantics of afv_points_set_descriptors_from_table); N = 0 leaves the row as it is.
+ * params.normals = 1: EVERY observation contributes, bad keyframes too (the routine does not test isBad):
+ *   normal = (0.0f + n_0 / |n_0| + ...) / n summed in list order; ref_distance = |XYZ - centre(ref)|; ref_size = the table's keyPtsSize
+ *   of the ref keyframe's observation; ref_sigma = sqrtf(its sigma2); max_distance = ref_distance * ref_size; min_distance =
+ *   max_distance / max_size[ref].  It reads mpRefKF (ref_kf), NOT the refKeyframe the descriptor part has just chosen: the reference
+ *   keeps two reference keyframes, and so does this.
+ * Deliberate deviations:
+ *   R1  a point whose ref_kf is -1, or which ref_kf does not observe, answers AFV_REFRESH_NO_REF and its normal part is not written (the
+ *       reference would dereference a null Obs)
+ *   R2  a point with an observation at distance 0 or at a distance that is not finite answers AFV_REFRESH_BAD_DISTANCE and its normal
+ *       part is not written (R1 is tested first)
+ *   R3  what is not written reads 0 in the host outputs (best_obs: -1)
+ * The planes and the row of a skipped point are untouched, and so is every point the call does not name.
+ * One upload, one launch per part (csrc/k_refresh.hip: a wavefront per point) on the context's stream, one wait.  No atomics.
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(afv_refresh_params) */
+    int32_t descriptors;                     /* 1: ComputeDistinctiveDescriptors */
+    int32_t normals;                         /* 1: UpdateNormalAndDepth */
+} afv_refresh_params;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(afv_refresh_out) */
+    int32_t reserved;
+    int32_t *status;                         /* [np] AFV_REFRESH_*; host arrays, any of which may be NULL */
+    int32_t *best_obs;                       /* [np] the position in the observation arrays of the winning row: the host sets refKeyframe /
+                                              * refIndex from it; -1: nothing was chosen */
+    int32_t *best_median;                    /* [np] its median: an int32 for binary tables, the bits of the float for float tables */
+} afv_refresh_out;
+#define AFV_REFRESH_DONE 0           /* every part that was asked for was written (the descriptor part: unless N = 0) */
+#define AFV_REFRESH_SKIPPED 1        /* the point is unset or bad in the store */
+#define AFV_REFRESH_NO_OBSERVATIONS 2
+#define AFV_REFRESH_NO_REF 3         /* R1: the descriptor part ran, the normal part did not */
+#define AFV_REFRESH_BAD_DISTANCE 4   /* R2: likewise */
+/* slots[nk], centres[nk][3], max_size[nk], kf_bad[nk] | NULL, point_ids[np], ref_kf[np], obs_point / obs_kf / obs_idx[ne] (host).
+ * Refused before any launch, the store and the outputs untouched: AFV_EINVAL for a NULL argument (kf_bad and the members of out
+ * excepted), an unknown struct_size, descriptors / normals other than 0 / 1, nk > AFV_LBA_MAX_KF, np > AFV_LBA_MAX_POINTS, ne >
+ * AFV_LBA_MAX_EDGES or a negative count, a store of another context, a slot out of range or one holding features without geometry or
+ * (normals) without the scale plane, a point id outside [0, capacity) or named twice, ref_kf outside [-1, nk), obs_point / obs_kf /
+ * obs_idx out of range, observations not grouped by point, a point observed twice by one keyframe, more than 65535 observations of one
+ * point; AFV_EUNSUPPORTED for a store whose row kind or width is not the table's. */
+int afv_table_refresh_points(afv_table *t, afv_points *points, const int32_t *slots, int nk, const float *centres, const float *max_size,
+                             const uint8_t *kf_bad, const int32_t *point_ids, int np, const int32_t *ref_kf, const int32_t *obs_point,
+                             const int32_t *obs_kf, const int32_t *obs_idx, int ne, const afv_refresh_params *params, afv_refresh_out *out);
 
 /* ---- Initializer: monocular start-up between two resident frames (src/Initializer.cc:41-908, as Tracking::MonocularInitialization calls
  * it, src/Tracking.cc:487).  One synchronous call does what Initializer::Initialize does, from matches12 (what
