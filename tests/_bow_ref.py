@@ -19,7 +19,7 @@ depends on the rule the scene is named after.  The issue's `rule01` is the pair 
 """
 import numpy as np
 
-from _proj_ref import HISTO_LENGTH, hamming, l2sqr, rotation_bin, three_maxima
+from _proj_ref import DISTANCE, HISTO_LENGTH, hamming, l2sqr, rotation_bin, three_maxima  # noqa: F401  (l2sqr: used by the scene files)
 
 f32 = np.float32
 FLT_MAX = np.finfo(np.float32).max   # highestPossibleDistance (FeatureMatcher.h:116)
@@ -69,7 +69,7 @@ def _new_trace(n1):
 
 def _dist(D1, i, D2, idxs):
     rows = D2[np.asarray(idxs, np.int64)] if len(idxs) else D2[:0]
-    return l2sqr(D1[i], rows) if D1.dtype.kind == "f" else hamming(D1[i], rows)
+    return DISTANCE["l2sqr"](D1[i], rows) if D1.dtype.kind == "f" else hamming(D1[i], rows)
 
 
 def _rows(desc):

@@ -8,6 +8,7 @@ and that its outcome depends on it; tests/test_gpu_match_scenes.py runs them thr
 Descriptors are built from DISTANCES with row_at / rows / base_row of _proj_scenes.py: a KF1 row is the base row, a KF2 column the base
 with d bits flipped (binary) or an integer offset whose squares sum to d (float: every L2^2 is a small integer).  Rows that must pair up
 one to one (the rotation scenes) are `distinct` rows: 2 bits / L2^2 >= 1 apart from each other, 0 from their partner.
+(Small integer distances are exact in any summation order: the order of the float distance is tested in tests/_l2_scenes.py.)
 
 Each rule scene comes in three node shapes, one per kernel body behind afv_match_bow:
   single  no FeatureVector (or ONE shared node where the listed order matters)    k_match_bow, or the top-4 + resolve path when eligible

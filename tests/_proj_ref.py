@@ -95,10 +95,15 @@ def l2sqr(a, rows):
     return s.astype(np.float32)
 
 
+# the float distance every restatement built on this file evaluates (_bow_ref, _stereo_ref): tests/_l2_scenes.arithmetic() puts a wrong
+# arithmetic here to prove that a scene's outcome depends on the right one
+DISTANCE = {"l2sqr": l2sqr}
+
+
 def _distances(F, Q, q, idxs):
     rows = F.descriptors[np.asarray(idxs, np.int64)] if len(idxs) else F.descriptors[:0]
     if F.descriptors.dtype.kind == "f":
-        return l2sqr(Q.descriptors[q], rows)
+        return DISTANCE["l2sqr"](Q.descriptors[q], rows)
     return hamming(Q.descriptors[q], rows)
 
 

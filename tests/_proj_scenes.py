@@ -8,6 +8,7 @@ rule at equality and that its outcome depends on it; tests/test_gpu_proj_scenes.
 Descriptors are built from DISTANCES: a query is the `base` row, a feature is the base with `d` bits flipped (binary rows) or with an
 integer offset vector whose squares sum to `d` (float rows: every L2^2 is a small integer, exact in any summation order).  `variant`
 moves the flipped bits / permutes the offset, so that several features can sit at the same distance without being equal.
+(The summation order of the float distance is tested in tests/_l2_scenes.py, on rows that tell orders apart.)
 Coordinates that must sit exactly on an edge are found with np.nextafter against the expression the reference evaluates, in float32.
 """
 import collections

@@ -60,6 +60,11 @@ def l2sqr(a, b):
     return f32(s)
 
 
+# the float distance distinctive() evaluates: tests/_l2_scenes.arithmetic() puts a wrong arithmetic here (and in _proj_ref.DISTANCE) to
+# prove that a scene's outcome depends on the right one
+DISTANCE = {"l2sqr": l2sqr}
+
+
 def median_of_row(row):
     """vDists sorted, entry floor(0.5 * (N - 1)) - by counting, not sorting: the smallest v of the row with #{d <= v} > m"""
     row = np.asarray(row)
@@ -79,7 +84,7 @@ def distinctive(rows, float_rows, desc_bytes):
     D = [[(f32(0.0) if float_rows else 0)] * N for _ in range(N)]
     for i in range(N):
         for j in range(i + 1, N):
-            d = l2sqr(rows[i], rows[j]) if float_rows else hamming(rows[i], rows[j], desc_bytes)
+            d = DISTANCE["l2sqr"](rows[i], rows[j]) if float_rows else hamming(rows[i], rows[j], desc_bytes)
             D[i][j] = d
             D[j][i] = d
     best_idx, best_median = 0, None

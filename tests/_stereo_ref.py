@@ -35,7 +35,7 @@ import math
 
 import numpy as np
 
-from _proj_ref import hamming, l2sqr
+from _proj_ref import DISTANCE, hamming, l2sqr  # noqa: F401
 
 f32 = np.float32
 W = 5  # :567 const int w = 5
@@ -100,7 +100,7 @@ def c_round(v):
 def distance(a, b):
     """FeatureMatcher::DescriptorDistance (FeatureMatcher.cc:1508-1531) as Descriptor_Distance_Type = float"""
     if a.dtype.kind == "f":
-        return f32(l2sqr(a, b[None, :])[0])
+        return f32(DISTANCE["l2sqr"](a, b[None, :])[0])
     return f32(hamming(a, b[None, :])[0])
 
 
