@@ -16,6 +16,8 @@ Layout:
   lba.py         LocalBundleAdjustment / BundleAdjustment over table slots and store ids (reference: Optimizer.cc:450-768, :61-243)
   refresh.py     RefreshMapPoints: ComputeDistinctiveDescriptors and UpdateNormalAndDepth of resident map points from the observation list
                  of the bundle adjustment (reference: MapPoint.cc:279-349, :372-418)
+  essgraph.py    OptimizeEssentialGraph over plain arrays and the store, the edge list of the essential graph, the Sim3 point correction
+                 (reference: Optimizer.cc:771-1031, LoopClosing.cc:487-516)
   pnp.py         PnPsolver mirror: all EPnP RANSAC hypotheses of a relocalisation in one device call (reference: PnPsolver.{h,cc})
   initializer.py Initializer mirror: H and F RANSAC and the reconstruction in one device call (reference: Initializer.{h,cc})
   synth.py       bit-reproducible synthetic inputs
@@ -30,6 +32,7 @@ from . import akaze, table  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
 from .sim3 import OptimizeSim3, OptimizeSim3Batch, Sim3Solver  # noqa: F401
 from .lba import BundleAdjustment, LocalBundleAdjustment  # noqa: F401
+from .essgraph import OptimizeEssentialGraph, essential_graph_edges  # noqa: F401
 from .initializer import Initializer  # noqa: F401
 from .pnp import PnPsolver  # noqa: F401
 from .akaze import AkazeContext  # noqa: F401

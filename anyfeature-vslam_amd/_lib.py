@@ -193,6 +193,28 @@ LBA_MAX_FREE, LBA_MAX_KF, LBA_MAX_POINTS, LBA_MAX_EDGES = 64, 256, 32768, 262144
 LBA_EDGE_DROPPED, LBA_EDGE_KEPT, LBA_EDGE_REMOVED_KEPT, LBA_EDGE_ERASE = 0, 1, 2, 3
 
 
+class Sim3d(C.Structure):
+    """afv_sim3d: a Sim3 in double, R row-major; 13 doubles, the rows of a float64 [n, 13] array"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("s", C.c_double)]
+
+
+class EssParams(C.Structure):
+    """afv_ess_params: the driver of afv_essential_graph"""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("lambda_init", C.c_double), ("fix_scale", C.c_int32),
+                ("write_points", C.c_int32)]
+
+
+class EssResult(C.Structure):
+    """afv_ess_result: the trace of the one optimize() call"""
+    _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("chi2_first", C.c_double), ("chi2_last", C.c_double), ("lam", C.c_double),
+                ("l_blocks", C.c_int32), ("status", C.c_int32)]
+
+
+ESS_MAX_KF, ESS_MAX_EDGES, ESS_MAX_L_BLOCKS, ESS_MAX_UPDATES = 4096, 65536, 131072, 2097152
+ESS_OK, ESS_NOT_FINITE, ESS_EMPTY = 0, 1, 2
+POINT_MOVED, POINT_BAD_OR_UNSET, POINT_NO_PAIR = 0, 1, 2
+
+
 class RefreshParams(C.Structure):
     """afv_refresh_params: which parts afv_table_refresh_points runs"""
     _fields_ = [("struct_size", C.c_uint32), ("descriptors", C.c_int32), ("normals", C.c_int32)]
@@ -374,6 +396,9 @@ SYMBOLS = {
     "afv_table_refresh_points": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(RefreshParams),
                                       C.POINTER(RefreshOut)]),
     "afv_table_set_inf": (_i, [_vp, _i, _vp]),
+    "afv_essential_graph": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, C.POINTER(EssParams), _vp, _vp, _i, C.POINTER(EssResult), _vp, _vp, _vp,
+                                 _vp]),
+    "afv_points_correct_sim3": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "afv_frame_initializer": (_i, [_vp, _vp, C.POINTER(InitJob), _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _vp, _vp, _vp, _vp,
                                    C.POINTER(InitTrace), _vp, _vp, _vp, _vp, _i]),
     "afv_frame_pnp_hypotheses": (_i, [_vp, _vp, C.POINTER(PnpJob), _i, _vp, _i, _i] + [_vp] * 13),

@@ -1824,4 +1824,59 @@ class Initializer {
     DeviceFrame &ref;
 };
 
+// ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:771-1031) and the point correction of LoopClosing::CorrectLoop
+// (LoopClosing.cc:487-516): ONE afv_essential_graph / afv_points_correct_sim3 call each (include/afv_hip.h, "Essential graph": quirk G-Q1,
+// deviations G1-G11).  The caller lists the keyframes that are not bad in ascending keyId and the edges in the reference's order (:835-971);
+// what stays with the host's map: SetPose from Tiw (the float cast), UpdateNormalAndDepth of the moved points (RefreshMapPoints).
+struct EssentialGraphEdge {
+    int32_t v0, v1;        // positions in the keyframe list; v0 the vertex of setVertex(0, ...)
+    afv_sim3d measurement; // Sji
+};
+struct EssentialGraphAnswer {
+    std::vector<afv_sim3d> CorrectedSiw;  // the optimised estimate of every keyframe
+    std::vector<double> Tiw;              // [nk][12]: R row-major, t / s
+    std::vector<double> xyz;              // [np][3]; the store holds the float cast when write_points
+    std::vector<uint8_t> point_status;    // AFV_POINT_*
+    afv_ess_result trace;
+};
+// points may be nullptr when no point is corrected.  S_init: CorrectedSim3 of a keyframe or (Rcw, tcw, 1); fixed: the position of pLoopKF;
+// point_ref: per point the position of mnCorrectedReference (mnCorrectedByKF == pCurKF) or of mpRefKF in the keyframe list, -1 for none
+inline EssentialGraphAnswer OptimizeEssentialGraph(afv_ctx *ctx, DeviceMapPoints *points, const std::vector<afv_sim3d> &S_init, int fixed,
+                                                   const std::vector<EssentialGraphEdge> &edges, bool bFixScale, const std::vector<int32_t> &point_ids,
+                                                   const std::vector<int32_t> &point_ref, int nIterations = 20, double userLambdaInit = 1e-16,
+                                                   bool write_points = true) {
+    const size_t nk = S_init.size(), ne = edges.size(), np = point_ids.size();
+    if (point_ref.size() != np) fatal("OptimizeEssentialGraph: one reference per point is expected", AFV_EINVAL, ctx);
+    std::vector<int32_t> v0(std::max<size_t>(ne, 1), 0), v1(std::max<size_t>(ne, 1), 0);
+    std::vector<afv_sim3d> meas(std::max<size_t>(ne, 1));
+    for (size_t e = 0; e < ne; ++e) { v0[e] = edges[e].v0; v1[e] = edges[e].v1; meas[e] = edges[e].measurement; }
+    afv_ess_params prm;
+    std::memset(&prm, 0, sizeof(prm));
+    prm.struct_size = (uint32_t)sizeof(afv_ess_params);
+    prm.iterations = nIterations; prm.lambda_init = userLambdaInit; prm.fix_scale = bFixScale ? 1 : 0; prm.write_points = write_points ? 1 : 0;
+    EssentialGraphAnswer A;
+    std::memset(&A.trace, 0, sizeof(A.trace));
+    A.CorrectedSiw.resize(std::max<size_t>(nk, 1));
+    A.Tiw.assign(std::max<size_t>(nk, 1) * 12, 0.0);
+    A.xyz.assign(std::max<size_t>(np, 1) * 3, 0.0);
+    A.point_status.assign(std::max<size_t>(np, 1), 0);
+    const int rc = afv_essential_graph(ctx, points ? points->handle() : nullptr, S_init.data(), (int)nk, fixed, v0.data(), v1.data(), meas.data(), (int)ne,
+                                       &prm, point_ids.data(), point_ref.data(), (int)np, &A.trace, A.CorrectedSiw.data(), A.Tiw.data(), A.xyz.data(),
+                                       A.point_status.data());
+    if (rc != AFV_OK) fatal("afv_essential_graph", rc, ctx);
+    A.CorrectedSiw.resize(nk); A.Tiw.resize(nk * 12); A.xyz.resize(np * 3); A.point_status.resize(np);
+    return A;
+}
+// CorrectedSwi.map(Siw.map(P)) of every listed point in the store, in place: pair_of_point[i] names the (S_from, S_to) pair of point i, -1 none
+inline std::vector<uint8_t> CorrectPointsSim3(afv_ctx *ctx, DeviceMapPoints &points, const std::vector<int32_t> &ids, const std::vector<int32_t> &pair_of_point,
+                                              const std::vector<afv_sim3d> &S_from, const std::vector<afv_sim3d> &S_to) {
+    if (pair_of_point.size() != ids.size() || S_from.size() != S_to.size()) fatal("CorrectPointsSim3: mismatched arrays", AFV_EINVAL, ctx);
+    std::vector<uint8_t> status(std::max<size_t>(ids.size(), 1), 0);
+    const int rc = afv_points_correct_sim3(points.handle(), ids.data(), (int)ids.size(), pair_of_point.data(), S_from.data(), S_to.data(), (int)S_from.size(),
+                                           status.data());
+    if (rc != AFV_OK) fatal("afv_points_correct_sim3", rc, ctx);
+    status.resize(ids.size());
+    return status;
+}
+
 }  // namespace afv

@@ -89,6 +89,21 @@ class MapPoints:
         self.ctx.check(self.lib.afv_points_set_descriptors_from_table(self.handle, ptr(ids), len(ids), table.handle, ptr(sl), ptr(ix)),
                        "afv_points_set_descriptors_from_table")
 
+    def correct_sim3(self, ids, pair_of_point, S_from, S_to):
+        """The point correction of LoopClosing::CorrectLoop (LoopClosing.cc:487-516) in place: point ids[i] moves to
+        float(S_to[q].map(S_from[q].map(double(P)))), q = pair_of_point[i] (-1: no pair).  S_from / S_to: m Sim3 as (R, t, s) or [m, 13]
+        doubles.  Returns status [n] (_lib.POINT_MOVED / POINT_BAD_OR_UNSET / POINT_NO_PAIR)"""
+        from .essgraph import sim3_records
+        ids, pair = self._ids(ids), self._ids(pair_of_point)
+        A, B = sim3_records(S_from), sim3_records(S_to)
+        if len(pair) != len(ids) or len(A) != len(B):
+            raise ValueError("one pair per id and as many S_to as S_from are expected")
+        st = np.zeros(max(len(ids), 1), np.uint8)
+        pad = lambda a: a if len(a) else np.zeros((4,) + a.shape[1:], a.dtype)
+        self.ctx.check(self.lib.afv_points_correct_sim3(self.handle, ptr(pad(ids)), len(ids), ptr(pad(pair)), ptr(pad(A)), ptr(pad(B)), len(A), ptr(st)),
+                       "afv_points_correct_sim3")
+        return st[:len(ids)]
+
     def get(self, ids):
         """what the store holds for `ids` (tests): dict of pos, normal, min_distance, max_distance, ref_size, ref_distance, ref_sigma, flags
         (_lib.PTF_* bits), descriptors"""

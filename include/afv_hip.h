@@ -1087,6 +1087,101 @@ int afv_table_refresh_points(afv_table *t, afv_points *points, const int32_t *sl
                              const uint8_t *kf_bad, const int32_t *point_ids, int np, const int32_t *ref_kf, const int32_t *obs_point,
                              const int32_t *obs_kf, const int32_t *obs_idx, int ne, const afv_refresh_params *params, afv_refresh_out *out);
 
+/* ---- Essential graph: Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:771-1031, as LoopClosing::CorrectLoop calls it at
+ * LoopClosing.cc:581) over plain arrays and the map-point store, and the point correction of CorrectLoop (LoopClosing.cc:487-516) as a
+ * call of its own.  It was the one step of a loop closure that left the device; it ends by moving every map point of the map, which
+ * lives in the store.
+ * The normative semantics are tests/_essgraph_ref.py (double, one rounding per operator, every operator order fixed there); the device is
+ * held to it bit for bit, and so is the scalar host program tools/essgraph_host.cpp, which compiles the same text
+ * (csrc/afv_essgraph_math.h).  g2o is not shipped by the reference, so what it runs (VertexSim3Expmap, EdgeSim3 with Sim3::log,
+ * BaseBinaryEdge's numeric Jacobians, BlockSolver_7_3, OptimizationAlgorithmLevenberg with userLambdaInit) is restated after upstream g2o
+ * as bundled with ORB-SLAM2 - parity with a real g2o is UNPINNED.
+ * The problem: nk vertices in the order of the caller's keyframe list, S_init[k] = CorrectedSim3 of keyframe k or (Rcw, tcw, 1); vertex
+ * `fixed` (pLoopKF) is fixed.  Edge e has the error log(edge_meas[e] * S(edge_v0[e]) * S(edge_v1[e])^-1), information I7, no robust
+ * kernel, edge_v0 the vertex of setVertex(0, ...); the edges come in the order in which the reference adds them (the Python package's
+ * essential_graph_edges builds that list from :835-971).  Several edges may join one pair.  One optimize(params.iterations) call (20 in the
+ * reference) with lambda = params.lambda_init at iteration 0 (userLambdaInit: 1e-16), at most 10 trials per iteration.
+ * Then (:979-998) S_out[k] = the estimate, Tiw_out[k] = [R | t * (1 / s)] (12 doubles, R row-major; SetPose takes the float cast), and
+ * (:1000-1030) every point point_ids[i] that is set and not bad in the store and has point_ref[i] >= 0 (the position in the keyframe
+ * list of mnCorrectedReference or mpRefKF) moves to float(S(ref)^-1.map(S_init(ref).map(double(P)))), map(P) = s (R P) + t; xyz_out has the
+ * doubles (0 where nothing moved), the store receives the float cast when params.write_points.  Every other point and plane of the
+ * store is untouched; UpdateNormalAndDepth of the moved points is afv_table_refresh_points.
+ * The launches (csrc/k_essgraph.hip): per iteration k_ess_perturb (a lane per vertex and perturbation), k_ess_linearise (a lane per edge
+ * and perturbed error), k_ess_terms (a lane per edge and term), k_ess_build (a wavefront per free vertex / per off-diagonal block),
+ * k_ess_begin; per trial k_ess_load, k_ess_factor (ONE workgroup walks the block columns of L and runs both substitutions), k_ess_step,
+ * k_ess_trial, k_ess_judge, then ONE wait in which the host reads the status record.  The accept / reject decision, lambda and ni are
+ * the device's.  After the last iteration k_ess_recover and k_ess_correct_points.  One upload: the host builds the by-vertex order of
+ * the edges, the symbolic factorisation and the update triples while it checks the arguments.  No spinning flag, no cooperative
+ * launch, no captured graph, no atomics.
+ * Deliberate deviations from upstream (the numbering of tests/_essgraph_ref.py, where the full text is):
+ *   G1  the system is block-sparse in 7 x 7 blocks over the free vertices in the order of the caller's keyframe list, factorised by an
+ *       unpivoted block L L^T on the symbolic fill of that order, block column by block column, every entry subtracting its products in
+ *       ascending order; forward substitution ascending, back substitution descending; a pivot that is not positive and finite is a
+ *       failed trial; a vertex without edges stays in the system (the reference: Eigen's sparse Cholesky with a fill-reducing order)
+ *   G2  the state is R, t, s in double, no quaternion
+ *   G3  no libm: the Horner tables of PoseOptimization for sin / cos, (1 - cos) / th^2 and (th - sin) / th^3; log by exponent split and
+ *       a fixed polynomial (at most 3 ulp from math.log), acos by fdlibm's rational approximation (at most 1 ulp)
+ *   G4  W^-1 t by cofactors in a fixed order, not by LU
+ *   G5  an error that is not finite (theta at pi, a zero determinant) makes the trial fail; not finite at the initial estimate: nothing
+ *       is evaluated, status AFV_ESS_NOT_FINITE, the outputs hold the initial estimate
+ *   G6  every sum has one fixed shape: per free vertex 64 strided partial sums over its edges in list order, then p[l] += p[l + s], s =
+ *       32 .. 1; per off-diagonal block its edges one after the other; chi2 and computeScale the same tree over the edge list / the unknowns
+ *   G7  under fix_scale the scale column of every Jacobian is exactly zero, row 6 of every block holds lambda alone
+ *   G8  no free vertex, no edge or no iteration: nothing is evaluated, status AFV_ESS_EMPTY
+ *   G9  the caller lists only keyframes that are not bad; an edge from a vertex to itself is refused
+ *   G10 near the identity with |sigma| >= eps, Sim3::log's B carries the "- 1" that upstream's text lacks (without it W degenerates and
+ *       Levenberg stalls short of the optimum of every monocular loop)
+ *   G11 the edge list of essential_graph_edges walks a keyframe's loop edges in ascending keyId (the reference's set<Keyframe> is ordered
+ *       by pointer); the order of the edge list fixes the bits of the sums of G6
+ * Quirk kept (G-Q1): on a graph whose chi2 is exactly 0 the zero step has rho == 0, is rejected and ends optimize().
+ * The capacities: AFV_ESS_MAX_L_BLOCKS blocks of L (49 doubles each: 49 MiB at the cap) and AFV_ESS_MAX_UPDATES update triples (three
+ * ints each: 24 MiB); beside them an edge costs 2.6 KB of device scratch (its 29 errors and 120 terms: 166 MiB at AFV_ESS_MAX_EDGES).
+ * A keyframe order whose fill exceeds one of them answers AFV_ECAPACITY before any launch, outputs and store untouched.
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+#define AFV_ESS_MAX_KF 4096
+#define AFV_ESS_MAX_EDGES 65536
+#define AFV_ESS_MAX_L_BLOCKS 131072
+#define AFV_ESS_MAX_UPDATES 2097152
+typedef struct {
+    double R[9], t[3], s;                    /* a Sim3: R row-major; map(P) = s (R P) + t */
+} afv_sim3d;
+typedef struct {
+    uint32_t struct_size;                    /* sizeof(afv_ess_params) */
+    int32_t iterations;                      /* numItEssGraphOpt: 20 */
+    double lambda_init;                      /* userLambdaInit: 1e-16; > 0 */
+    int32_t fix_scale;                       /* bFixScale: 0 / 1 */
+    int32_t write_points;                    /* 1: the store receives (float)xyz_out (SetWorldPos); 0: it stays */
+} afv_ess_params;
+typedef struct {
+    int32_t iterations, trials;
+    double chi2_first, chi2_last, lambda;    /* the chi2 at the initial estimate and at the accepted one, the last lambda */
+    int32_t l_blocks;                        /* 7 x 7 blocks of L in the given order, the diagonal ones included */
+    int32_t status;                          /* AFV_ESS_* */
+} afv_ess_result;
+#define AFV_ESS_OK 0
+#define AFV_ESS_NOT_FINITE 1         /* G5 */
+#define AFV_ESS_EMPTY 2              /* G8 */
+#define AFV_POINT_MOVED 0            /* point_status / status, one byte per point */
+#define AFV_POINT_BAD_OR_UNSET 1
+#define AFV_POINT_NO_PAIR 2          /* point_ref / pair_of_point is -1 */
+/* points may be NULL when np == 0.  S_init[nk], edge_v0 / edge_v1 / edge_meas[ne], point_ids / point_ref[np] (host).  Outputs (host):
+ * result[1], S_out[nk], Tiw_out[nk][12], xyz_out[np][3], point_status[np].
+ * Refused before any launch, outputs and store untouched: AFV_EINVAL for a NULL argument, an unknown struct_size, nk outside 1 ..
+ * AFV_ESS_MAX_KF, ne > AFV_ESS_MAX_EDGES, a negative count, iterations below 0, fix_scale / write_points other than 0 / 1, a lambda_init
+ * that is not positive and finite, fixed or an edge end out of range, an edge from a vertex to itself, a measurement or an initial Sim3
+ * that is not finite or has s <= 0, a store of another context, a point id outside [0, capacity) or named twice, a point_ref outside
+ * [-1, nk); AFV_ECAPACITY for a fill beyond AFV_ESS_MAX_L_BLOCKS or AFV_ESS_MAX_UPDATES. */
+int afv_essential_graph(afv_ctx *ctx, afv_points *points, const afv_sim3d *S_init, int nk, int fixed, const int32_t *edge_v0, const int32_t *edge_v1,
+                        const afv_sim3d *edge_meas, int ne, const afv_ess_params *params, const int32_t *point_ids, const int32_t *point_ref, int np,
+                        afv_ess_result *result, afv_sim3d *S_out, double *Tiw_out, double *xyz_out, uint8_t *point_status);
+/* The point correction alone (LoopClosing.cc:487-516: CorrectedSwi.map(Siw.map(P)) over the points of the current keyframe's
+ * neighbours): point ids[i] moves to float(S_to[q].map(S_from[q].map(double(P)))) with q = pair_of_point[i], in the store, in place;
+ * status[i] is AFV_POINT_MOVED, AFV_POINT_BAD_OR_UNSET or AFV_POINT_NO_PAIR (q == -1).  The same kernel as afv_essential_graph's last
+ * launch.  One upload, one launch, one wait.  Refused before any launch, the store untouched: AFV_EINVAL for a NULL argument, n < 0, m
+ * outside 0 .. AFV_ESS_MAX_KF, an id outside [0, capacity) or named twice, a pair outside [-1, m), a Sim3 that is not finite or has s <= 0. */
+int afv_points_correct_sim3(afv_points *points, const int32_t *ids, int n, const int32_t *pair_of_point, const afv_sim3d *S_from, const afv_sim3d *S_to,
+                            int m, uint8_t *status);
+
 /* ---- Initializer: monocular start-up between two resident frames (src/Initializer.cc:41-908, as Tracking::MonocularInitialization calls
  * it, src/Tracking.cc:487).  One synchronous call does what Initializer::Initialize does, from matches12 (what
  * afv_frame_match_initialization answers) to (R21, t21, vP3D, vbTriangulated): one upload, three launches on the context's stream, one
