@@ -13,7 +13,8 @@ Layout:
   database.py    KeyFrameDatabase mirror over the keyframe table (reference: KeyFrameDatabase.{h,cc}, LoopClosing.cc:137-157)
   sim3.py        Sim3Solver mirror: all RANSAC hypotheses of a loop check in one device call (reference: Sim3Solver.{h,cc});
                  OptimizeSim3 / OptimizeSim3Batch: Optimizer::OptimizeSim3 for every candidate in one device call
-  lba.py         LocalBundleAdjustment / BundleAdjustment over table slots and store ids (reference: Optimizer.cc:450-768, :61-243)
+  lba.py         LocalBundleAdjustment / BundleAdjustment over table slots and store ids (reference: Optimizer.cc:450-768, :61-243);
+                 GlobalBundleAdjustment: the block-sparse route for the whole map (Optimizer.cc:53-58, LoopClosing.cc:664)
   refresh.py     RefreshMapPoints: ComputeDistinctiveDescriptors and UpdateNormalAndDepth of resident map points from the observation list
                  of the bundle adjustment (reference: MapPoint.cc:279-349, :372-418)
   essgraph.py    OptimizeEssentialGraph over plain arrays and the store, the edge list of the essential graph, the Sim3 point correction
@@ -31,7 +32,7 @@ from .points import MapPoints  # noqa: F401
 from . import akaze, table  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
 from .sim3 import OptimizeSim3, OptimizeSim3Batch, Sim3Solver  # noqa: F401
-from .lba import BundleAdjustment, LocalBundleAdjustment  # noqa: F401
+from .lba import BundleAdjustment, GlobalBundleAdjustment, LocalBundleAdjustment  # noqa: F401
 from .essgraph import OptimizeEssentialGraph, essential_graph_edges  # noqa: F401
 from .initializer import Initializer  # noqa: F401
 from .pnp import PnPsolver  # noqa: F401

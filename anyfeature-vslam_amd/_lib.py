@@ -191,6 +191,8 @@ class LbaResult(C.Structure):
 
 LBA_MAX_FREE, LBA_MAX_KF, LBA_MAX_POINTS, LBA_MAX_EDGES = 64, 256, 32768, 262144
 LBA_EDGE_DROPPED, LBA_EDGE_KEPT, LBA_EDGE_REMOVED_KEPT, LBA_EDGE_ERASE = 0, 1, 2, 3
+# afv_table_global_bundle_adjust: the same records, caps of its own
+GBA_MAX_KF, GBA_MAX_POINTS, GBA_MAX_EDGES, GBA_MAX_L_BLOCKS = 4096, 524288, 2097152, 1048576
 
 
 class Sim3d(C.Structure):
@@ -393,6 +395,10 @@ SYMBOLS = {
     "afv_table_optimize_sim3": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Sim3OptJob), _i, _vp, _vp, _vp, C.POINTER(Sim3OptResult), _vp]),
     "afv_table_bundle_adjust": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(LbaCam), _vp, _i, _vp, _vp, _vp, _i, C.POINTER(LbaParams), _vp,
                                      C.POINTER(LbaResult), _vp, _vp, _vp]),
+    "afv_table_global_bundle_adjust": (_i, [_vp, _vp, _vp, _i, _i, C.POINTER(LbaCam), _vp, _i, _vp, _vp, _vp, _i, C.POINTER(LbaParams), _vp,
+                                            C.POINTER(LbaResult), _vp, _vp, _vp]),
+    "afv_gba_plan_probe": (_i, [_i, _i, _vp, _vp, _i, C.c_longlong, _vp]),
+    "afv_points_correct_se3": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "afv_table_refresh_points": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(RefreshParams),
                                       C.POINTER(RefreshOut)]),
     "afv_table_set_inf": (_i, [_vp, _i, _vp]),

@@ -1450,7 +1450,8 @@ struct BundleAnswer {
 };
 inline BundleAnswer BundleAdjust(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<BundleKeyFrame> &kfs,
                                  const std::vector<int32_t> &point_ids, const std::vector<BundleObservation> &observations, int it0, int it1,
-                                 bool robust0, bool robust1, bool checks, bool write_points, const volatile int32_t *pbStopFlag) {
+                                 bool robust0, bool robust1, bool checks, bool write_points, const volatile int32_t *pbStopFlag,
+                                 bool block_sparse = false) {  // true: afv_table_global_bundle_adjust (its own caps, deviation L7')
     std::vector<size_t> order;  // free keyframes first, each group in the caller's order
     for (size_t k = 0; k < kfs.size(); ++k)
         if (!kfs[k].fixed) order.push_back(k);
@@ -1497,9 +1498,10 @@ inline BundleAnswer BundleAdjust(afv_ctx *ctx, afv_table *table, DeviceMapPoints
     std::vector<double> kf((size_t)std::max(n_free, 1) * 12, 0.0);
     std::vector<uint8_t> state(std::max<size_t>(ne, 1), 0);
     A.xyz.assign(std::max<size_t>(np, 1) * 3, 0.0);
-    const int rc = afv_table_bundle_adjust(table, points.handle(), slots.data(), (int)kfs.size(), n_free, cams.data(), ids.data(), (int)np, op.data(),
-                                           ok.data(), oi.data(), (int)ne, &prm, pbStopFlag, &A.trace, kf.data(), A.xyz.data(), state.data());
-    if (rc != AFV_OK) fatal("afv_table_bundle_adjust", rc, ctx);
+    const int rc = (block_sparse ? afv_table_global_bundle_adjust : afv_table_bundle_adjust)(
+        table, points.handle(), slots.data(), (int)kfs.size(), n_free, cams.data(), ids.data(), (int)np, op.data(), ok.data(), oi.data(), (int)ne, &prm,
+        pbStopFlag, &A.trace, kf.data(), A.xyz.data(), state.data());
+    if (rc != AFV_OK) fatal(block_sparse ? "afv_table_global_bundle_adjust" : "afv_table_bundle_adjust", rc, ctx);
     A.xyz.resize(np * 3);
     A.edge_state.assign(ne, 0);
     if (A.trace.stopped == 1) return A;  // the return at :645-647: nothing was written
@@ -1525,6 +1527,30 @@ inline BundleAnswer BundleAdjustment(afv_ctx *ctx, afv_table *table, DeviceMapPo
                                      const std::vector<int32_t> &point_ids, const std::vector<BundleObservation> &observations, int nIterations = 5,
                                      const volatile int32_t *pbStopFlag = nullptr, bool bRobust = true, bool write_points = true) {
     return BundleAdjust(ctx, table, points, kfs, point_ids, observations, nIterations, 0, bRobust, false, false, write_points, pbStopFlag);
+}
+// Optimizer::GlobalBundleAdjustemnt (Optimizer.cc:53-58; defaults: Optimizer.h:42-43) over the whole map on the block-sparse route: up to
+// AFV_GBA_MAX_KF keyframes, every one free except keyId == 0.  LoopClosing::RunGlobalBundleAdjustment passes (10, &mbStopGBA, false) and
+// write_points = false, keeps xyz as mPosGBA and the poses as mTcwGBA, and moves the points the BA did not optimise with CorrectPointsSE3
+inline BundleAnswer GlobalBundleAdjustment(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<BundleKeyFrame> &kfs,
+                                           const std::vector<int32_t> &point_ids, const std::vector<BundleObservation> &observations, int nIterations = 5,
+                                           const volatile int32_t *pbStopFlag = nullptr, bool bRobust = true, bool write_points = true) {
+    return BundleAdjust(ctx, table, points, kfs, point_ids, observations, nIterations, 0, bRobust, false, false, write_points, pbStopFlag, true);
+}
+struct SE3f {  // 12 floats: R row-major, t
+    float R[9], t[3];
+};
+// LoopClosing.cc:731-750 for the points the global BA did not optimise, in float, in the store, in place: Tcw_before[q] = mTcwBefGBA of
+// reference keyframe q, Twc_after[q] = its GetPoseInverse() after SetPose(TcwGBA); pair_of_point[i] names the pair of point i, -1 none
+inline std::vector<uint8_t> CorrectPointsSE3(afv_ctx *ctx, DeviceMapPoints &points, const std::vector<int32_t> &ids, const std::vector<int32_t> &pair_of_point,
+                                             const std::vector<SE3f> &Tcw_before, const std::vector<SE3f> &Twc_after) {
+    static_assert(sizeof(SE3f) == 48, "SE3f is 12 floats");
+    if (pair_of_point.size() != ids.size() || Tcw_before.size() != Twc_after.size()) fatal("CorrectPointsSE3: mismatched arrays", AFV_EINVAL, ctx);
+    std::vector<uint8_t> status(std::max<size_t>(ids.size(), 1), 0);
+    const int rc = afv_points_correct_se3(points.handle(), ids.data(), (int)ids.size(), pair_of_point.data(), reinterpret_cast<const float *>(Tcw_before.data()),
+                                          reinterpret_cast<const float *>(Twc_after.data()), (int)Tcw_before.size(), status.data());
+    if (rc != AFV_OK) fatal("afv_points_correct_se3", rc, ctx);
+    status.resize(ids.size());
+    return status;
 }
 
 // ---- MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:279-349) and MapPoint::UpdateNormalAndDepth (:372-418) of resident points:

@@ -281,6 +281,21 @@ extern "C" void afv_launch_lba_iteration(const LbView *V, hipStream_t stream);  
 extern "C" void afv_launch_lba_trial(const LbView *V, hipStream_t stream);      // invert, schur, solve, step, trial, judge
 extern "C" void afv_launch_lba_check(const LbView *V, int final_check, hipStream_t stream);
 extern "C" void afv_launch_lba_finish(const LbView *V, const DevLbaFinish *F, hipStream_t stream);
+extern "C" void afv_launch_lba_trial_head(const LbView *V, hipStream_t stream);  // invert: what stands before the solve of either route
+extern "C" void afv_launch_lba_trial_tail(const LbView *V, hipStream_t stream);  // step, trial, judge: what stands after it
+
+// ---- k_gba.hip: the block-sparse solve of afv_table_global_bundle_adjust and afv_points_correct_se3 (the arithmetic: afv_gba_math.h) ----
+struct GbView;
+struct DevGbaCorrect {       // k_gba_correct_points: a kernel argument
+    float *pos[3];           // the store's position planes
+    const uint8_t *flags;
+    const int *ids, *pair;   // [n]; pair: a position in T_before / T_after, -1: none
+    const float *T_before, *T_after;  // [m][12]: R row-major, t
+    uint8_t *status;         // [n]
+    int n;
+};
+extern "C" void afv_launch_gba_solve(const LbView *V, const GbView *G, hipStream_t stream);  // schur (and the zeroing of the fill), factor
+extern "C" void afv_launch_gba_correct_points(const DevGbaCorrect *J, hipStream_t stream);
 
 // ---- k_refresh.hip: ComputeDistinctiveDescriptors / UpdateNormalAndDepth of resident map points (host side: afv_refresh.hip) ----
 struct DevRefresh {          // a kernel argument of both launches

@@ -280,6 +280,17 @@ extern "C" void afv_launch_lba_trial(const LbView *V, hipStream_t stream) {
     hipLaunchKernelGGL(k_lba_judge, dim3(1), dim3(64), 0, stream, *V);
 }
 
+// the same launches around another solve (k_gba.hip: the block-sparse route of afv_table_global_bundle_adjust)
+extern "C" void afv_launch_lba_trial_head(const LbView *V, hipStream_t stream) {
+    hipLaunchKernelGGL(k_lba_invert, dim3(lb_blocks(V->np)), dim3(LB_T), 0, stream, *V);
+}
+
+extern "C" void afv_launch_lba_trial_tail(const LbView *V, hipStream_t stream) {
+    hipLaunchKernelGGL(k_lba_step, dim3(lb_blocks(std::max(V->np, V->nk))), dim3(LB_T), 0, stream, *V);
+    hipLaunchKernelGGL(k_lba_trial, dim3(lb_blocks(V->ne)), dim3(LB_T), 0, stream, *V);
+    hipLaunchKernelGGL(k_lba_judge, dim3(1), dim3(64), 0, stream, *V);
+}
+
 extern "C" void afv_launch_lba_check(const LbView *V, int final_check, hipStream_t stream) {
     if (V->ne > 0) hipLaunchKernelGGL(k_lba_check, dim3(lb_blocks(V->ne)), dim3(LB_T), 0, stream, *V, final_check);
 }

@@ -47,8 +47,8 @@ def edge_arrays(point_ids, kf_slots, observations):
 
 
 def bundle_adjust(table, points, slots, n_free, cams, point_ids, obs_point, obs_kf, obs_idx, iterations, robust, checks, write_points=True,
-                  trial_budget=0, stop=None):
-    """afv_table_bundle_adjust as it is.  stop: None, or a ctypes.c_int32 the caller (another thread) raises.  Returns (result: LbaResult,
+                  trial_budget=0, stop=None, entry="afv_table_bundle_adjust"):
+    """afv_table_bundle_adjust (or, with entry="afv_table_global_bundle_adjust", the block-sparse route with its own caps) as it is.  stop: None, or a ctypes.c_int32 the caller (another thread) raises.  Returns (result: LbaResult,
     kf [n_free, 12] float64, xyz [np, 3] float64, edge_state [ne] uint8)"""
     slots, point_ids = (np.ascontiguousarray(v, np.int32).reshape(-1) for v in (slots, point_ids))
     obs_point, obs_kf, obs_idx = (np.ascontiguousarray(v, np.int32).reshape(-1) for v in (obs_point, obs_kf, obs_idx))
@@ -63,10 +63,9 @@ def bundle_adjust(table, points, slots, n_free, cams, point_ids, obs_point, obs_
     res = LbaResult()
     kf, xyz, state = np.zeros((max(n_free, 1), 12), np.float64), np.zeros((max(npts, 1), 3), np.float64), np.zeros(max(ne, 1), np.uint8)
     pad = lambda a: a if len(a) else np.zeros(1, np.int32)
-    table.ctx.check(table.lib.afv_table_bundle_adjust(table.handle, points.handle, ptr(pad(slots)), nk, int(n_free), cams, ptr(pad(point_ids)), npts,
-                                                      ptr(pad(obs_point)), ptr(pad(obs_kf)), ptr(pad(obs_idx)), ne, C.byref(prm),
-                                                      None if stop is None else C.byref(stop), C.byref(res), ptr(kf), ptr(xyz), ptr(state)),
-                    "afv_table_bundle_adjust")
+    table.ctx.check(getattr(table.lib, entry)(table.handle, points.handle, ptr(pad(slots)), nk, int(n_free), cams, ptr(pad(point_ids)), npts,
+                                             ptr(pad(obs_point)), ptr(pad(obs_kf)), ptr(pad(obs_idx)), ne, C.byref(prm),
+                                             None if stop is None else C.byref(stop), C.byref(res), ptr(kf), ptr(xyz), ptr(state)), entry)
     return res, kf[:n_free], xyz[:npts], state[:ne]
 
 
@@ -75,13 +74,14 @@ def _trace(res):
                 n_removed_first=res.n_removed_first, n_erase=res.n_erase, stopped=res.stopped)
 
 
-def _run(table, points, kfs, fixed_flags, cams, point_ids, observations, iterations, robust, checks, write_points, stop):
+def _run(table, points, kfs, fixed_flags, cams, point_ids, observations, iterations, robust, checks, write_points, stop,
+         entry="afv_table_bundle_adjust"):
     kfs = [int(s) for s in kfs]
     free = [s for s, f in zip(kfs, fixed_flags) if not f]
     order_kf = free + [s for s, f in zip(kfs, fixed_flags) if f]
     op, ok, oi, order = edge_arrays(point_ids, order_kf, observations)
     recs = lba_cams([cams[s] for s in order_kf])
-    res, kf, xyz, state = bundle_adjust(table, points, order_kf, len(free), recs, point_ids, op, ok, oi, iterations, robust, checks, write_points, 0, stop)
+    res, kf, xyz, state = bundle_adjust(table, points, order_kf, len(free), recs, point_ids, op, ok, oi, iterations, robust, checks, write_points, 0, stop, entry)
     poses = {s: (kf[i, :9].reshape(3, 3).copy(), kf[i, 9:].copy()) for i, s in enumerate(free)} if res.stopped != 1 else {}
     st = np.zeros(len(order), np.uint8)
     st[order] = state
@@ -110,6 +110,20 @@ def BundleAdjustment(table, points, kfs, cams, point_ids, observations, nIterati
     entries = [(e, False) if np.isscalar(e) else (e[0], bool(e[1])) for e in kfs]
     res, poses, xyz, st = _run(table, points, [e[0] for e in entries], [e[1] for e in entries], cams, point_ids, observations, (nIterations, 0),
                                (robust, 0), 0, write_points, stop)
+    trace = _trace(res)
+    trace["edge_state"] = st
+    return poses, xyz, trace
+
+
+def GlobalBundleAdjustment(table, points, kfs, cams, point_ids, observations, nIterations=5, robust=True, stop=None, write_points=True):
+    """Optimizer::GlobalBundleAdjustemnt (Optimizer.cc:53-58; the defaults are Optimizer.h:42-43) over the whole map, on the block-sparse
+    route (afv_table_global_bundle_adjust: up to _lib.GBA_MAX_KF keyframes, deviation L7' of include/afv_hip.h).  The arguments and the
+    answer are BundleAdjustment's: kfs [(slot, is_fixed), ...] with keyId == 0 flagged fixed.  LoopClosing::RunGlobalBundleAdjustment
+    passes nIterations=10, robust=False, write_points=False and keeps xyz as mPosGBA; the points the BA did not optimise are then moved
+    by MapPoints.correct_se3.  Returns (poses, xyz, trace)."""
+    entries = [(e, False) if np.isscalar(e) else (e[0], bool(e[1])) for e in kfs]
+    res, poses, xyz, st = _run(table, points, [e[0] for e in entries], [e[1] for e in entries], cams, point_ids, observations, (nIterations, 0),
+                               (robust, 0), 0, write_points, stop, "afv_table_global_bundle_adjust")
     trace = _trace(res)
     trace["edge_state"] = st
     return poses, xyz, trace

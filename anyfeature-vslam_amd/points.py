@@ -104,6 +104,27 @@ class MapPoints:
                        "afv_points_correct_sim3")
         return st[:len(ids)]
 
+    def correct_se3(self, ids, pair_of_point, Tcw_before, Twc_after):
+        """The point correction of LoopClosing::RunGlobalBundleAdjustment (LoopClosing.cc:731-750) for points the BA did not optimise, in
+        place and IN FLOAT: point ids[i] moves to Rwc * (Rcw_bef * X + tcw_bef) + twc with q = pair_of_point[i] (-1: no pair).
+        Tcw_before [m]: mTcwBefGBA of the reference keyframes; Twc_after [m]: their GetPoseInverse() after SetPose(TcwGBA) - nothing is
+        inverted here.  Each as [m, 4, 4] / [m, 3, 4] matrices or [m, 12] (R row-major, then t), float32.  Returns status [n]
+        (_lib.POINT_MOVED / POINT_BAD_OR_UNSET / POINT_NO_PAIR)"""
+        def records(T):
+            T = np.asarray(T, np.float32)
+            if T.ndim == 3:
+                T = np.concatenate([T[:, :3, :3].reshape(-1, 9), T[:, :3, 3]], 1)
+            return np.ascontiguousarray(T.reshape(-1, 12))
+        ids, pair = self._ids(ids), self._ids(pair_of_point)
+        A, B = records(Tcw_before), records(Twc_after)
+        if len(pair) != len(ids) or len(A) != len(B):
+            raise ValueError("one pair per id and as many Twc_after as Tcw_before are expected")
+        st = np.zeros(max(len(ids), 1), np.uint8)
+        pad = lambda a: a if len(a) else np.zeros((4,) + a.shape[1:], a.dtype)
+        self.ctx.check(self.lib.afv_points_correct_se3(self.handle, ptr(pad(ids)), len(ids), ptr(pad(pair)), ptr(pad(A)), ptr(pad(B)), len(A), ptr(st)),
+                       "afv_points_correct_se3")
+        return st[:len(ids)]
+
     def get(self, ids):
         """what the store holds for `ids` (tests): dict of pos, normal, min_distance, max_distance, ref_size, ref_distance, ref_sigma, flags
         (_lib.PTF_* bits), descriptors"""

@@ -1029,6 +1029,61 @@ int afv_table_bundle_adjust(afv_table *t, afv_points *points, const int32_t *slo
                             const afv_lba_params *params, const volatile int32_t *stop_flag, afv_lba_result *results, double *kf_out,
                             double *xyz_out, uint8_t *edge_state);
 
+/* ---- Global bundle adjustment: Optimizer::GlobalBundleAdjustemnt (src/Optimizer.cc:53-58) as LoopClosing::RunGlobalBundleAdjustment
+ * calls it after every loop closure (LoopClosing.cc:664: every keyframe of the map free except keyId == 0), and any bundle adjustment
+ * with more than AFV_LBA_MAX_FREE free keyframes.  The arguments, the records (afv_lba_cam, afv_lba_params, afv_lba_result), the outputs,
+ * the edge states, the stop-flag rule and the refusals are those of afv_table_bundle_adjust; both values of params.checks are accepted.
+ * The normative semantics are tests/_gba_ref.py: tests/_lba_ref.py (L-Q1, L1 - L6, L8, L9, the order of every sum) with one amendment:
+ *   L7' the reduced system is block-sparse in 6 x 6 blocks over the free keyframes, in the order of the caller's list.  Block (i, j) is
+ *       structural when some listed point has an edge to both keyframes - taken from the edge list as given, before points are dropped
+ *       and before a check removes edges, so a block that became empty holds exact zeros.  The factorisation is the unpivoted L L^T of L7
+ *       restricted to the symbolic fill of that order: every scalar element subtracts its products one after the other in ascending k,
+ *       the products with a factor in a block outside the fill are skipped; the forward substitution ascends, the back substitution
+ *       descends, each product by product; a pivot that is not positive and finite is a failed trial; a free keyframe without active
+ *       edges stays in the system with lambda on its diagonal.  On finite data this gives the doubles of L7 (skipping s - (+-0) changes
+ *       nothing unless s is -0.0); where a zero sign ever differs, L7' is normative for this entry point.
+ * On an input that both entry points accept they answer the same bytes.
+ * The launches: those of afv_table_bundle_adjust, with k_lba_schur and k_lba_solve replaced per trial by k_gba_schur (a wavefront per
+ * block of L from the plan's list: a structural block is evaluated and stored where it loads to, a fill block is zeroed) and
+ * k_gba_factor (ONE workgroup walks the block columns: diagonal 6 x 6 factorisation, sub-diagonal blocks a lane per row, updates a lane
+ * per entry, both substitutions in the same launch); csrc/k_gba.hip.  The dense n x n matrix is not allocated.  The host derives the plan
+ * (the structural blocks, the column structure of L by symbolic elimination in list order) while it checks the arguments and uploads
+ * it with the inputs in the call's one copy; one wait per trial, as before.
+ * The capacities.  AFV_GBA_MAX_KF is the essential graph's (the same map goes through both).  A block of L costs 288 bytes + 9 bytes of
+ * plan: 297 MiB at AFV_GBA_MAX_L_BLOCKS.  No update triples are stored (the kernel finds an update's target by a binary search in the
+ * target column), so there is no cap on them.  An edge costs about 0.5 KB of device scratch (its 55 terms, observation, chi2 and
+ * lists): 1.0 GiB at AFV_GBA_MAX_EDGES; a point 0.3 KB: 0.15 GiB at AFV_GBA_MAX_POINTS.  The context's arena has no limit of its own
+ * below that (it is one device allocation that grows by half again: 2.2 GiB at all caps together).  A keyframe order whose fill exceeds
+ * AFV_GBA_MAX_L_BLOCKS answers AFV_ECAPACITY before any launch, outputs and store untouched.
+ * New symbols only: AFV_ABI_VERSION stays 6. */
+#define AFV_GBA_MAX_KF 4096
+#define AFV_GBA_MAX_POINTS 524288
+#define AFV_GBA_MAX_EDGES 2097152
+#define AFV_GBA_MAX_L_BLOCKS 1048576
+/* Refused before any launch, outputs and store untouched: everything afv_table_bundle_adjust refuses, with nk > AFV_GBA_MAX_KF, n_free >
+ * nk, np > AFV_GBA_MAX_POINTS, ne > AFV_GBA_MAX_EDGES in the place of its caps (AFV_EINVAL); AFV_ECAPACITY for a fill beyond
+ * AFV_GBA_MAX_L_BLOCKS. */
+int afv_table_global_bundle_adjust(afv_table *t, afv_points *points, const int32_t *slots, int nk, int n_free, const afv_lba_cam *cams,
+                                   const int32_t *point_ids, int np, const int32_t *obs_point, const int32_t *obs_kf, const int32_t *obs_idx, int ne,
+                                   const afv_lba_params *params, const volatile int32_t *stop_flag, afv_lba_result *results, double *kf_out,
+                                   double *xyz_out, uint8_t *edge_state);
+/* Internal, for the tests of the capacity answer: the plan of an edge list (obs_point ascending; obs_kf < n_free: a free keyframe)
+ * against a block cap of the caller's choice - the entry point above always uses AFV_GBA_MAX_L_BLOCKS.  AFV_OK with counts[3] = the
+ * blocks of L, the structural blocks among them, n_free; AFV_ECAPACITY (counts untouched) when the fill exceeds max_blocks.  No device is
+ * touched. */
+int afv_gba_plan_probe(int n_free, int np, const int32_t *obs_point, const int32_t *obs_kf, int ne, long long max_blocks, int32_t *counts);
+/* The point correction of RunGlobalBundleAdjustment for the points the BA did not optimise (LoopClosing.cc:731-750): point ids[i] moves
+ * to Rwc * (Rcw_bef * X + tcw_bef) + twc with q = pair_of_point[i], IN FLOAT, in the store, in place: T_before[q] = (Rcw, tcw) of the
+ * reference keyframe before the BA (mTcwBefGBA), T_after[q] = (Rwc, twc) as the host's GetPoseInverse() holds it after SetPose(TcwGBA)
+ * - nothing is inverted here; each record is 12 floats, R row-major, then t.  Each row is ((R[r][0] * x + R[r][1] * y) + R[r][2] * z) +
+ * t[r], one rounding per operator (tests/_gba_ref.py, correct_se3; parity with the reference's cv::Mat product is UNPINNED).
+ * afv_points_correct_sim3 works in double and is another arithmetic.  status[i] is AFV_POINT_MOVED, AFV_POINT_BAD_OR_UNSET or
+ * AFV_POINT_NO_PAIR (q == -1).  One upload, one launch, one wait.  Refused before any launch, the store untouched: AFV_EINVAL for a NULL
+ * argument, n < 0, n beyond the store's capacity, m outside 0 .. AFV_GBA_MAX_KF, an id outside [0, capacity) or named twice, a pair
+ * outside [-1, m), a transform that is not finite.  The spanning-tree walk over the poses (:690-714) and SetPose stay with the host. */
+int afv_points_correct_se3(afv_points *points, const int32_t *ids, int n, const int32_t *pair_of_point, const float *T_before, const float *T_after,
+                           int m, uint8_t *status);
+
 /* ---- Refresh of resident map points from their observations: MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:279-349) and
  * MapPoint::UpdateNormalAndDepth (:372-418) for a batch of points, every row and every plane read where it is resident (the keyframe
  * table, the store).  The reference calls the two after BundleAdjustment (Optimizer.cc:234), LocalBundleAdjustment (:766) and
