@@ -105,6 +105,28 @@ class ProjQueries(C.Structure):
                 ("qref_table", C.c_void_p), ("qref_slot", C.c_void_p), ("qref_idx", C.c_void_p)]
 
 
+class TableCamera(C.Structure):
+    """afv_table_camera: the image bounds and the grid of KeyFrame::GetFeaturesInArea for every slot of a table"""
+    _fields_ = [("struct_size", C.c_uint32), ("min_x", C.c_float), ("max_x", C.c_float), ("min_y", C.c_float), ("max_y", C.c_float),
+                ("grid_cols", C.c_int32), ("grid_rows", C.c_int32), ("grid_inv_w", C.c_float), ("grid_inv_h", C.c_float)]
+
+
+class TableFusePose(C.Structure):
+    """afv_table_fuse_pose: the decomposed Scw of Fuse(pKF, Scw, ...)"""
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("Ow", C.c_float * 3)]
+
+
+class TableFuseJob(C.Structure):
+    """afv_table_fuse_job: one target keyframe of afv_table_fuse_points"""
+    _fields_ = [("struct_size", C.c_uint32), ("slot", C.c_int32), ("ids", C.c_void_p), ("nq", C.c_int32), ("radius_th", C.c_float),
+                ("radius_scale", C.c_float), ("th_low", C.c_float), ("use_inf_gate", C.c_int32), ("pose_override", C.POINTER(TableFusePose))]
+
+
+KFFUSE_MAX_TARGETS, KFFUSE_MAX_QUERIES = 64, 1 << 20
+# status of a (target, query) of afv_table_fuse_points
+KFFUSE_STATUS = {"invalid": 0, "in_keyframe": 1, "not_in_view": 2, "no_feature": 3, "free": 4, "occupant_bad": 5, "replace": 6}
+
+
 class PointSearch(C.Structure):
     """afv_point_search: a projection search through the ids of resident map points"""
     _fields_ = [("struct_size", C.c_uint32), ("flavour", C.c_int32), ("points", C.c_void_p), ("ids", C.c_void_p), ("nq", C.c_int32),
@@ -402,6 +424,11 @@ SYMBOLS = {
     "afv_table_refresh_points": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(RefreshParams),
                                       C.POINTER(RefreshOut)]),
     "afv_table_set_inf": (_i, [_vp, _i, _vp]),
+    "afv_table_set_camera": (_i, [_vp, C.POINTER(TableCamera)]),
+    "afv_table_set_pose": (_i, [_vp, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f]),
+    "afv_table_set_map_points": (_i, [_vp, _i, _vp]),
+    "afv_table_get_map_points": (_i, [_vp, _i, _vp]),
+    "afv_table_fuse_points": (_i, [_vp, _vp, C.POINTER(TableFuseJob), _i, _vp, _vp, _vp, _vp]),
     "afv_essential_graph": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, C.POINTER(EssParams), _vp, _vp, _i, C.POINTER(EssResult), _vp, _vp, _vp,
                                  _vp]),
     "afv_points_correct_sim3": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),

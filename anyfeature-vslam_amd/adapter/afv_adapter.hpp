@@ -1905,4 +1905,83 @@ inline std::vector<uint8_t> CorrectPointsSim3(afv_ctx *ctx, DeviceMapPoints &poi
     return status;
 }
 
+// ---- FeatureMatcher::Fuse into keyframes of the table (include/afv_hip.h afv_table_fuse_points; reference: FeatureMatcher.cc:794-940,
+// :942-1064 as LocalMapping::SearchInNeighbors and LoopClosing::SearchAndFuse call them).  The slots carry the table's camera
+// (afv_table_set_camera), KeyFrame::SetPose (afv_table_set_pose) and mvpMapPoints (afv_table_set_map_points): INTEGRATION.md, "Fusing into
+// keyframes".  Every target is answered against the store and the planes AS THEY STAND: AddObservation (status 4), Replace (status 6) and
+// ComputeDistinctiveDescriptors stay with the caller; one target per call with the map updated in between is the reference's loop. ----
+struct FuseTarget {
+    int32_t slot;
+    const std::vector<int32_t> *ids;  // the points in the reference's iteration order, -1 allowed; targets naming ONE vector share its gather
+};
+struct FuseAnswer {  // per target, over its queries
+    std::vector<std::vector<int32_t>> best, occupant;  // the winning feature | -1; the point id the keyframe holds there | -1
+    std::vector<std::vector<uint8_t>> status;          // 0 .. 6, see afv_table_fuse_points
+    std::vector<int32_t> nFused;                        // what Fuse returns
+};
+inline FuseAnswer FuseRun(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<FuseTarget> &targets, float radiusTh, float th_low,
+                          bool use_inf_gate, const std::vector<afv_table_fuse_pose> *poses) {
+    const size_t nt = targets.size();
+    if (poses && poses->size() != nt) fatal("Fuse: one Scw per target", AFV_EINVAL, ctx);
+    std::vector<afv_table_fuse_job> jobs(std::max<size_t>(nt, 1));
+    size_t total = 0;
+    for (size_t k = 0; k < nt; ++k) {
+        afv_table_fuse_job &j = jobs[k];
+        j = afv_table_fuse_job{};
+        j.struct_size = (uint32_t)sizeof(j);
+        j.slot = targets[k].slot;
+        j.ids = targets[k].ids->data();
+        j.nq = (int32_t)targets[k].ids->size();
+        j.radius_th = radiusTh; j.radius_scale = 1.15f; j.th_low = th_low;  // FeatureMatcher's static radiusScale
+        j.use_inf_gate = use_inf_gate ? 1 : 0;
+        j.pose_override = poses ? &(*poses)[k] : nullptr;
+        total += targets[k].ids->size();
+    }
+    std::vector<int32_t> best(std::max<size_t>(total, 1), -1), occ(std::max<size_t>(total, 1), -1), nf(std::max<size_t>(nt, 1), 0);
+    std::vector<uint8_t> st(std::max<size_t>(total, 1), 0);
+    const int rc = afv_table_fuse_points(table, points.handle(), jobs.data(), (int)nt, best.data(), occ.data(), st.data(), nf.data());
+    if (rc != AFV_OK) fatal("afv_table_fuse_points", rc, ctx);
+    FuseAnswer A;
+    size_t at = 0;
+    for (size_t k = 0; k < nt; ++k) {
+        const size_t nq = targets[k].ids->size();
+        A.best.emplace_back(best.begin() + at, best.begin() + at + nq);
+        A.occupant.emplace_back(occ.begin() + at, occ.begin() + at + nq);
+        A.status.emplace_back(st.begin() + at, st.begin() + at + nq);
+        A.nFused.push_back(nf[k]);
+        at += nq;
+    }
+    return A;
+}
+// Fuse(pKF, vpMapPoints, th) into every target (up to 64) in one call
+inline FuseAnswer FuseIntoKeyFrames(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<FuseTarget> &targets, float th_low,
+                                    float radiusTh = 3.0f) {
+    return FuseRun(ctx, table, points, targets, radiusTh, th_low, true, nullptr);
+}
+// Rcw, tcw, Ow of a row-major 4 x 4 Scw as Fuse(pKF, Scw, ...) writes them (FeatureMatcher.cc:954-958): scw = |row 0 of sRcw|,
+// Rcw = sRcw / scw, Ow = -Rcw^T tcw - and tcw is Scw's translation AS IT STANDS, the reference does not divide it by scw (a kept quirk).
+// Compile the caller with -ffp-contract=off for the reference's bits.
+inline afv_table_fuse_pose DecomposeScw(const float *Scw) {
+    afv_table_fuse_pose p;
+    const float s00 = Scw[0] * Scw[0], s01 = Scw[1] * Scw[1], s02 = Scw[2] * Scw[2];
+    const float scw = std::sqrt(s00 + (s01 + s02));
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) p.R[3 * r + c] = Scw[4 * r + c] / scw;
+        p.t[r] = Scw[4 * r + 3];
+    }
+    for (int k = 0; k < 3; ++k) {
+        const float a0 = -p.R[k] * p.t[0], a1 = -p.R[3 + k] * p.t[1], a2 = -p.R[6 + k] * p.t[2];
+        p.Ow[k] = a0 + (a1 + a2);
+    }
+    return p;
+}
+// Fuse(pKF, Scw, vpPoints, th, vpReplacePoint): no reprojection gate, target k seen through Scw[k] (16 floats, row-major); status 6 is
+// vpReplacePoint[iMP] = occupant
+inline FuseAnswer FuseIntoKeyFramesSim3(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<FuseTarget> &targets,
+                                        const std::vector<std::array<float, 16>> &Scw, float th_low, float radiusTh = 4.0f) {
+    std::vector<afv_table_fuse_pose> poses;
+    for (const std::array<float, 16> &S : Scw) poses.push_back(DecomposeScw(S.data()));
+    return FuseRun(ctx, table, points, targets, radiusTh, th_low, false, &poses);
+}
+
 }  // namespace afv

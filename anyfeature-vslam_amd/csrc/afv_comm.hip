@@ -52,6 +52,7 @@ static void table_free(afv_table *t) {
     void *ptrs[] = {t->d_desc, t->d_angle, t->d_n, t->d_idx, t->d_geo, t->d_scale, t->d_inf, t->d_valid, t->d_pairs, t->d_out, t->d_nm, t->d_bow_word, t->d_bow_value, t->d_bow_n};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
+    afv_kffuse_free(t);
     if (t->h_pin) (void)hipHostFree(t->h_pin);
     if (t->ev0) (void)hipEventDestroy(t->ev0);
     if (t->ev1) (void)hipEventDestroy(t->ev1);
@@ -162,6 +163,7 @@ extern "C" int afv_table_set(afv_table *t, int set, const uint8_t *desc32, const
     t->has_inf[set] = 0;
     t->has_bow[set] = 0;
     t->h_bow_n[set] = 0;
+    afv_kffuse_slot_reset(t, set);
     if (t->d_bow_n) HIPCHK(c, hipMemsetAsync(t->d_bow_n + set, 0, sizeof(int32_t), c->stream));
     if (t->d_valid) HIPCHK(c, hipMemsetAsync(t->d_valid + (size_t)set * t->cap, 1, (size_t)t->cap, c->stream));
     HIPCHK(c, hipMemcpyAsync(t->d_n + set, &t->h_n[set], sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
@@ -198,6 +200,7 @@ extern "C" int afv_table_set_geometry(afv_table *t, int set, const float *x, con
     if (!t->d_geo) HIPCHK(c, hipMalloc(&t->d_geo, 4 * plane * sizeof(float)));
     const int n = t->h_n[set];
     t->has_geo[set] = 1;
+    afv_kffuse_grid_stale(t, set);
     if (n == 0) return AFV_OK;
     const std::vector<float> mono((size_t)n, -1.0f);  // a keyframe is monocular until afv_table_set_u_right says otherwise
     const float *src[4] = {x, y, sigma2, mono.data()};
@@ -243,6 +246,7 @@ extern "C" int afv_table_set_scale(afv_table *t, int set, const float *size, con
         if (!t->d_scale) HIPCHK(c, hipMalloc(&t->d_scale, 4 * plane * sizeof(float)));
         const int n = t->h_n[set];
         t->has_scale[set] = 1;
+        afv_kffuse_grid_stale(t, set);
         if (n == 0) return AFV_OK;
         const std::vector<float> none((size_t)n, -1.0f);  // mvDepth of a monocular keyframe
         HIPCHK(c, hipMemcpy(t->d_scale + row0, size, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
@@ -343,6 +347,7 @@ extern "C" int afv_table_sync_counts(afv_table *t) {  // after a broadcast / ext
         }
         t->h_n[s] = v;
     }
+    afv_kffuse_grid_stale(t, -1);
     return AFV_OK;
 }
 
@@ -448,7 +453,8 @@ extern "C" int afv_table_clone(const afv_table *src, afv_table *dst) {
         if (rc) return rc;
         std::vector<int32_t> blob;
         table_pack_meta(src, blob);
-        return table_unpack_meta(dst, blob.data(), blob.size());  // the code path every receiver of afv_table_broadcast runs
+        rc = table_unpack_meta(dst, blob.data(), blob.size());  // the code path every receiver of afv_table_broadcast runs
+        return rc ? rc : afv_kffuse_clone(src, dst);
     });
 }
 
@@ -768,6 +774,7 @@ extern "C" int afv_table_set_from_frame(afv_table *t, int slot, afv_frame *f) {
         }
         t->has_geo[slot] = 1;
         t->has_scale[slot] = 1;
+        afv_kffuse_slot_reset(t, slot);  // a new keyframe: the pose and the mvpMapPoints of the slot's previous occupant are not its own
         // ... and its keyPtsInf, the information plane (what PoseOptimization reads on the frame, OptimizeSim3 on the keyframe)
         if (!t->d_inf) HIPCHK(c, hipMalloc(&t->d_inf, plane * sizeof(float)));
         if (f->n) HIPCHK(c, hipMemcpyAsync(t->d_inf + (size_t)slot * t->cap, f->d_inf, (size_t)f->n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
@@ -1052,7 +1059,10 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         HIPCHK(c, hipEventRecord(t->ev1, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (elapsed_ms) HIPCHK(c, hipEventElapsedTime(elapsed_ms, t->ev0, t->ev1));
-        if (m->rank == root) return afv_table_sync_counts(t);
+        if (m->rank == root) {
+            rc = afv_table_sync_counts(t);
+            return rc ? rc : afv_kffuse_broadcast(m, t, root);
+        }
         // receivers: nothing of the previous content survives; counts first, then the FeatureVectors against them
         for (int s = 0; s < t->nsets; ++s) {
             t->fv[s] = HostFeatVec();
@@ -1065,7 +1075,8 @@ extern "C" int afv_table_broadcast(afv_comm *m, afv_table *t, int root, float *e
         if (rc) return rc;
         blob.resize((size_t)flags[3]);
         HIPCHK(c, hipMemcpy(blob.data(), d_meta, blob.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        return table_unpack_meta(t, blob.data(), blob.size());
+        rc = table_unpack_meta(t, blob.data(), blob.size());
+        return rc ? rc : afv_kffuse_broadcast(m, t, root);  // camera, poses and the mvpMapPoints plane (afv_kffuse.hip)
     });
 }
 

@@ -143,6 +143,25 @@ struct DevPointsMove {       // k_points_move: n ids between packed arrays (host
     int mark_set;
 };
 extern "C" void afv_launch_points_project(const DevPointsJob *job, hipStream_t stream);
+// afv_table_fuse_points (host side: afv_kffuse.hip): one record per target keyframe.  The camera fields carry the names k_points_project
+// reads from its job: one text evaluates the geometry for both
+struct DevKfFuseJob {
+    float R[9], t[3], Ow[3], fx, fy, cx, cy, mbf;
+    float min_x, max_x, min_y, max_y;
+    float rs_th, cos_limit, tol;
+    const int *ids;          // [nq]
+    int nq, n;               // queries; features of the slot
+    const int *plane;        // [n] the slot's mvpMapPoints
+    float *qu, *qv, *qr, *qmin, *qmax, *q_ur;
+    uint8_t *qvalid;         // 1: the query goes into the search
+    uint8_t *status;         // [nq] 0 / 1 / 2, AFV_KF_PENDING for a query the search decides
+    uint4 *qd;               // [nq] rows of the id list; null: another job of the call gathers them
+    const int *best;         // [nq] what k_match_fuse leaves
+    int *occupant;           // [nq]
+};
+#define AFV_KF_PENDING 255
+extern "C" void afv_launch_kffuse_project(const DevPointPlanes *P, const DevKfFuseJob *jobs, int njobs, int max_nq, hipStream_t stream);
+extern "C" void afv_launch_kffuse_finish(const DevPointPlanes *P, const DevKfFuseJob *jobs, int njobs, int max_nq, hipStream_t stream);
 extern "C" void afv_launch_points_move(const DevPointsMove *job, hipStream_t stream);
 // descriptor rows of n ids: from packed rows of the store's pitch (table == null), from rows (slot, idx) of a keyframe table, or (gather)
 // out of the store into packed rows
@@ -777,6 +796,9 @@ struct HostFeatVec {  // host copy of one keyframe's FeatureVector (node ids, CS
     std::vector<int32_t> node_id, seg_ptr, seg_idx;
 };
 
+struct KfPose {  // afv_table_set_pose
+    float R[9], t[3], Ow[3], fx, fy, cx, cy, mbf;
+};
 struct afv_table {
     afv_ctx *c = nullptr;
     int nsets = 0, cap = 0;
@@ -809,7 +831,23 @@ struct afv_table {
     int32_t *h_pin = nullptr;    // pinned: [2][pair_cap] pairs, then [pair_cap] counts, then [pair_cap][cap] matches
     int pair_cap = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // fusing map points into slots (afv_kffuse.hip): the camera, a pose per slot (host side: it travels as a job record), the keyframe's
+    // mvpMapPoints and the grid of KeyFrame::GetFeaturesInArea per slot; everything lazily allocated
+    bool has_camera = false;
+    afv_table_camera cam{};
+    std::vector<KfPose> kf_pose;               // [nsets] once a pose or a plane was set
+    std::vector<uint8_t> kf_has_pose, kf_has_mp, kf_grid_ok;  // per set; kf_grid_ok: the slot's grid is that of its planes and the camera
+    int32_t *d_mp = nullptr;         // [nsets][cap] point id | -1
+    int *d_kf_cell_ptr = nullptr;    // [nsets][grid_cols * grid_rows + 1]
+    int4 *d_kf_cell_ent = nullptr;   // [nsets][cap]
+    int kf_cells = 0;                // cells the grid planes were allocated for
 };
+// afv_kffuse.hip: what the table's own entry points (afv_comm.hip) tell the fuse state of a slot
+AFV_LOCAL void afv_kffuse_slot_reset(afv_table *t, int slot);   // afv_table_set / a promoted frame: pose, plane and grid are forgotten
+AFV_LOCAL void afv_kffuse_grid_stale(afv_table *t, int slot);   // the geometry or the scale planes changed (slot < 0: every slot)
+AFV_LOCAL int afv_kffuse_clone(const afv_table *src, afv_table *dst);
+AFV_LOCAL void afv_kffuse_free(afv_table *t);
+AFV_LOCAL int afv_kffuse_broadcast(afv_comm *m, afv_table *t, int root);  // behind the planes of afv_table_broadcast, on every rank
 
 // ---- the pair matchers (afv_api.hip), shared with afv_comm.hip ----
 int afv_match_pairs_core(afv_ctx *c, const uint8_t *d_desc, const float *d_ang, int ang_stride, const int32_t *d_n, int cap,

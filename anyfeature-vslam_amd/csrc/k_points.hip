@@ -16,22 +16,16 @@
 __device__ __forceinline__ float pt_sum3(float a0, float a1, float a2) { return a0 + (a1 + a2); }
 __device__ __forceinline__ bool pt_finite(float v) { return __builtin_isfinite(v); }
 
-__global__ __launch_bounds__(PT_T) void k_points_project(const DevPointsJob J) {
-    __shared__ int s_id[PT_T];  // the point of an in-view query of this workgroup, -1 otherwise: what the gather below reads
-    const int tid = threadIdx.x, q = blockIdx.x * PT_T + tid;
-    const DevPointPlanes &P = J.P;
-    bool ok = false;
-    int id = -1;
-    unsigned fl = 0;
+// what the rule set `fv` makes of point `id` (set and not bad) seen by camera J: in view or not, and the query the searches read.
+// CAM: DevPointsJob, or the record of a target keyframe (DevKfFuseJob) - the same field names, ONE text for every route
+struct PtQuery {
+    float u, v, ur, r, er, size, sigma, vcos, mn, mx;
+};
+template <class CAM>
+__device__ __forceinline__ bool pt_project_one(const DevPointPlanes &P, const CAM &J, int fv, int id, float last_size, PtQuery &o) {
+    bool ok = true;
     float u = 0.0f, v = 0.0f, ur = 0.0f, r = 0.0f, er = 0.0f, size = 0.0f, sigma = 0.0f, vcos = 0.0f, mn = 0.0f, mx = 0.0f;
-    if (q < J.nq) {
-        id = J.ids[q];
-        if (id >= 0 && id < P.cap) fl = P.flags[id];
-        else id = -1;
-    }
-    if ((fl & AFV_PTF_SET) && !(fl & AFV_PTF_BAD)) {
-        ok = true;
-        const int fv = J.flavour;
+    {
         const float X = P.pos[0][id], Y = P.pos[1][id], Z = P.pos[2][id];
         const float pcx = pt_sum3(J.R[0] * X, J.R[1] * Y, J.R[2] * Z) + J.t[0];
         const float pcy = pt_sum3(J.R[3] * X, J.R[4] * Y, J.R[5] * Z) + J.t[1];
@@ -52,7 +46,7 @@ __global__ __launch_bounds__(PT_T) void k_points_project(const DevPointsJob J) {
         }
         ur = u - J.mbf * invz;
         if (fv == AFV_PT_LASTFRAME) {
-            size = J.last_size[q];  // :1341
+            size = last_size;  // :1341
         } else {
             const float p0 = X - J.Ow[0], p1 = Y - J.Ow[1], p2 = Z - J.Ow[2];
             const float dist = sqrtf(pt_sum3(p0 * p0, p1 * p1, p2 * p2));
@@ -82,6 +76,28 @@ __global__ __launch_bounds__(PT_T) void k_points_project(const DevPointsJob J) {
         mn = size / J.tol;
         mx = size * J.tol;
         if (!(pt_finite(u) && pt_finite(v) && pt_finite(r) && pt_finite(mn) && pt_finite(mx))) ok = false;  // D1
+    }
+    o.u = u; o.v = v; o.ur = ur; o.r = r; o.er = er; o.size = size; o.sigma = sigma; o.vcos = vcos; o.mn = mn; o.mx = mx;
+    return ok;
+}
+
+__global__ __launch_bounds__(PT_T) void k_points_project(const DevPointsJob J) {
+    __shared__ int s_id[PT_T];  // the point of an in-view query of this workgroup, -1 otherwise: what the gather below reads
+    const int tid = threadIdx.x, q = blockIdx.x * PT_T + tid;
+    const DevPointPlanes &P = J.P;
+    bool ok = false;
+    int id = -1;
+    unsigned fl = 0;
+    float u = 0.0f, v = 0.0f, ur = 0.0f, r = 0.0f, er = 0.0f, size = 0.0f, sigma = 0.0f, vcos = 0.0f, mn = 0.0f, mx = 0.0f;
+    if (q < J.nq) {
+        id = J.ids[q];
+        if (id >= 0 && id < P.cap) fl = P.flags[id];
+        else id = -1;
+    }
+    if ((fl & AFV_PTF_SET) && !(fl & AFV_PTF_BAD)) {
+        PtQuery o;
+        ok = pt_project_one(P, J, J.flavour, id, J.flavour == AFV_PT_LASTFRAME ? J.last_size[q] : 0.0f, o);
+        u = o.u; v = o.v; ur = o.ur; r = o.r; er = o.er; size = o.size; sigma = o.sigma; vcos = o.vcos; mn = o.mn; mx = o.mx;
     }
     if (!ok) u = v = ur = r = er = size = sigma = vcos = mn = mx = 0.0f;
     if (q < J.nq) {
@@ -166,6 +182,95 @@ __global__ __launch_bounds__(PT_T) void k_points_rows(const DevPointPlanes P, co
     if (gather) packed[t] = row[h];
     else if (table) row[h] = reinterpret_cast<const uint4 *>(table + ((size_t)slot[i] * table_cap + idx[i]) * P.words * 4)[h];  // (host-checked references)
     else row[h] = packed[t];
+}
+
+// ---------------- afv_table_fuse_points: Fuse into keyframes of the table ----------------
+//   k_kffuse_project  a workgroup per (target, 256 queries): the AFV_PT_FUSE geometry with the target's camera (pt_project_one), the
+//                     membership test IsInKeyFrame against the slot's plane of point ids held in the LDS, the status 0 / 1 / 2 and the
+//                     rows of the id list (by the first job that names the list)
+//   k_kffuse_finish   behind k_match_fuse: what sits on the winning feature - occupant and the status 3 .. 6
+__global__ __launch_bounds__(PT_T) void k_kffuse_project(const DevPointPlanes P, const DevKfFuseJob *__restrict__ jobs) {
+    __shared__ __attribute__((aligned(16))) int s_plane[4096];  // the slot's mvpMapPoints (a table's cap is at most 4096)
+    __shared__ int s_id[PT_T];
+    const DevKfFuseJob &J = jobs[blockIdx.y];
+    const int tid = threadIdx.x, q = blockIdx.x * PT_T + tid;
+    const int nq = J.nq, n = min(J.n, 4096);
+    if ((int)blockIdx.x * PT_T >= nq) return;  // (uniform)
+    const int n4 = (n + 3) & ~3;
+    for (int i = tid; i < n4; i += PT_T) s_plane[i] = i < n ? J.plane[i] : -1;
+    int id = -1;
+    unsigned fl = 0;
+    if (q < nq) {
+        id = J.ids[q];
+        if (id >= 0 && id < P.cap) fl = P.flags[id];
+        else id = -1;
+    }
+    const bool valid = (fl & AFV_PTF_SET) && !(fl & AFV_PTF_BAD);
+    bool ok = false;
+    PtQuery o{};
+    if (valid) ok = pt_project_one(P, J, AFV_PT_FUSE, id, 0.0f, o);
+    __syncthreads();
+    bool member = false;
+    if (valid) {  // every lane walks the whole plane: the reads are broadcasts, four ids each
+        const int4 *pl = reinterpret_cast<const int4 *>(s_plane);
+        for (int i = 0; i < (n4 >> 2); ++i) {
+            const int4 e = pl[i];
+            member = member || e.x == id || e.y == id || e.z == id || e.w == id;
+        }
+    }
+    const bool search = valid && !member && ok;
+    if (!search) o = PtQuery{};
+    if (q < nq) {
+        J.qu[q] = o.u; J.qv[q] = o.v; J.qr[q] = o.r; J.qmin[q] = o.mn; J.qmax[q] = o.mx; J.q_ur[q] = o.ur;
+        J.qvalid[q] = search ? 1 : 0;
+        J.status[q] = !valid ? 0 : member ? 1 : !ok ? 2 : AFV_KF_PENDING;
+    }
+    if (!J.qd) return;  // (uniform)
+    s_id[tid] = valid ? id : -1;
+    __syncthreads();
+    const int quads = P.words >> 2;
+    for (int t = tid; t < PT_T * quads; t += PT_T) {
+        const int ql = t / quads, h = t - ql * quads, qq = blockIdx.x * PT_T + ql;
+        if (qq >= nq) break;
+        const int i = s_id[ql];
+        uint4 val = make_uint4(0, 0, 0, 0);
+        if (i >= 0) val = reinterpret_cast<const uint4 *>(P.desc + (size_t)i * P.words * 4)[h];
+        J.qd[(size_t)qq * quads + h] = val;
+    }
+}
+
+__global__ __launch_bounds__(PT_T) void k_kffuse_finish(const DevPointPlanes P, const DevKfFuseJob *__restrict__ jobs) {
+    const DevKfFuseJob &J = jobs[blockIdx.y];
+    const int q = blockIdx.x * PT_T + threadIdx.x;
+    if (q >= J.nq) return;
+    const int b = J.best[q];
+    int occ = -1;
+    unsigned st = J.status[q];
+    if (st == AFV_KF_PENDING) {
+        if (b < 0 || b >= J.n) {
+            st = 3;
+        } else {
+            occ = J.plane[b];
+            if (occ < 0) {
+                st = 4;
+            } else {
+                unsigned fl = AFV_PTF_SET;  // an occupant out of range counts as good: the store is not read for it
+                if (occ < P.cap) fl = P.flags[occ];
+                st = ((fl & AFV_PTF_SET) && (fl & AFV_PTF_BAD)) ? 5 : 6;
+            }
+        }
+        J.status[q] = (uint8_t)st;
+    }
+    J.occupant[q] = occ;
+}
+
+extern "C" void afv_launch_kffuse_project(const DevPointPlanes *P, const DevKfFuseJob *jobs, int njobs, int max_nq, hipStream_t stream) {
+    if (njobs <= 0 || max_nq <= 0) return;
+    hipLaunchKernelGGL(k_kffuse_project, dim3((max_nq + PT_T - 1) / PT_T, njobs), dim3(PT_T), 0, stream, *P, jobs);
+}
+extern "C" void afv_launch_kffuse_finish(const DevPointPlanes *P, const DevKfFuseJob *jobs, int njobs, int max_nq, hipStream_t stream) {
+    if (njobs <= 0 || max_nq <= 0) return;
+    hipLaunchKernelGGL(k_kffuse_finish, dim3((max_nq + PT_T - 1) / PT_T, njobs), dim3(PT_T), 0, stream, *P, jobs);
 }
 
 extern "C" void afv_launch_points_project(const DevPointsJob *job, hipStream_t stream) {

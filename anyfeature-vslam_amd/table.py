@@ -493,3 +493,141 @@ class DescriptorTable:
         if n_done < nn:
             raise AfvError(ECAPACITY, "afv_table_create_new_points " + self.lib.afv_last_error(self.ctx.handle).decode())
         return out
+
+    # ---- fusing map points into keyframes of the table: Fuse (FeatureMatcher.cc:794-940, :942-1064) ----
+    RADIUS_SCALE = 1.15  # FeatureMatcher's static radiusScale
+
+    def set_camera(self, min_x, max_x, min_y, max_y, grid_cols, grid_rows, grid_inv_w, grid_inv_h):
+        """the image bounds mnMinX .. mnMaxY and the grid of KeyFrame::GetFeaturesInArea for every slot (what FrameParams carries for a
+        frame); the grid of a slot is built on the device on demand and kept until its geometry, its scale planes or this camera change"""
+        cam = _lib.sized(_lib.TableCamera)
+        cam.min_x, cam.max_x, cam.min_y, cam.max_y = float(min_x), float(max_x), float(min_y), float(max_y)
+        cam.grid_cols, cam.grid_rows, cam.grid_inv_w, cam.grid_inv_h = int(grid_cols), int(grid_rows), float(grid_inv_w), float(grid_inv_h)
+        self.ctx.check(self.lib.afv_table_set_camera(self.handle, C.byref(cam)), "afv_table_set_camera")
+
+    def set_pose(self, slot, Rcw, tcw, Ow, fx, fy, cx, cy, mbf=0.0):
+        """KeyFrame::SetPose of a slot + its intrinsics: Rcw [3, 3], tcw [3], Ow = -Rcw^T tcw as the host computes it (KeyFrame.cc:67-75)"""
+        R = np.ascontiguousarray(Rcw, np.float32).reshape(9)
+        t = np.ascontiguousarray(tcw, np.float32).reshape(3)
+        o = np.ascontiguousarray(Ow, np.float32).reshape(3)
+        self.ctx.check(self.lib.afv_table_set_pose(self.handle, int(slot), ptr(R), ptr(t), ptr(o), float(fx), float(fy), float(cx), float(cy),
+                                                   float(mbf)), "afv_table_set_pose")
+
+    def set_map_points(self, slot, ids):
+        """KeyFrame::mvpMapPoints of a slot: one point id per feature, -1 = none"""
+        ids = _i32(ids).reshape(-1)
+        self.ctx.check(self.lib.afv_table_set_map_points(self.handle, int(slot), ptr(ids) if len(ids) else None), "afv_table_set_map_points")
+
+    def get_map_points(self, slot, n):
+        """the plane of a slot as the device holds it (tests): n = the slot's feature count"""
+        out = np.full(max(int(n), 1), -1, np.int32)
+        self.ctx.check(self.lib.afv_table_get_map_points(self.handle, int(slot), ptr(out)), "afv_table_get_map_points")
+        return out[:int(n)].copy()
+
+    def _fuse(self, points, targets, ids, radiusTh, th_low, use_inf_gate, poses):
+        from .matcher import FeatureMatcher
+        targets = [int(s) for s in targets]
+        nt = len(targets)
+        if nt and isinstance(ids, (list, tuple)) and len(ids) == nt and all(not np.isscalar(v) for v in ids):
+            lists = [v if isinstance(v, np.ndarray) and v.dtype == np.int32 and v.flags.c_contiguous and v.ndim == 1 else _i32(v).reshape(-1)
+                     for v in ids]
+        else:
+            shared = _i32(ids).reshape(-1)
+            lists = [shared] * nt  # one pointer: the targets share one upload and one descriptor gather
+        th = float(FeatureMatcher.TH_LOW if th_low is None else th_low)
+        jobs = (_lib.TableFuseJob * max(nt, 1))()
+        keep = []
+        for k, (s, a) in enumerate(zip(targets, lists)):
+            j = jobs[k]
+            j.struct_size = C.sizeof(_lib.TableFuseJob)
+            j.slot, j.nq = s, len(a)
+            j.ids = a.ctypes.data if len(a) else None
+            j.radius_th, j.radius_scale, j.th_low = float(radiusTh), float(np.float32(self.RADIUS_SCALE)), th
+            j.use_inf_gate = int(bool(use_inf_gate))
+            if poses is not None:
+                R, t, Ow = poses[k]
+                p = _lib.TableFusePose()
+                for name, v, cnt in (("R", R, 9), ("t", t, 3), ("Ow", Ow, 3)):
+                    v = np.asarray(v, np.float32).reshape(cnt)
+                    dst = getattr(p, name)
+                    for q in range(cnt):
+                        dst[q] = float(v[q])
+                keep.append(p)
+                j.pose_override = C.pointer(p)
+        total = sum(len(a) for a in lists)
+        best, occ = np.full(max(total, 1), -1, np.int32), np.full(max(total, 1), -1, np.int32)
+        status, nf = np.zeros(max(total, 1), np.uint8), np.zeros(max(nt, 1), np.int32)
+        self.ctx.check(self.lib.afv_table_fuse_points(self.handle, points.handle, jobs, nt, ptr(best), ptr(occ), ptr(status), ptr(nf)),
+                       "afv_table_fuse_points")
+        cut = np.cumsum([0] + [len(a) for a in lists])
+        split = lambda a: [a[cut[k]:cut[k + 1]].copy() for k in range(nt)]
+        return split(best), split(occ), split(status), nf[:nt].copy()
+
+    def FusePoints(self, points, targets, ids, radiusTh=3.0, th_low=None):
+        """Fuse(pKF, vpMapPoints, th) (FeatureMatcher.cc:794-940) of the store's points `ids` into every slot of `targets` (up to 64) in ONE
+        call.  ids: one list for all targets or a list per target, in the reference's iteration order, -1 allowed.
+        Returns (best, occupant, status, nFused): lists with one array per target over its queries - the winning feature | -1, the point id
+        the slot's plane holds there | -1, _lib.KFFUSE_STATUS - and nFused int32 [len(targets)], what the reference returns.
+        SNAPSHOT: every target is answered against the store and the planes as they stand now; nothing is written.  The map surgery
+        (AddObservation for status 4, Replace for 6) stays with the caller; one target per call with the updates in between gives the
+        reference's sequential loop."""
+        return self._fuse(points, targets, ids, radiusTh, th_low, True, None)
+
+    @staticmethod
+    def decompose_scw(Scw):
+        """Rcw, tcw, Ow of a 4 x 4 Scw as Fuse(pKF, Scw, ...) writes them (FeatureMatcher.cc:954-958), in float, one rounding per
+        operator: scw = the norm of row 0 of sRcw, Rcw = sRcw / scw, Ow = -Rcw^T tcw - and tcw is Scw's translation AS IT STANDS: the
+        reference does not divide it by scw here (a kept quirk; it matters whenever s != 1)"""
+        f32 = np.float32
+        S = np.asarray(Scw, np.float32).reshape(4, 4)
+        sR = S[:3, :3]
+        scw = np.sqrt(f32(sR[0, 0] * sR[0, 0]) + (f32(sR[0, 1] * sR[0, 1]) + f32(sR[0, 2] * sR[0, 2])))
+        R = (sR / f32(scw)).astype(np.float32)
+        t = S[:3, 3].copy()
+        Ow = np.array([f32(-R[0, k]) * t[0] + (f32(-R[1, k]) * t[1] + f32(-R[2, k]) * t[2]) for k in range(3)], np.float32)
+        return R, t, Ow
+
+    def FusePointsSim3(self, points, targets, Scw, ids, radiusTh=4.0, th_low=None):
+        """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (FeatureMatcher.cc:942-1064): as FusePoints, without the reprojection gates, each
+        target seen through its own Scw (a 4 x 4 matrix per target, decomposed by decompose_scw).  Status 6 is vpReplacePoint[iMP]"""
+        poses = [self.decompose_scw(S) for S in Scw]
+        if len(poses) != len(targets):
+            raise ValueError("DescriptorTable.FusePointsSim3: %d targets need %d Scw" % (len(targets), len(targets)))
+        return self._fuse(points, targets, ids, radiusTh, th_low, False, poses)
+
+    def SearchInNeighborsFuse(self, points, cur, targets, ids_cur, ids_of_target, on_fuse, radiusTh=3.0, th_low=None):
+        """both halves of LocalMapping::SearchInNeighbors (LocalMapping.cc:505-533) with the reference's sequential semantics: one target
+        per call, the caller's map surgery in between.  ids_cur(): the current keyframe's points at the time of the call (vpMapPointMatches
+        is taken once, :507, so it is called once); ids_of_target(slot): GetMapPointMatches of a target when the second half reaches it.
+        on_fuse(slot, ids, best, occupant, status) does AddObservation / Replace and must refresh the store flags and the planes it changed
+        (set_flags, set_map_points).  The second half's candidate list is built with the mnFuseCandidateForKF de-duplication of :517-533.
+        Returns (nFused per target, nFused of the second half)"""
+        first = ids_cur()
+        nf = []
+        for s in targets:
+            b, o, st, n = self.FusePoints(points, [s], first, radiusTh, th_low)
+            on_fuse(int(s), np.asarray(first, np.int32), b[0], o[0], st[0])
+            nf.append(int(n[0]))
+        cand, seen = [], set()
+        for s in targets:
+            for i in ids_of_target(int(s)):
+                i = int(i)
+                if i < 0 or i in seen:  # (a bad point stays in the list: the store knows it and answers status 0, as :523 skips it)
+                    continue
+                seen.add(i)
+                cand.append(i)
+        b, o, st, n = self.FusePoints(points, [cur], cand, radiusTh, th_low)
+        on_fuse(int(cur), np.asarray(cand, np.int32), b[0], o[0], st[0])
+        return nf, int(n[0])
+
+    def SearchAndFuse(self, points, corrected, Scw, loop_ids, on_fuse, radiusTh=4.0, th_low=None):
+        """LoopClosing::SearchAndFuse (LoopClosing.cc:601-628): the loop map points into every corrected keyframe through its corrected
+        Scw, one target per call; on_fuse(slot, ids, best, occupant, status) replaces the occupants of status 6 (:616-624).
+        Returns nFused per keyframe"""
+        ids = _i32(loop_ids).reshape(-1)
+        nf = []
+        for s, S in zip(corrected, Scw):
+            b, o, st, n = self.FusePointsSim3(points, [s], [S], ids, radiusTh, th_low)
+            on_fuse(int(s), ids, b[0], o[0], st[0])
+            nf.append(int(n[0]))
+        return nf

@@ -1577,6 +1577,71 @@ int afv_debug_fast_tiles(const afv_orb_params *params, int width, int height, in
  * tests/test_describe_reach_cpu.py holds the tables to an angle sweep of the pattern. */
 int afv_debug_describe_reach(uint8_t *R, uint16_t *items, uint16_t *dwords, int32_t *counts, int32_t *layout);
 
+/* ---- fusing map points into keyframes of the table: FeatureMatcher::Fuse(pKF, vpMapPoints, th) (FeatureMatcher.cc:794-940) and
+ * Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:942-1064) as LocalMapping::SearchInNeighbors (LocalMapping.cc:475-555) and
+ * LoopClosing::SearchAndFuse (LoopClosing.cc:601-628) run them: the points of a resident store into up to 64 table slots in one call.
+ * What a slot needs next to its rows, geometry (afv_table_set_geometry) and scale planes (afv_table_set_scale): the table's camera, a pose
+ * (or a pose_override in the job) and the keyframe's mvpMapPoints as a plane of point ids; with use_inf_gate its information plane
+ * (afv_table_set_inf).  All of it is allocated on first use and nothing existing changes its behaviour.
+ *
+ * The camera of the table: the image bounds mnMinX .. mnMaxY and the grid of KeyFrame::GetFeaturesInArea (KeyFrame.cc:613-652), the
+ * fields afv_frame_params carries for a frame; sizeTolerance is the context's scale factor, as for frames.  grid_cols * grid_rows <= 8192
+ * (else AFV_EINVAL); a grid whose one-workgroup build does not fit the LDS: AFV_EUNSUPPORTED.  The grid of a slot is built on the device
+ * by the kernel that builds a frame's (cells in ix, iy order, ascending feature index inside a cell), on demand by the fuse call, and kept
+ * until the slot's geometry, scale planes or the camera change.
+ * The pose of a slot: the argument rule of afv_frame_set_pose (Ow computed by the host with the reference's own expression); kept on the
+ * host side of the table.  The plane: ids[n] over the slot's features, -1 = no point.  afv_table_set forgets pose and plane of its slot;
+ * afv_table_clone carries both along (and the camera).
+ *
+ * Per (job, query), packed in job order: best (feature index | -1), occupant (the id the plane holds at best | -1) and status:
+ *   0  invalid query: id -1, never set, or bad in the store
+ *   1  already in the keyframe: the id occurs in the slot's plane (IsInKeyFrame / spAlreadyFound: one rule for both overloads)
+ *   2  not in view: any geometric test of the AFV_PT_FUSE rule set, deviation D1 included
+ *   3  no feature won: empty window, every candidate gated, or bestDist > th_low
+ *   4  the winning feature is free: the host adds the observation
+ *   5  the winning feature holds a point that is bad in the store (the reference counts it and does nothing)
+ *   6  the winning feature holds a good point: Replace / vpReplacePoint.  An occupant id outside [0, capacity) or never set counts as
+ *      good; the store is not read for it.
+ * nfused[job] counts statuses 4 to 6: what the reference returns.  The geometry is AFV_PT_FUSE's with the camera of the job, the search
+ * that of afv_match_fuse (one kernel text for both); use_inf_gate = 1 is Fuse no. 1 with its 5.99 / 7.8 gates, 0 is Fuse no. 2.
+ * SNAPSHOT RULE: every job is answered against the store and the planes as they stand when the call is made; the call writes neither.
+ * Two queries of a job may win the same free feature (both status 4); AddObservation, Replace and ComputeDistinctiveDescriptors stay
+ * with the caller.  One target per call with the caller's updates in between gives the reference's loop.
+ * Limits: nt 0 .. 64, nq <= 65535 per job, the nq of a call sum to at most AFV_KFFUSE_MAX_QUERIES; jobs that pass the same ids pointer
+ * and nq share one descriptor gather.  Refused before any launch, outputs untouched (AFV_EINVAL unless noted): nt out of range, a slot
+ * out of range, a slot without geometry, scale planes, information plane (use_inf_gate), map-point plane or pose (a pose_override replaces
+ * Rcw, tcw and Ow only: the intrinsics are always those given with afv_table_set_pose), no camera, store and table on different contexts, a store of another descriptor kind or width (AFV_EUNSUPPORTED), an id outside
+ * [-1, capacity), a query total beyond the cap, an unknown struct_size.
+ * New symbols and records only: AFV_ABI_VERSION stays 6. */
+#define AFV_KFFUSE_MAX_TARGETS 64
+#define AFV_KFFUSE_MAX_QUERIES (1 << 20)
+typedef struct {
+    uint32_t struct_size;         /* sizeof(afv_table_camera) */
+    float min_x, max_x, min_y, max_y;   /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+    int32_t grid_cols, grid_rows;
+    float grid_inv_w, grid_inv_h;       /* mfGridElementWidthInv, mfGridElementHeightInv */
+} afv_table_camera;
+typedef struct {
+    float R[9], t[3], Ow[3];      /* Fuse no. 2: the decomposed Scw (sRcw / scw, Scw's translation as it stands, -Rcw^T tcw) */
+} afv_table_fuse_pose;
+typedef struct {
+    uint32_t struct_size;         /* sizeof(afv_table_fuse_job) */
+    int32_t slot;
+    const int32_t *ids;           /* [nq] host: point id | -1, in the reference's iteration order */
+    int32_t nq;
+    float radius_th, radius_scale, th_low;
+    int32_t use_inf_gate;
+    const afv_table_fuse_pose *pose_override;   /* NULL: the slot's pose */
+} afv_table_fuse_job;
+int afv_table_set_camera(afv_table *t, const afv_table_camera *cam);
+int afv_table_set_pose(afv_table *t, int slot, const float *Rcw, const float *tcw, const float *Ow, float fx, float fy, float cx, float cy,
+                       float mbf);
+int afv_table_set_map_points(afv_table *t, int slot, const int32_t *ids);
+/* for tests: the plane of a slot, n ints.  AFV_EINVAL for a slot without a plane.  Synchronous. */
+int afv_table_get_map_points(afv_table *t, int slot, int32_t *ids);
+int afv_table_fuse_points(afv_table *t, afv_points *points, const afv_table_fuse_job *jobs, int nt, int32_t *best, int32_t *occupant,
+                          uint8_t *status, int32_t *nfused);
+
 #ifdef __cplusplus
 }
 #endif
