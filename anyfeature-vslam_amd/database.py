@@ -46,7 +46,8 @@ class KeyFrameDatabase:
         for s in self._seq:
             mask[s] = 1
         for s in exclude:
-            mask[int(s)] = 0
+            if 0 <= int(s) < self.table.nsets:   # an id outside the table names no keyframe here (a negative one must not wrap around)
+                mask[int(s)] = 0
         return mask
 
     def _sharing(self, query, mask):
@@ -138,7 +139,7 @@ class KeyFrameDatabase:
     # ---- LoopClosing::DetectLoop, the reference score (LoopClosing.cc:142-155) ----
     def min_score_to_connected(self, slot, connected):
         """the lowest score between keyframe `slot` and its covisible keyframes `connected` (the caller leaves out the bad ones)"""
-        connected = [int(s) for s in connected]
+        connected = [int(s) for s in connected if 0 <= int(s) < self.table.nsets]   # ids outside the table: skipped, like the C++ mirror
         min_score = F32(1)
         if not connected:
             return min_score

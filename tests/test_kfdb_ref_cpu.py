@@ -1,6 +1,7 @@
 """CPU: the plain-Python restatement of DBoW2's BowVector / L1 score and of KeyFrameDatabase.cc:76-309 / LoopClosing.cc:142-155
 (tests/_kfdb_ref.py) against answers worked out by hand; the scenes of tests/_bow_scenes.py meet the conditions that keep the GPU tests
-from being vacuous (asserted on the restatement alone); the new C-ABI names are declared and exported."""
+from being vacuous (asserted on the restatement alone); the new C-ABI names are declared and exported.  The constructed scenes of tests/_kfdb_scenes.py:
+each reaches the rule it names (trace counters) and is moved by the flip it names - a scene that no flip moves fails."""
 import ctypes as C
 import os
 
@@ -9,6 +10,7 @@ import pytest
 
 import _bow_scenes as scenes
 import _kfdb_ref as ref
+import _kfdb_scenes as ks
 
 F32 = np.float32
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -152,3 +154,164 @@ def _conditions(out, tr):
     failed = [k for (a, k), kf in zip(tr["acc"], tr["passed"]) if not a > tr["min_retain"]]
     assert len(tr["passed"]) < len(tr["scored"]) or failed                            # (c)
     assert any(k != kf for (a, k), kf in zip(tr["acc"], tr["passed"]) if a > tr["min_retain"])   # (d): a returned entry names another keyframe
+
+
+# ---------------- the constructed scenes of tests/_kfdb_scenes.py: every rule is reached, every scene is moved by its flip ----------------
+
+def _bits(bow):
+    return list(bow.keys()), np.array(list(bow.values()), np.float64).tobytes()
+
+
+def test_flips_are_named_and_silent_by_default():
+    assert len(set(ref.FLIPS)) == 14
+    with pytest.raises(ValueError):
+        ref.bow_vector([], [], [], flip="common_ge")
+    with pytest.raises(ValueError):
+        ref.l1_score({}, {}, flip="no_such_flip")
+    tr = {}
+    assert _db([{0: 1.0}]).detect_relocalization_candidates({0: 1.0}, lambda s: [], tr) == [0]
+    assert all(tr[c] == 0 for c in ref.COUNTERS)
+
+
+def test_bow_scenes_cover_the_sizes_the_issue_names():
+    S = {s.name: s for s in ks.bow_scenes()}
+    assert len(S) == len(ks.bow_scenes())
+    assert {len(s.leaves) for s in S.values()} >= {0, 1, 63, 64, 65, 1023, 1024, 1025, 4097, 8192}
+    assert {len(s.want()) for s in S.values()} >= {0, 1, 1024, 1025, 2049, 8192}
+    w = ks.weights("mixed")
+    pos = w[w > 0]
+    assert pos.min() < 2.0 ** -38 and pos.max() > 2.0 ** 9 and len(set(np.frexp(pos)[1].tolist())) >= 50
+    _, word_id, is_leaf = ks.tree()
+    assert int(is_leaf.sum()) == 10000
+    # the descriptor pool reaches every leaf a scene uses, by the CPU descent
+    desc, leaf, reach, row_of = ks.pool()
+    for s in S.values():
+        assert set(s.leaves.tolist()) <= set(reach.tolist())
+    assert all(leaf[row_of[int(l)]] == l for l in reach[::97])
+    # runs_3_9: in the sorted keys, runs of 3 and of 9 start at every offset modulo the 8 keys of a thread's stretch
+    keys = np.sort(word_id[S["runs_3_9"].leaves])
+    starts = np.flatnonzero(np.r_[True, keys[1:] != keys[:-1]])
+    length = np.diff(np.r_[starts, len(keys)])
+    for run in (3, 9):
+        assert set((starts[length == run] % 8).tolist()) == set(range(8))
+    # heavy_word: one run of 8190 keys; half_stopped: stopped and kept features alternate all through the feature order
+    hw = word_id[S["heavy_word"].leaves]
+    assert np.bincount(hw).max() == 8190
+    for name in ("half_stopped_8192", "half_stopped_4097"):
+        kept = S[name].weight[S[name].leaves] > 0
+        assert 0.3 < kept.mean() < 0.7 and kept[:64].any() and (~kept[:64]).any() and kept[-64:].any() and (~kept[-64:]).any()
+    assert not (S["all_stopped"].weight > 0).any() and S["all_stopped"].want() == {}
+
+
+@pytest.mark.parametrize("scene", ks.bow_scenes(), ids=lambda s: s.name)
+def test_bow_scene_is_moved_by_its_flips(scene):
+    want = scene.want()
+    assert list(want.keys()) == sorted(want.keys())
+    if not scene.flips:
+        # a size edge: at most one entry, and then its value is v / v = 1.0: there is no arithmetic a flip could change
+        assert len(want) <= 1 and list(want.values()) in ([], [1.0])
+        assert all(_bits(scene.want(f)) == _bits(want) for f in ref.BOW_FLIPS)
+        return
+    for f in scene.flips:
+        assert f in ref.BOW_FLIPS
+        assert _bits(scene.want(f)) != _bits(want), "%s is not moved by %s" % (scene.name, f)
+        assert list(scene.want(f).keys()) == list(want.keys())          # the flips move bits, not words
+
+
+def test_score_scenes_follow_the_launch_rule():
+    S = {s.name: s for s in ks.score_scenes()}
+    assert ks.slots_per_wg(5, 99) == 4 and ks.slots_per_wg(1, 1) == 4 and ks.slots_per_wg(65535, 100000) == 64
+    for name, per in (("batch_8", 8), ("batch_64", 64)):
+        s = S[name]
+        assert ks.slots_per_wg(len(s.queries), s.nsets) == per and s.nsets % per and s.cap <= 40
+        kinds = [x if isinstance(x, str) else "bow" for x in s.slots]
+        assert kinds.count(ks.NO_BOW) >= 3 and kinds.count(ks.EMPTY) >= 3 and 0 < s.mask.sum() < s.nsets
+        assert any(isinstance(x, dict) and not x for x in s.slots) and any(isinstance(q, tuple) for q in s.queries)
+        assert len({id(s.query_bow(q)) for q in s.queries}) <= 40          # a handful of distinct queries, repeated
+        # the slots one wavefront visits in a row never hold the same vector
+        assert all(s.slots[i] is not s.slots[i + 4] or isinstance(s.slots[i], str) for i in range(s.nsets - 4))
+    for s in S.values():
+        if not s.name.startswith("batch"):
+            assert ks.slots_per_wg(len(s.queries), s.nsets) == 4
+    sizes = {len(x) for x in S["chunk_edges"].slots if isinstance(x, dict)}
+    assert sizes >= {0, 1, 63, 64, 65, 129}
+    assert {len(S["query_edges"].query_bow(q)) for q in S["query_edges"].queries} >= {0, 1, 8192}
+
+
+@pytest.mark.parametrize("scene", ks.score_scenes(), ids=lambda s: s.name)
+def test_score_scene_is_moved_by_its_flips(scene):
+    common, score, first = scene.want()
+    for r, s, (c, sc, f) in scene.facts:                                 # the cells worked out by hand
+        assert (common[r, s], first[r, s]) == (c, f), (scene.name, r, s)
+        if sc is not None:
+            assert score[r, s].tobytes() == np.float64(sc).tobytes(), (scene.name, r, s)   # bits: -0.0 is not +0.0
+    assert scene.flips
+    for f in scene.flips:
+        c2, s2, f2 = scene.want(flip=f)
+        assert s2.tobytes() != score.tobytes(), "%s is not moved by %s" % (scene.name, f)
+        assert np.array_equal(c2, common) and np.array_equal(f2, first)
+    masked = scene.want(mask=scene.mask)
+    assert (masked[0][:, scene.mask == 0] == -1).all() and np.array_equal(masked[0][:, scene.mask == 1], common[:, scene.mask == 1])
+
+
+def test_zero_scores_carry_the_sign_the_reference_gives():
+    s = [x for x in ks.score_scenes() if x.name == "signed_values"][0]
+    _, score, _ = s.want()
+    assert score[0, 1] == 0 and np.signbit(score[0, 1])                  # shared words, all terms +0: -(+0) / 2
+    assert score[0, 3] == 0 and not np.signbit(score[0, 3])              # nothing shared: the literal 0
+
+
+@pytest.mark.parametrize("scene", ks.decision_scenes(), ids=lambda s: s.name)
+def test_decision_scene_reaches_its_rule_and_is_moved_by_its_flip(scene):
+    traces = []
+    want = ks.run_ref(scene, traces=traces)
+    assert any(isinstance(a, list) and a for a in want)                  # some query returns candidates
+    if scene.counter:
+        assert sum(t[scene.counter] for t in traces) >= 1, "%s never meets %s" % (scene.name, scene.counter)
+    assert scene.flip in ref.DETECT_FLIPS
+    flipped = ks.run_ref(scene, flip=scene.flip)
+    assert [list(a) if isinstance(a, list) else a.tobytes() for a in flipped] != \
+        [list(a) if isinstance(a, list) else a.tobytes() for a in want], "%s is not moved by %s" % (scene.name, scene.flip)
+    assert ks.run_ref(scene) == want                                     # a fresh database gives the same answers
+    out = ks.parse_script_output("".join("%s: %s\n" % ("minscore" if not isinstance(a, list) else "q", float(a).hex() if not isinstance(a, list)
+                                                         else " ".join(map(str, a))) for a in want))
+    assert [a if isinstance(a, list) else a.tobytes() for a in out] == [a if isinstance(a, list) else a.tobytes() for a in want]
+
+
+def test_decision_scenes_cover_every_flip_and_the_edges():
+    S = ks.decision_scenes()
+    assert {s.flip for s in S} == set(ref.DETECT_FLIPS)
+    adds = [[op[1] for op in s.ops if op[0] == "add"] for s in S]
+    assert all(a != sorted(a) for a in adds)                             # never in ascending slot order
+    covis = [c for s in S for v in s.covis.values() for c in v]
+    assert any(c >= 8 for c in covis) and any(c < 0 for c in covis)      # covisibles outside the table
+    assert any(op[0] == "erase" and any(op[1] in v for v in s.covis.values()) for s in S for op in s.ops)   # an erased covisible
+    assert any(op[0] == "loop" and set(op[3]) & {c for v in s.covis.values() for c in v} for s in S for op in s.ops)   # connected and covisible
+    # int(max * 0.8f) in float: 0.8f is above 0.8, the products truncate where the scenes say
+    assert [int(F32(m) * F32(0.8)) for m in (2, 5, 7, 8)] == [1, 4, 5, 6]
+    assert "script " in ks.script_text(S[0])
+
+
+class _RestatedTable:
+    """DescriptorTable.score_bow answered by the restatement: what database.py needs of a table, without a device"""
+
+    def __init__(self, scene):
+        self.nsets, self.bows = scene.nsets, scene.bows
+
+    def score_bow(self, queries, slot_mask=None, want_first=True):
+        common = np.full((len(queries), self.nsets), -1, np.int32); score = np.zeros((len(queries), self.nsets)); first = np.full((len(queries), self.nsets), -1, np.int32)
+        for r, q in enumerate(queries):
+            qb = self.bows[q] if isinstance(q, (int, np.integer)) else dict(zip(q[0].tolist(), q[1].tolist()))
+            for s, b in self.bows.items():
+                if slot_mask is None or slot_mask[s]:
+                    common[r, s], score[r, s], first[r, s] = ref.l1_score(qb, b)
+        return common, score, first if want_first else None
+
+
+@pytest.mark.parametrize("scene", ks.decision_scenes(), ids=lambda s: s.name)
+def test_decision_scene_on_the_python_mirror_over_restated_scores(afv, scene):
+    """database.py's own float arithmetic, order and bookkeeping, with the scores taken from the restatement (the device route is
+    tests/test_gpu_kfdb_scenes.py)"""
+    got = ks.run_db(scene, afv.KeyFrameDatabase(_RestatedTable(scene)))
+    want = ks.run_ref(scene)
+    assert [a if isinstance(a, list) else a.tobytes() for a in got] == [a if isinstance(a, list) else a.tobytes() for a in want]
