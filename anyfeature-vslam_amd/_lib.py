@@ -489,6 +489,10 @@ SYMBOLS = {
     "afv_debug_get_candidates": (_i, [_vp, _i, _i, _vp, _vp, _i, C.POINTER(_i)]),
     "afv_debug_get_selected": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_i)]),
     "afv_debug_blur_level": (_i, [_vp, _i, _i, _vp]),
+    "afv_debug_scratch_bytes": (_i, [_vp, _vp, _i]),
+    "afv_debug_paint_scratch": (_i, [_vp, _i]),
+    "afv_debug_rest_words": (_i, [_vp, C.POINTER(C.c_int32)]),
+    "afv_debug_scratch_read": (_i, [_vp, _i, C.c_size_t, _vp, C.c_size_t]),
     "afv_num_stages": (_i, []),
 }
 

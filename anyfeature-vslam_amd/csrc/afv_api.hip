@@ -4,6 +4,8 @@
 // pipeline, its entry points) is afv_extract.hip; the BoW-guided matchers are afv_match_jobs.hip; the projection searches are
 // afv_project.hip.
 // No CPU fallback exists: without a HIP device afv_create fails with AFV_ENODEV.
+#include <algorithm>
+
 #include "afv_runtime.h"
 
 static const char *k_errors[] = {"ok", "invalid argument", "no usable HIP device", "out of memory", "HIP runtime error",
@@ -243,6 +245,102 @@ extern "C" int afv_profile_read(afv_ctx *c, int32_t *launches, float *total_ms, 
         total_ms[st] = c->prof_ms[st];
         if (units) units[st] = c->prof_units[st];
     }
+    return AFV_OK;
+}
+
+// ---- test hooks for the per-call scratch (include/afv_hip.h, "test hooks for the per-call scratch"): sizes, a fill, the zero-at-rest
+// words.  The list of buffers is the header comment's; nothing in the product calls these ----
+static int scratch_quiesce(afv_ctx *c) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
+    return AFV_OK;
+}
+
+// slot -> the buffers it stands for, in a fixed order; host: they are host memory (memset / memcpy), else device memory
+static void scratch_segments(afv_ctx *c, std::vector<ScratchSeg> seg[AFV_SCRATCH_SLOTS]) {
+    seg[AFV_SCRATCH_D_MATCH].push_back(ScratchSeg{c->d_match, c->match_bytes});
+    seg[AFV_SCRATCH_H_STAGE].push_back(ScratchSeg{c->h_stage, c->stage_bytes});
+    seg[AFV_SCRATCH_D_TOPK].push_back(ScratchSeg{c->d_topk, c->topk_bytes});
+    seg[AFV_SCRATCH_D_SLICE].push_back(ScratchSeg{c->d_slice, c->slice_bytes});
+    seg[AFV_SCRATCH_D_L2].push_back(ScratchSeg{c->d_l2_scratch, c->l2_bytes});
+    for (const afv_points *p : c->points) {
+        seg[AFV_SCRATCH_POINTS_STAGE].push_back(ScratchSeg{p->d_stage, p->stage_bytes});
+        seg[AFV_SCRATCH_POINTS_PIN].push_back(ScratchSeg{p->h_pin, p->pin_bytes});
+    }
+    afv_tables_pair_scratch(c, seg[AFV_SCRATCH_TABLE_PAIRS], seg[AFV_SCRATCH_TABLE_PIN]);
+    for (int i = 0; i < AFV_SCRATCH_SLOTS; ++i) {  // a buffer that was never made counts as empty
+        auto &v = seg[i];
+        v.erase(std::remove_if(v.begin(), v.end(), [](const ScratchSeg &s) { return !s.p || !s.n; }), v.end());
+    }
+}
+static inline bool scratch_on_host(int slot) { return slot == AFV_SCRATCH_H_STAGE || slot == AFV_SCRATCH_POINTS_PIN || slot == AFV_SCRATCH_TABLE_PIN; }
+
+extern "C" int afv_debug_scratch_bytes(afv_ctx *c, size_t *out, int n) {
+    if (!c || !out || n < 1) return AFV_EINVAL;
+    std::vector<ScratchSeg> seg[AFV_SCRATCH_SLOTS];
+    scratch_segments(c, seg);
+    for (int i = 0; i < n && i < AFV_SCRATCH_SLOTS; ++i) {
+        out[i] = 0;
+        for (const ScratchSeg &s : seg[i]) out[i] += s.n;
+    }
+    return AFV_OK;
+}
+
+extern "C" int afv_debug_paint_scratch(afv_ctx *c, int byte) {
+    if (!c || byte < 0 || byte > 255) return AFV_EINVAL;
+    int rc = scratch_quiesce(c);
+    if (rc) return rc;
+    for (afv_points *p : c->points)
+        if (p->ev_armed) HIPCHK(c, hipEventSynchronize(p->ev));  // the stream was waited for: the upload out of h_pin is over
+    std::vector<ScratchSeg> seg[AFV_SCRATCH_SLOTS];
+    scratch_segments(c, seg);
+    for (int i = 0; i < AFV_SCRATCH_SLOTS; ++i)
+        for (const ScratchSeg &s : seg[i]) {
+            if (scratch_on_host(i)) std::memset(s.p, byte, s.n);
+            else HIPCHK(c, afv_fill(c, s.p, byte, s.n));
+        }
+    return AFV_OK;
+}
+
+extern "C" int afv_debug_rest_words(afv_ctx *c, int32_t *nonzero) {
+    if (!c || !nonzero) return AFV_EINVAL;
+    *nonzero = -1;
+    int rc = scratch_quiesce(c);
+    if (rc) return rc;
+    std::vector<int32_t> w(3 + c->tickets_n, 0);
+    if (c->d_proj_ticket) HIPCHK(c, hipMemcpyAsync(w.data(), c->d_proj_ticket, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (c->d_points_count) HIPCHK(c, hipMemcpyAsync(w.data() + 1, c->d_points_count, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (c->d_tickets && c->tickets_n)
+        HIPCHK(c, hipMemcpyAsync(w.data() + 3, c->d_tickets, c->tickets_n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int32_t n = 0;
+    for (int32_t v : w) n += v != 0;
+    *nonzero = n;
+    return AFV_OK;
+}
+
+extern "C" int afv_debug_scratch_read(afv_ctx *c, int which, size_t offset, void *out, size_t bytes) {
+    if (!c || !out || which < 0 || which >= AFV_SCRATCH_SLOTS) return AFV_EINVAL;
+    std::vector<ScratchSeg> seg[AFV_SCRATCH_SLOTS];
+    scratch_segments(c, seg);
+    size_t total = 0;
+    for (const ScratchSeg &s : seg[which]) total += s.n;
+    if (offset > total || bytes > total - offset) return AFV_EINVAL;
+    int rc = scratch_quiesce(c);
+    if (rc) return rc;
+    uint8_t *dst = static_cast<uint8_t *>(out);
+    size_t base = 0;  // the slot's buffers read as one run of bytes, in the order of scratch_segments
+    for (const ScratchSeg &s : seg[which]) {
+        const size_t lo = std::max(offset, base), hi = std::min(offset + bytes, base + s.n);
+        if (lo < hi) {
+            const uint8_t *src = static_cast<const uint8_t *>(s.p) + (lo - base);
+            if (scratch_on_host(which)) std::memcpy(dst + (lo - offset), src, hi - lo);
+            else HIPCHK(c, hipMemcpyAsync(dst + (lo - offset), src, hi - lo, hipMemcpyDeviceToHost, c->stream));
+        }
+        base += s.n;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return AFV_OK;
 }
 

@@ -478,6 +478,20 @@ static int table_reserve_pairs(afv_table *t, int npairs) {
     return AFV_OK;
 }
 
+// test hooks (afv_debug_scratch_bytes / _paint_scratch / _scratch_read): the buffers of table_reserve_pairs of every table of `c`.  Scratch
+// by contract: afv_table_match_pairs uploads the pairs, the matcher writes d_out / d_nm, the call copies them out and nothing reads them later
+AFV_LOCAL void afv_tables_pair_scratch(afv_ctx *c, std::vector<ScratchSeg> &dev, std::vector<ScratchSeg> &pin) {
+    std::lock_guard<std::mutex> g(g_reg_mutex);
+    for (afv_table *t : g_tables) {
+        if (t->c != c || !t->pair_cap) continue;
+        const size_t pc = (size_t)t->pair_cap, n_pairs = pc * 2 * sizeof(int32_t), n_out = pc * t->cap * sizeof(int32_t), n_nm = pc * sizeof(int32_t);
+        dev.push_back(ScratchSeg{t->d_pairs, n_pairs});
+        dev.push_back(ScratchSeg{t->d_out, n_out});
+        dev.push_back(ScratchSeg{t->d_nm, n_nm});
+        pin.push_back(ScratchSeg{t->h_pin, n_pairs + n_nm + n_out});  // [2][pair_cap] pairs, [pair_cap] counts, [pair_cap][cap] matches
+    }
+}
+
 static int check_pairs(const afv_table *t, const int32_t *pa, const int32_t *pb, int npairs) {
     for (int i = 0; i < npairs; ++i)
         if (pa[i] < 0 || pa[i] >= t->nsets || pb[i] < 0 || pb[i] >= t->nsets) return AFV_EINVAL;

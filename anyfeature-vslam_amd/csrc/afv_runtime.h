@@ -842,6 +842,10 @@ struct afv_table {
     int4 *d_kf_cell_ent = nullptr;   // [nsets][cap]
     int kf_cells = 0;                // cells the grid planes were allocated for
 };
+// afv_comm.hip, for the scratch test hooks (afv_api.hip): the pair buffers of every table of context `c`, in the order the tables were
+// made - per table d_pairs, d_out, d_nm appended to `dev`, the pinned image h_pin to `pin`
+struct ScratchSeg { void *p; size_t n; };
+AFV_LOCAL void afv_tables_pair_scratch(afv_ctx *c, std::vector<ScratchSeg> &dev, std::vector<ScratchSeg> &pin);
 // afv_kffuse.hip: what the table's own entry points (afv_comm.hip) tell the fuse state of a slot
 AFV_LOCAL void afv_kffuse_slot_reset(afv_table *t, int slot);   // afv_table_set / a promoted frame: pose, plane and grid are forgotten
 AFV_LOCAL void afv_kffuse_grid_stale(afv_table *t, int slot);   // the geometry or the scale planes changed (slot < 0: every slot)

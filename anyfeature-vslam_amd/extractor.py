@@ -269,6 +269,33 @@ class Context:
         self.check(self.lib.afv_debug_get_selected(self.handle, frame, level, ptr(x), ptr(y), ptr(r), cap, C.byref(n)))
         return x[:n.value].copy(), y[:n.value].copy(), r[:n.value].copy()
 
+    # ---- test hooks for the per-call scratch (tests/test_gpu_scratch.py; nothing in the product calls them) ----
+    SCRATCH_NAMES = ("d_match", "h_stage", "d_topk", "d_slice", "d_l2_scratch", "points_stage", "points_pin", "table_pairs", "table_pin")
+
+    def scratch_bytes(self):
+        """afv_debug_scratch_bytes: the current size of every per-call scratch buffer, in the order of SCRATCH_NAMES"""
+        out = np.zeros(len(self.SCRATCH_NAMES), np.uintp)
+        self.check(self.lib.afv_debug_scratch_bytes(self.handle, ptr(out), len(out)))
+        return tuple(int(v) for v in out)
+
+    def paint_scratch(self, byte):
+        """afv_debug_paint_scratch: fill every byte of those buffers"""
+        self.check(self.lib.afv_debug_paint_scratch(self.handle, int(byte)))
+
+    def rest_words(self):
+        """afv_debug_rest_words: how many of the zero-at-rest words (d_proj_ticket, d_points_count, d_tickets) are not zero"""
+        n = C.c_int32(-1)
+        self.check(self.lib.afv_debug_rest_words(self.handle, C.byref(n)))
+        return int(n.value)
+
+    def scratch_read(self, which, offset, nbytes):
+        """afv_debug_scratch_read: bytes [offset, offset + nbytes) of buffer `which` (index or name; the first five of SCRATCH_NAMES)"""
+        if isinstance(which, str):
+            which = self.SCRATCH_NAMES.index(which)
+        out = np.zeros(int(nbytes), np.uint8)
+        self.check(self.lib.afv_debug_scratch_read(self.handle, int(which), int(offset), ptr(out), int(nbytes)))
+        return out
+
 
 class FeatureExtractor_orb32:
     """Mirror of FeatureExtractor_orb32 (Feature_orb32.h:12-33) + the FeatureExtractor base (FeatureExtractor.h:68-161).

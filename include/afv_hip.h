@@ -1577,6 +1577,43 @@ int afv_debug_fast_tiles(const afv_orb_params *params, int width, int height, in
  * tests/test_describe_reach_cpu.py holds the tables to an angle sweep of the pattern. */
 int afv_debug_describe_reach(uint8_t *R, uint16_t *items, uint16_t *dwords, int32_t *counts, int32_t *layout);
 
+/* ---- test hooks for the per-call scratch of a context (tests/test_gpu_scratch.py).  Nothing in the product calls them. ----
+ * Every entry point lays its inputs, outputs and device-only scratch into grow-only buffers of its context and must not depend on what
+ * an earlier call left there.  These hooks make that a property a test can check: report the buffers' sizes, fill them with a byte,
+ * read them back, and read the words every call has to leave zero.
+ *
+ * afv_debug_scratch_bytes: out[i] for i < min(n, AFV_SCRATCH_SLOTS), in this order (the AFV_SCRATCH_* indices):
+ *   0 d_match       device staging of the matcher / solver entry points (Blob)
+ *   1 h_stage       its pinned host image
+ *   2 d_topk        key records of the brute-force pair matcher
+ *   3 d_slice       per-slice key records of the column-sliced phase 1
+ *   4 d_l2_scratch  key records of the float pair matcher
+ *   5 sum over the context's map-point stores of afv_points::d_stage (device staging of the setters / afv_points_get)
+ *   6 sum over them of afv_points::h_pin (its pinned image)
+ *   7 sum over the context's keyframe tables of the pair buffers d_pairs + d_out + d_nm (afv_table_match_pairs)
+ *   8 sum over them of the pinned image h_pin of those
+ * afv_debug_paint_scratch: waits for the context's stream, then fills every byte of exactly those buffers with `byte` - the device ones
+ * on the context's own stream (and waits), the host ones with memset.
+ * LEFT OUT, because they carry state from one call to the next by design or are not per-call scratch:
+ *   d_proj_ticket, d_points_count, d_tickets   zero at rest: afv_debug_rest_words reads them
+ *   the extraction working set (d_pyr, d_cand_*, d_l1*, d_hq*, d_kept_*, d_sel*, d_frames, d_out_block, d_n, d_status; sized once at
+ *     afv_create / afv_set_geometry)   the afv_debug_get_* getters read the last extraction out of it, and its counters are cleared by
+ *     the extraction itself; tests/test_gpu_extract*.py compare it stage by stage
+ *   d_geo, d_tab, d_pf_blob   the geometry's plan, written when the geometry is set and read by every extraction
+ *   the planes of frames, map-point stores and tables, a frame's pyramid and grid, a table's d_mp / d_kf_cell_*   resident data
+ *   the AKAZE context (akaze_api.hip)   a context type of its own
+ * afv_debug_rest_words: waits for the context's stream, copies d_proj_ticket, both words of d_points_count (once a map-point store made
+ * them) and d_tickets[0, tickets_n) to the host and stores in *nonzero how many of them are not zero.
+ * afv_debug_scratch_read: bytes [offset, offset + bytes) of slot `which` (0 .. 8) after a wait for the stream; a slot that stands for
+ * several buffers (5 .. 8) reads as one run of bytes: the stores, then the tables, in the order they were made, per table d_pairs, d_out,
+ * d_nm.  AFV_EINVAL beyond the slot's size.  All four: AFV_OK | AFV_EINVAL | AFV_EHIP. */
+enum { AFV_SCRATCH_D_MATCH = 0, AFV_SCRATCH_H_STAGE = 1, AFV_SCRATCH_D_TOPK = 2, AFV_SCRATCH_D_SLICE = 3, AFV_SCRATCH_D_L2 = 4,
+       AFV_SCRATCH_POINTS_STAGE = 5, AFV_SCRATCH_POINTS_PIN = 6, AFV_SCRATCH_TABLE_PAIRS = 7, AFV_SCRATCH_TABLE_PIN = 8, AFV_SCRATCH_SLOTS = 9 };
+int afv_debug_scratch_bytes(afv_ctx *ctx, size_t *out, int n);
+int afv_debug_paint_scratch(afv_ctx *ctx, int byte);
+int afv_debug_rest_words(afv_ctx *ctx, int32_t *nonzero);
+int afv_debug_scratch_read(afv_ctx *ctx, int which, size_t offset, void *out, size_t bytes);
+
 /* ---- fusing map points into keyframes of the table: FeatureMatcher::Fuse(pKF, vpMapPoints, th) (FeatureMatcher.cc:794-940) and
  * Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:942-1064) as LocalMapping::SearchInNeighbors (LocalMapping.cc:475-555) and
  * LoopClosing::SearchAndFuse (LoopClosing.cc:601-628) run them: the points of a resident store into up to 64 table slots in one call.
