@@ -17,6 +17,8 @@ Layout:
                  GlobalBundleAdjustment: the block-sparse route for the whole map (Optimizer.cc:53-58, LoopClosing.cc:664)
   refresh.py     RefreshMapPoints: ComputeDistinctiveDescriptors and UpdateNormalAndDepth of resident map points from the observation list
                  of the bundle adjustment (reference: MapPoint.cc:279-349, :372-418)
+  covisibility.py the covisibility count and the local map from the table's map-point planes (include/afv_covis.h) and CovisibilityGraph, the
+                 host mirror of UpdateConnections and Tracking::UpdateLocalMap (reference: KeyFrame.cc:131-219, :329-418, Tracking.cc:1040-1144)
   essgraph.py    OptimizeEssentialGraph over plain arrays and the store, the edge list of the essential graph, the Sim3 point correction
                  (reference: Optimizer.cc:771-1031, LoopClosing.cc:487-516)
   pnp.py         PnPsolver mirror: all EPnP RANSAC hypotheses of a relocalisation in one device call (reference: PnPsolver.{h,cc})
@@ -31,6 +33,8 @@ from .frame import Frame  # noqa: F401
 from .points import MapPoints  # noqa: F401
 from . import akaze, table  # noqa: F401
 from .database import KeyFrameDatabase  # noqa: F401
+from . import covisibility  # noqa: F401
+from .covisibility import CovisibilityGraph, covisibility_votes, local_points  # noqa: F401
 from .sim3 import OptimizeSim3, OptimizeSim3Batch, Sim3Solver  # noqa: F401
 from .lba import BundleAdjustment, GlobalBundleAdjustment, LocalBundleAdjustment  # noqa: F401
 from .essgraph import OptimizeEssentialGraph, essential_graph_edges  # noqa: F401

@@ -39,6 +39,7 @@
 #include <cstring>
 
 #include "afv_akaze.h"
+#include "afv_covis.h"
 #include "afv_hip.h"
 
 #ifdef AFV_WITH_OPENCV
@@ -1983,5 +1984,299 @@ inline FuseAnswer FuseIntoKeyFramesSim3(afv_ctx *ctx, afv_table *table, DeviceMa
     for (const std::array<float, 16> &S : Scw) poses.push_back(DecomposeScw(S.data()));
     return FuseRun(ctx, table, points, targets, radiusTh, th_low, false, &poses);
 }
+
+// ---- the covisibility count and the local map (include/afv_covis.h; reference: KeyFrame::UpdateConnections, AddConnection,
+// UpdateBestCovisibles and the getters, KeyFrame.cc:131-219, :329-418; Tracking::UpdateLocalKeyFrames / UpdateLocalPoints, Tracking.cc:1040-1144).
+// The device counts from the mvpMapPoints planes of the table (afv_table_set_map_points) and the flags of the store; what stays here is the
+// bookkeeping of who is connected to whom.  Keyframes are named by their table slot and ordered by their keyId. ----
+struct CovisQuery {  // one query of CovisibilityVotes: a position in the keyframe list (ids == nullptr) or a list of point ids
+    int32_t position = -1;
+    const std::vector<int32_t> *ids = nullptr;
+    int32_t th = 15;
+    bool skip_bad = false;
+};
+struct CovisAnswer {  // per query
+    std::vector<std::vector<int32_t>> votes, order;  // [nk]; the positions of the connection rule
+    std::vector<int32_t> best, n_nonzero;
+};
+inline CovisAnswer CovisibilityVotes(afv_ctx *ctx, afv_table *table, DeviceMapPoints &points, const std::vector<int32_t> &slots,
+                                     const std::vector<int32_t> &key_ids, const std::vector<uint8_t> *kf_bad, const std::vector<CovisQuery> &queries) {
+    const size_t nk = slots.size(), nq = queries.size();
+    if (key_ids.size() != nk || (kf_bad && kf_bad->size() != nk)) fatal("CovisibilityVotes: one keyId and one flag per slot", AFV_EINVAL, ctx);
+    std::vector<afv_covis_query> recs(std::max<size_t>(nq, 1));
+    for (size_t q = 0; q < nq; ++q) {
+        afv_covis_query &r = recs[q];
+        r = afv_covis_query{};
+        r.struct_size = (uint32_t)sizeof(r);
+        r.th = queries[q].th;
+        r.skip_bad = queries[q].skip_bad ? 1 : 0;
+        if (queries[q].ids) {
+            r.kind = AFV_COVIS_QUERY_IDS;
+            r.n = (int32_t)queries[q].ids->size();
+            r.ids = queries[q].ids->data();
+        } else {
+            r.kind = AFV_COVIS_QUERY_SLOT;
+            r.position = queries[q].position;
+        }
+    }
+    const size_t cells = std::max<size_t>(nq * nk, 1);
+    std::vector<int32_t> votes(cells, 0), order(cells, -1), n_order(std::max<size_t>(nq, 1), 0), best(std::max<size_t>(nq, 1), -1), nz(std::max<size_t>(nq, 1), 0);
+    const int rc = afv_table_covis_votes(table, points.handle(), slots.data(), key_ids.data(), kf_bad ? kf_bad->data() : nullptr, (int)nk, recs.data(),
+                                         (int)nq, votes.data(), order.data(), n_order.data(), best.data(), nz.data());
+    if (rc != AFV_OK) fatal("afv_table_covis_votes", rc, ctx);
+    CovisAnswer A;
+    for (size_t q = 0; q < nq; ++q) {
+        A.votes.emplace_back(votes.begin() + q * nk, votes.begin() + (q + 1) * nk);
+        A.order.emplace_back(order.begin() + q * nk, order.begin() + q * nk + n_order[q]);
+        A.best.push_back(best[q]);
+        A.n_nonzero.push_back(nz[q]);
+    }
+    return A;
+}
+struct LocalPointsAnswer {
+    std::vector<int32_t> ids;   // localPts in the reference's order
+    std::vector<uint8_t> seen;  // 1: a point of the frame (SearchLocalPoints skips it); empty without frame_pts
+};
+// Tracking::UpdateLocalPoints over `local`, the slots in the order of localKeyframes; cap = the table's features per slot
+inline LocalPointsAnswer LocalPoints(afv_ctx *ctx, afv_table *table, int cap, DeviceMapPoints &points, const std::vector<int32_t> &local,
+                                     const std::vector<int32_t> *frame_pts) {
+    const size_t room = std::max<size_t>(local.size() * (size_t)cap, 1);
+    LocalPointsAnswer A;
+    A.ids.assign(room, -1);
+    if (frame_pts) A.seen.assign(room, 0);
+    int32_t n = 0;
+    const int rc = afv_table_local_points(table, points.handle(), local.data(), (int)local.size(), frame_pts && !frame_pts->empty() ? frame_pts->data() : nullptr,
+                                          frame_pts ? (int)frame_pts->size() : 0, (int)(local.size() * (size_t)cap), A.ids.data(),
+                                          frame_pts ? A.seen.data() : nullptr, &n);
+    if (rc != AFV_OK) fatal("afv_table_local_points", rc, ctx);
+    A.ids.resize((size_t)n);
+    if (frame_pts) A.seen.resize((size_t)n);
+    return A;
+}
+
+class CovisibilityGraph {
+  public:
+    struct Node {  // the connection members of one KeyFrame
+        int32_t slot = -1, key_id = -1;
+        bool bad = false, first = true;
+        std::map<int32_t, int32_t> weights;          // connectedKeyFrameWeights: slot -> weight
+        std::vector<int32_t> ordered, ordered_w;     // orderedConnectedKeyFrames / orderedWeights
+        int32_t parent = -1;                         // -1: none
+        std::set<int32_t> children, loop_edges;
+    };
+    struct LocalMap {
+        bool valid = false;                          // false: the reference returns before it touches the local map
+        std::vector<int32_t> keyframes;              // localKeyframes (slots)
+        int32_t ref = -1;                            // refKeyframe | -1
+        std::vector<int32_t> ids;                    // localPts
+        std::vector<uint8_t> seen;
+    };
+    int th = 15;  // KeyFrame.cc:369
+
+    CovisibilityGraph(afv_ctx *ctx_, afv_table *table_, int cap_, DeviceMapPoints &points_) : ctx(ctx_), table(table_), cap(cap_), points(points_) {}
+
+    void add_keyframe(int32_t slot, int32_t key_id) {
+        if (kf.count(slot)) fatal("CovisibilityGraph::add_keyframe: the slot is listed", AFV_EINVAL, ctx);
+        for (const auto &e : kf)
+            if (e.second.key_id == key_id) fatal("CovisibilityGraph::add_keyframe: the keyId is listed", AFV_EINVAL, ctx);
+        Node n;
+        n.slot = slot;
+        n.key_id = key_id;
+        kf[slot] = n;
+        listed.push_back(slot);
+    }
+    void set_bad(int32_t slot, bool bad = true) { node(slot).bad = bad; }
+
+    void UpdateConnections(int32_t slot) { UpdateConnectionsBatch({slot}); }
+    // one device call per 64 slots: the planes are read as they stand at the call, the host side effects are applied in list order
+    void UpdateConnectionsBatch(const std::vector<int32_t> &batch) {
+        std::vector<int32_t> keys;
+        std::map<int32_t, int32_t> pos;
+        for (size_t p = 0; p < listed.size(); ++p) {
+            keys.push_back(kf[listed[p]].key_id);
+            pos[listed[p]] = (int32_t)p;
+        }
+        for (size_t at = 0; at < batch.size(); at += AFV_COVIS_MAX_QUERIES) {
+            const size_t end = std::min(batch.size(), at + AFV_COVIS_MAX_QUERIES);
+            std::vector<CovisQuery> qs;
+            for (size_t b = at; b < end; ++b) {
+                if (!pos.count(batch[b])) fatal("CovisibilityGraph::UpdateConnections: unknown slot", AFV_EINVAL, ctx);
+                CovisQuery q;
+                q.position = pos[batch[b]];
+                q.th = th;
+                qs.push_back(q);
+            }
+            const CovisAnswer A = CovisibilityVotes(ctx, table, points, listed, keys, nullptr, qs);
+            for (size_t b = at; b < end; ++b) Apply(batch[b], A.votes[b - at], A.order[b - at]);
+        }
+    }
+
+    std::vector<int32_t> GetVectorCovisibleKeyFrames(int32_t slot) { return node(slot).ordered; }
+    std::vector<int32_t> GetBestCovisibilityKeyFrames(int32_t slot, int N = 10) {
+        const Node &n = node(slot);
+        return std::vector<int32_t>(n.ordered.begin(), n.ordered.begin() + std::min<size_t>(n.ordered.size(), (size_t)std::max(N, 0)));
+    }
+    std::vector<int32_t> GetCovisiblesByWeight(int32_t slot, int w) {
+        const Node &n = node(slot);
+        size_t k = 0;
+        while (k < n.ordered_w.size() && n.ordered_w[k] >= w) ++k;  // upper_bound with weightComp
+        if (k == n.ordered_w.size()) return {};                     // it == end(): the reference answers an empty vector
+        return std::vector<int32_t>(n.ordered.begin(), n.ordered.begin() + k);
+    }
+    int GetWeight(int32_t slot, int32_t other) {
+        const Node &n = node(slot);
+        const auto it = n.weights.find(other);
+        return it == n.weights.end() ? 0 : it->second;
+    }
+    std::vector<int32_t> GetConnectedKeyFrames(int32_t slot) {  // ascending keyId, as the reference's map
+        std::vector<int32_t> out;
+        for (const auto &e : node(slot).weights) out.push_back(e.first);
+        std::sort(out.begin(), out.end(), [&](int32_t a, int32_t b) { return kf[a].key_id < kf[b].key_id; });
+        return out;
+    }
+    void EraseConnection(int32_t slot, int32_t other) {
+        Node &n = node(slot);
+        if (n.weights.erase(other)) Reorder(n);
+    }
+    int32_t GetParent(int32_t slot) { return node(slot).parent; }
+    std::vector<int32_t> GetChilds(int32_t slot) {  // ascending keyId (the reference's set is ordered by pointer)
+        const Node &n = node(slot);
+        std::vector<int32_t> out(n.children.begin(), n.children.end());
+        std::sort(out.begin(), out.end(), [&](int32_t a, int32_t b) { return kf[a].key_id < kf[b].key_id; });
+        return out;
+    }
+    void AddLoopEdge(int32_t slot, int32_t other) { node(slot).loop_edges.insert(other); }
+    // the pieces the edge list of OptimizeEssentialGraph is built from, keyed by keyId, over the keyframes that are not bad
+    struct EssentialGraphPieces {
+        std::map<int32_t, int32_t> parent;  // keyId -> keyId of the parent | -1
+        std::map<int32_t, std::vector<int32_t>> loop_edges, covisibles;  // ascending keyId; GetCovisiblesByWeight(min_feat) in its order
+    };
+    EssentialGraphPieces essential_graph_dict(int min_feat = 100) {
+        EssentialGraphPieces P;
+        for (int32_t s : listed) {
+            const Node &n = kf[s];
+            if (n.bad) continue;
+            P.parent[n.key_id] = n.parent < 0 ? -1 : kf[n.parent].key_id;
+            std::vector<int32_t> le;
+            for (int32_t o : n.loop_edges) le.push_back(kf[o].key_id);
+            std::sort(le.begin(), le.end());
+            P.loop_edges[n.key_id] = le;
+            std::vector<int32_t> cv;
+            for (int32_t o : GetCovisiblesByWeight(s, min_feat)) cv.push_back(kf[o].key_id);
+            P.covisibles[n.key_id] = cv;
+        }
+        return P;
+    }
+    // what KeyFrameDatabase::DetectLoopCandidates / min_score_to_connected take as `connected` (a list) ...
+    std::vector<int> connected(int32_t slot) {
+        const std::vector<int32_t> c = GetConnectedKeyFrames(slot);
+        return std::vector<int>(c.begin(), c.end());
+    }
+    // ... and what it and DetectRelocalizationCandidates take as `best_covisibles` (a callable): GetBestCovisibilityKeyFrames(10)
+    std::function<std::vector<int>(int)> best_covisibles() {
+        return [this](int slot) {
+            const std::vector<int32_t> c = GetBestCovisibilityKeyFrames(slot, 10);
+            return std::vector<int>(c.begin(), c.end());
+        };
+    }
+    const Node &GetNode(int32_t slot) { return node(slot); }
+
+    // Tracking::UpdateLocalMap: frame_pts = the point ids of the current frame, -1 = none
+    LocalMap UpdateLocalMap(const std::vector<int32_t> &frame_pts, size_t max_keyframes = 80, int best_cov = 10) {
+        LocalMap M;
+        if (listed.empty()) return M;
+        std::vector<int32_t> keys;
+        std::vector<uint8_t> bad;
+        for (int32_t s : listed) {
+            keys.push_back(kf[s].key_id);
+            bad.push_back(kf[s].bad ? 1 : 0);
+        }
+        CovisQuery q;
+        q.ids = &frame_pts;
+        q.th = 1;
+        q.skip_bad = true;
+        const CovisAnswer A = CovisibilityVotes(ctx, table, points, listed, keys, &bad, {q});
+        if (A.n_nonzero[0] == 0) return M;
+        M.valid = true;
+        for (int32_t p : A.order[0]) M.keyframes.push_back(listed[(size_t)p]);
+        std::sort(M.keyframes.begin(), M.keyframes.end(), [&](int32_t a, int32_t b) { return kf[a].key_id < kf[b].key_id; });  // the map iteration
+        M.ref = A.best[0] >= 0 ? listed[(size_t)A.best[0]] : -1;
+        std::set<int32_t> have(M.keyframes.begin(), M.keyframes.end());
+        const size_t first_phase = M.keyframes.size();  // the range-for reads end() once: keyframes pushed below are not walked
+        auto take = [&](int32_t s) {
+            if (kf[s].bad || have.count(s)) return false;
+            M.keyframes.push_back(s);
+            have.insert(s);
+            return true;
+        };
+        for (size_t k = 0; k < first_phase; ++k) {
+            if (M.keyframes.size() > max_keyframes) break;
+            const int32_t s = M.keyframes[k];
+            for (int32_t nb : GetBestCovisibilityKeyFrames(s, best_cov))
+                if (take(nb)) break;
+            for (int32_t ch : GetChilds(s))
+                if (take(ch)) break;
+            const int32_t pa = kf[s].parent;
+            if (pa >= 0 && take(pa)) break;
+        }
+        LocalPointsAnswer L = LocalPoints(ctx, table, cap, points, M.keyframes, &frame_pts);
+        M.ids.swap(L.ids);
+        M.seen.swap(L.seen);
+        return M;
+    }
+
+  private:
+    Node &node(int32_t slot) {
+        const auto it = kf.find(slot);
+        if (it == kf.end()) fatal("CovisibilityGraph: unknown slot", AFV_EINVAL, ctx);
+        return it->second;
+    }
+    // weight descending, ties by keyId descending: KeyframeComparison and push_front
+    void Reorder(Node &n) {
+        std::vector<std::pair<int32_t, int32_t>> pairs;  // (weight, slot)
+        for (const auto &e : n.weights) pairs.emplace_back(e.second, e.first);
+        std::sort(pairs.begin(), pairs.end(), [&](const std::pair<int32_t, int32_t> &a, const std::pair<int32_t, int32_t> &b) {
+            return a.first != b.first ? a.first > b.first : kf[a.second].key_id > kf[b.second].key_id;
+        });
+        n.ordered.clear();
+        n.ordered_w.clear();
+        for (const auto &e : pairs) {
+            n.ordered.push_back(e.second);
+            n.ordered_w.push_back(e.first);
+        }
+    }
+    void AddConnection(Node &n, int32_t other, int32_t weight) {  // KeyFrame.cc:131-146
+        const auto it = n.weights.find(other);
+        if (it != n.weights.end() && it->second == weight) return;
+        n.weights[other] = weight;
+        Reorder(n);
+    }
+    void Apply(int32_t slot, const std::vector<int32_t> &row, const std::vector<int32_t> &order) {  // KeyFrame.cc:361-417
+        Node &n = node(slot);
+        std::map<int32_t, int32_t> counter;
+        for (size_t p = 0; p < row.size(); ++p)
+            if (row[p] > 0) counter[listed[p]] = row[p];
+        if (counter.empty()) return;
+        for (int32_t p : order) AddConnection(kf[listed[(size_t)p]], slot, row[(size_t)p]);
+        n.weights = counter;  // the whole counter, not only the entries at the threshold (KeyFrame.cc:405)
+        n.ordered.clear();
+        n.ordered_w.clear();
+        for (int32_t p : order) {
+            n.ordered.push_back(listed[(size_t)p]);
+            n.ordered_w.push_back(row[(size_t)p]);
+        }
+        if (n.first && n.key_id != 0) {
+            n.parent = n.ordered.front();
+            kf[n.parent].children.insert(slot);
+            n.first = false;
+        }
+    }
+    afv_ctx *ctx;
+    afv_table *table;
+    int cap;
+    DeviceMapPoints &points;
+    std::map<int32_t, Node> kf;
+    std::vector<int32_t> listed;  // the slots in the order they were added
+};
 
 }  // namespace afv

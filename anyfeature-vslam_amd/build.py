@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libafv_hip.so")
 SOURCES = ["k_pyramid.hip", "k_fast.hip", "k_harris.hip", "k_select.hip", "k_describe.hip", "k_match.hip", "k_match_mfma.hip", "k_project.hip", "k_bow.hip", "k_bowvec.hip", "k_match_l2.hip", "k_frame.hip",
-           "afv_api.hip", "afv_extract.hip", "afv_comm.hip", "afv_match_jobs.hip", "afv_project.hip", "afv_frame.hip", "k_akaze.hip", "k_akaze_detect.hip", "k_akaze_desc.hip", "akaze_api.hip", "akaze_plan.hip", "k_voctrain.hip", "afv_voctrain.hip", "k_stereo.hip", "afv_stereo.hip", "k_points.hip", "afv_points.hip", "k_poseopt.hip", "afv_poseopt.hip", "k_triangulate.hip", "afv_triangulate.hip", "k_newpoints.hip", "afv_newpoints.hip", "k_sim3.hip", "afv_sim3.hip", "k_init.hip", "afv_init.hip", "k_pnp.hip", "afv_pnp.hip", "k_sim3opt.hip", "afv_sim3opt.hip", "k_lba.hip", "afv_lba.hip", "k_gba.hip", "k_refresh.hip", "afv_refresh.hip", "k_essgraph.hip", "afv_essgraph.hip", "afv_kffuse.hip"]
+           "afv_api.hip", "afv_extract.hip", "afv_comm.hip", "afv_match_jobs.hip", "afv_project.hip", "afv_frame.hip", "k_akaze.hip", "k_akaze_detect.hip", "k_akaze_desc.hip", "akaze_api.hip", "akaze_plan.hip", "k_voctrain.hip", "afv_voctrain.hip", "k_stereo.hip", "afv_stereo.hip", "k_points.hip", "afv_points.hip", "k_poseopt.hip", "afv_poseopt.hip", "k_triangulate.hip", "afv_triangulate.hip", "k_newpoints.hip", "afv_newpoints.hip", "k_sim3.hip", "afv_sim3.hip", "k_init.hip", "afv_init.hip", "k_pnp.hip", "afv_pnp.hip", "k_sim3opt.hip", "afv_sim3opt.hip", "k_lba.hip", "afv_lba.hip", "k_gba.hip", "k_refresh.hip", "afv_refresh.hip", "k_essgraph.hip", "afv_essgraph.hip", "afv_kffuse.hip", "k_covis.hip", "afv_covis.hip"]
 BASE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
               "-Wall", "-Wno-unused-function"]
 # no packed-fp32 instructions (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 / v_pk_mov_b32), in any kernel: with an operand broadcast

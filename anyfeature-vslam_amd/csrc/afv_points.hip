@@ -25,6 +25,7 @@ static void points_free(afv_points *p) {
     if (p->h_pin) (void)hipHostFree(p->h_pin);
     if (p->d_block) (void)hipFree(p->d_block);
     if (p->d_stage) (void)hipFree(p->d_stage);
+    if (p->d_covis) (void)hipFree(p->d_covis);
     delete p;
 }
 

@@ -499,6 +499,7 @@ struct afv_points {
     size_t pin_bytes = 0;
     hipEvent_t ev = nullptr;     // the last upload out of h_pin (the next setter waits for it before it refills the image)
     bool ev_armed = false;
+    uint32_t *d_covis = nullptr; // afv_table_local_points (afv_covis.hip): [2][cap] first-occurrence words (0xFFFFFFFF at rest), positions; made on first use
 };
 
 #define AFV_MAX_SIDE 8192
